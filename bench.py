@@ -9,15 +9,21 @@ copied from pinned host memory on its own stream while earlier steps computed (d
 reference moves every batch inside its loop, engine/trainer.py:103-107) -- the copy of step k+2 is in flight under step
 k, so the batch IS resident when its step starts; ``--resident-input`` re-uses one device batch instead (A/B).  A step is
 forward (frozen trunk + teacher pseudo-labelling + two student passes) -> backward with the bucketed
-gradient all-reduce overlapped -> SGD.  Rank 0 prints ONE JSON line with the fields the driver reads,
-plus
+gradient all-reduce overlapped -> SGD.  Rank 0 prints ONE JSON line with the fields the driver reads.  A plain run
+does only what that headline needs: set-up, clock warm-up, W warm-up steps, the K timed steps, the outputs of the last
+timed step when ``--dump-outputs DIR`` is given (DIR/<name>.npy: every loss term, and a seeded sample of every trainable
+parameter's gradient), the line.  ``--full`` adds
+  replay       : a few sequential steps after the timed region, for the per-kernel figures below;
+  secondary    : a short timed region of the teacher configuration (student workload only, --secondary-steps);
   roofline     : the hand-written kernel the step spends most time in (the pair-layout split GEMM of the res5
                  head / frozen trunk: matrix-core bound, bf16 MFMA flops issued / HIP-event time against the
                  2.5 PFLOP/s dense bf16 peak; a byte kernel would be priced against the 8 TB/s HBM peak),
                  measured with HIP events on the launch stream (sequential replay when the step is pipelined);
   kernels      : the same for every native op that ran;
+  config.roi_align_856MB : the one-second RoIAlign micro-benchmark (N=1);
   cpu_baseline : the reference's own CPU kernels (oracle/_ref; falls back to the C port) on the native-op
                  work of ONE image of the same step, on the host cores (N=1, rank 0 only).
+Without ``--full`` those fields are null (``kernels`` empty, ``replay_steps`` 0) and ``cpu_baseline`` is absent.
 """
 import argparse
 import json
@@ -509,6 +515,41 @@ def cpu_baseline(workload):
             "host_cpus": os.cpu_count(), "host_seconds": round(host_s, 1)}
 
 
+GRAD_SAMPLE_PER_PARAM = 4096
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(loss_dict, model):
+    """What a caller of the timed step holds after its last call, as host arrays: every loss term the step returned
+    (float64, named after the term) and ``grad_sample`` -- up to GRAD_SAMPLE_PER_PARAM entries of every trainable
+    parameter's gradient in ``named_parameters`` order, at indices drawn from a fixed seed (float32; all gradients would
+    be several times the 64 MB the dump may take)."""
+    import re
+    out = {re.sub(r"[^\w.-]", "_", k): v.detach().double().cpu().numpy() for k, v in loss_dict.items()}
+    g = torch.Generator().manual_seed(4321)
+    parts = []
+    for _, p in model.named_parameters():
+        if not p.requires_grad or p.grad is None:
+            continue
+        flat = p.grad.detach().reshape(-1)
+        if flat.numel() > GRAD_SAMPLE_PER_PARAM:
+            idx = torch.randint(0, flat.numel(), (GRAD_SAMPLE_PER_PARAM,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    out["grad_sample"] = (torch.cat(parts) if parts else torch.zeros(0)).numpy()
+    return out
+
+
+def write_outputs(outputs, path):
+    import numpy as np
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 TINY_OVERRIDES = ["MODEL.RPN.PRE_NMS_TOP_N_TRAIN", 300, "MODEL.RPN.PRE_NMS_TOP_N_TEST", 200, "MODEL.RPN.POST_NMS_TOP_N_TRAIN", 60,
                   "MODEL.RPN.POST_NMS_TOP_N_TEST", 40, "MODEL.ROI_HEADS.BATCH_SIZE_PER_IMAGE", 16]
 TINY_BATCH = dict(height=128, width=160, num_gt=3, num_nouns=2, n_vocab=50)
@@ -577,6 +618,12 @@ def parse_args(argv=None):
     ap.add_argument("--contention-copy-mb", type=float, default=0.0,
                     help="per step, device-to-device copies of this many MB in three pieces on a separate stream (an upper bound "
                          "on what an N-GPU job's gradient exchange costs the backward it overlaps; see Feed.add_contention)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: sequential replay with per-kernel / roofline figures, the secondary (teacher) "
+                         "region, the RoIAlign micro-benchmark and the CPU baseline (the --no-* switches below thin it out)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: every loss term "
+                         "(float64) and grad_sample (float32: a seeded sample of every trainable parameter's gradient)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roi-micro", action="store_true",
                     help="skip the one-second RoIAlign micro-benchmark (config.roi_align_backward_856MB) after the steps")
@@ -584,10 +631,10 @@ def parse_args(argv=None):
                     help="extend the timed region to at least this long (steps are added; the JSON reports the count)")
     ap.add_argument("--burn-seconds", type=float, default=3.0, help="GPU clock warm-up before the warm-up steps")
     ap.add_argument("--no-pipeline", action="store_true", help="plain sequential step (no side-stream overlap)")
-    ap.add_argument("--per-shape-csv", default="", help="write one row per distinct split-GEMM shape of the step")
+    ap.add_argument("--per-shape-csv", default="", help="write one row per distinct split-GEMM shape of the step (needs --full)")
     ap.add_argument("--secondary-steps", type=int, default=10,
-                    help="after the student region: this many timed steps of the teacher configuration (zeroshot_mask.yaml, "
-                         "BASELINE config 2) reported under `secondary`; 0 = skip")
+                    help="with --full, after the student region: this many timed steps of the teacher configuration "
+                         "(zeroshot_mask.yaml, BASELINE config 2) reported under `secondary`; 0 = skip")
     # DRY RUN of the multi-rank control flow without GPUs: the same rank code (rendezvous, parameter broadcast, barriers,
     # step-count calibration, MAX-reduce of the elapsed time, replay on every rank with live all-reduces, per-rank gather)
     # on the product's own host path (MODEL.DEVICE cpu, BASELINE configs[0]) over gloo.  Never a measurement.
@@ -603,6 +650,8 @@ def parse_args(argv=None):
     ap.add_argument("--host-batches", type=int, default=4, help="distinct pinned host batches the staged input stream cycles through")
     ap.add_argument("--fault-inject", default="", help=argparse.SUPPRESS)  # "RANK:STEP": that rank dies inside the timed region (tests)
     args = ap.parse_args(argv)
+    if args.per_shape_csv and not args.full:
+        ap.error("--per-shape-csv comes from the sequential replay of --full")
     return args
 
 
@@ -817,7 +866,7 @@ def main():
 
     name, model, feed, reducer, pipe = build_workload(args, args.workload, dev, world, rank, args.warmup)
     timer = OpTimer(_C)
-    if on_gpu:
+    if on_gpu and args.full:
         timer.install()
 
     def sync():
@@ -844,7 +893,8 @@ def main():
         feed.step(pipe)
     sync()
     overlapped = pipe.enabled
-    timer.enabled = on_gpu and not overlapped  # sequential workloads: per-kernel HIP-event timing live in the timed region
+    # sequential workloads under --full: per-kernel HIP-event timing live in the timed region
+    timer.enabled = on_gpu and args.full and not overlapped
     if args.min_seconds > 0:  # calibrate the step count on a short untimed probe (same count on every rank)
         t0 = time.perf_counter()
         for _ in range(3):
@@ -871,11 +921,13 @@ def main():
     own_elapsed = elapsed = time.perf_counter() - t0
     chunk_ms = [1e3 * (b[1] - a[1]) / (b[0] - a[0]) for a, b in zip(marks[:-1], marks[1:])]
     pipe.drain()
+    if args.dump_outputs and rank == 0:
+        write_outputs(last_step_outputs(loss_dict, model), args.dump_outputs)
     waits = reducer.exposed_wait_ms()
     hook_launches, n_buckets = reducer.hook_launches, len(reducer.buckets)
     timer.enabled = False
     replay_steps = 0
-    if overlapped or not on_gpu:
+    if args.full and (overlapped or not on_gpu):
         # In the pipelined step two streams share the GPU, so an event pair around one kernel also spans kernels of the
         # other stream.  The per-kernel roofline figures therefore come from a sequential replay of the same step
         # right after the timed region (same launches, one stream); `value` is the pipelined, timed region only.
@@ -918,7 +970,7 @@ def main():
     # both sides, MAX over ranks); the student model is released first.
     secondary = None
     shape_rows = per_shape_rows(timer, replay_steps or args.steps) if (args.per_shape_csv and rank == 0) else None
-    if args.workload == "student" and args.secondary_steps > 0:
+    if args.full and args.workload == "student" and args.secondary_steps > 0:
         kernels_primary = timer.summary() if rank == 0 else None
         timer.records.clear()
         for k in timer.bytes:
@@ -947,10 +999,10 @@ def main():
         k = kernels.get(dom, {"bound": "hbm", "achieved_GBps": 0.0})
         measured_in = (f"{replay_steps} sequential replay steps after the timed region (the timed steps overlap two "
                        "streams)") if replay_steps else "the timed region"
-        traffic, traffic_note = pmc_traffic(args.workload, dom)
-        mfma_busy, mfma_busy_note = pmc_mfma_busy(args.workload, dom)
+        traffic, traffic_note = pmc_traffic(args.workload, dom) if kernels else (None, None)
+        mfma_busy, mfma_busy_note = pmc_mfma_busy(args.workload, dom) if kernels else (None, None)
         if not kernels:
-            roofline = None  # dry run on the host path: nothing was launched on a GPU
+            roofline = None  # no --full, or a dry run on the host path: no kernel was timed
         elif k["bound"] == "mfma":
             roofline = {"bound": "mfma", "kernel": dom, "achieved": k["achieved_TFLOPs"], "peak": MFMA_BF16_PEAK_TFLOPS,
                         "unit": "TFLOP/s", "frac": k["achieved_TFLOPs"] / MFMA_BF16_PEAK_TFLOPS,
@@ -1033,7 +1085,7 @@ def main():
                         "rounds_of_resident_workgroups,us_per_step\n")
                 for r in shape_rows:
                     f.write(",".join(str(round(x, 3)) if isinstance(x, float) else str(x) for x in r) + "\n")
-        if world == 1 and on_gpu and not args.tiny and not args.no_roi_micro:
+        if args.full and world == 1 and on_gpu and not args.tiny and not args.no_roi_micro:
             # the a2 target's own micro-benchmark, recorded where the driver keeps it (VERDICT r5 missing-4)
             try:
                 torch.cuda.empty_cache()
@@ -1042,7 +1094,7 @@ def main():
                 out["config"]["roi_align_856MB"] = micro
             except Exception as e:  # noqa: BLE001 -- the headline is complete: report, do not lose the line
                 out["config"]["roi_align_backward_856MB"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not args.no_cpu_baseline and on_gpu:
+        if args.full and world == 1 and not args.no_cpu_baseline and on_gpu:
             out["cpu_baseline"] = cpu_baseline(args.workload)
         print(json.dumps(out), flush=True)
     if world > 1:

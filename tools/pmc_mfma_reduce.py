@@ -61,7 +61,7 @@ def main():
     dur = durations(os.path.join(out_dir, "pass1_kernel_trace.csv"))
     passes = [load(p) for p in sorted(glob.glob(os.path.join(out_dir, "pass[0-9].csv")))]
     res = {"workload": wl,
-           "command": "bash tools/pmc_mfma.sh (rocprofv3 --kernel-trace --pmc <group> -- python3 bench.py --steps 2 --warmup 2 "
+           "command": "bash tools/pmc_mfma.sh (rocprofv3 --kernel-trace --pmc <group> -- python3 bench.py --full --steps 2 --warmup 2 "
                       "--no-pipeline --no-cpu-baseline), every launch of the run",
            "formula": f"mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / ({SIMDS} x {CUS} x GRBM_GUI_ACTIVE / {XCDS}) (rocprofv3's "
                       f"MfmaUtil; the CSV sums GRBM_GUI_ACTIVE over the {XCDS} XCDs); cu_busy_frac = SQ_BUSY_CU_CYCLES / "

@@ -38,7 +38,7 @@ def load(path):
 fetch, write = load(sys.argv[1]), load(sys.argv[2])
 out = {"workload": sys.argv[3] if len(sys.argv) > 3 else "student",
        "command": "bash tools/pmc_step.sh (rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 bench.py "
-                  "--steps 2 --warmup 2 --no-pipeline), all launches of the run",
+                  "--full --steps 2 --warmup 2 --no-pipeline), all launches of the run",
        "correction": "bytes = (2 * FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950: wide reads are tallied at half their size)",
        "kernels": {}}
 for k in sorted(set(fetch) | set(write)):
