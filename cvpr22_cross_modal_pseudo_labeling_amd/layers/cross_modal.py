@@ -121,137 +121,6 @@ def linear_mfma(x, weight, bias=None):
     return _LinearMFMA.apply(x, weight, bias)
 
 
-class _SplitLinearMulti(Function):
-    """y_i = x @ w_i^T + b_i for several (w_i, b_i) sharing the operand x, as fp32-accurate GEMMs on the bf16 matrix
-    pipe: operands are split into bf16 hi + lo (csrc/split_bf16.hip) and the three products hi.hi + hi.lo + lo.hi
-    run as ONE bf16 GEMM with fp32 accumulation over a 3K-long concatenated inner dimension (hipBLASLt through
-    torch.mm(out_dtype=float32); 250-390 TFLOP/s fp32-equivalent on the res5 shapes vs 105-145 for the fp32
-    GEMM, relative error ~4e-6).  Backward: dX and dW are split products as well; dW contracts over the M rows."""
-
-    @staticmethod
-    def forward(ctx, x, *params):
-        xs = _C.split_bf16x3(x, 0)                       # [M, 3K] = [hi | hi | lo], shared by every product
-        ws = [p for p in params[0::2]]
-        outs = []
-        for w, b in zip(params[0::2], params[1::2]):
-            y = torch.mm(xs, _C.split_bf16x3(w, 1).t(), out_dtype=torch.float32)
-            if b is not None:
-                if y.shape[1] % 4 == 0:
-                    _C.bias_act_(y, b.contiguous(), None, relu=False)
-                else:
-                    y += b
-            outs.append(y)
-        ctx.save_for_backward(xs, *ws)
-        ctx.has_bias = [b is not None for b in params[1::2]]
-        ctx.k = x.shape[1]
-        return tuple(outs)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, *dys):
-        xs, *ws = ctx.saved_tensors
-        k = ctx.k
-        dx = None
-        grads = []
-        for i, (dy, w) in enumerate(zip(dys, ws)):
-            n = w.shape[0]
-            dys_ = _C.split_bf16x3(dy.contiguous(), 0)   # [M, 3N] = [hi | hi | lo]
-            if ctx.needs_input_grad[0]:
-                d = torch.mm(dys_, _C.split_bf16x3(w.t(), 1).t(), out_dtype=torch.float32)   # dY W
-                dx = d if dx is None else dx.add_(d)
-            dw = None
-            if ctx.needs_input_grad[1 + 2 * i]:
-                # dY^T X by M-contraction as ONE GEMM: columns N..3N of dys_ are [dY_hi | dY_lo], columns K..3K of the
-                # saved operand are [X_hi | X_lo], so [dY_hi | dY_lo]^T [X_hi | X_lo] holds all four hi/lo products
-                # as quadrants (the lo.lo one comes for free and is kept)
-                q = torch.mm(dys_[:, n:].t(), xs[:, k:], out_dtype=torch.float32)             # [2N, 2K]
-                dw = (q[:n, :k] + q[:n, k:]) + (q[n:, :k] + q[n:, k:])
-            db = dy.sum(0) if (ctx.has_bias[i] and ctx.needs_input_grad[2 + 2 * i]) else None
-            grads += [dw, db]
-        return (dx, *grads)
-
-
-class _SplitConvSame(Function):
-    """y[R,H,W,N] = conv(x[R,H,W,C], w[N,C,KH,KW]), stride 1, zero "same" padding, NHWC, as bf16 hi/lo split GEMMs:
-    the split + im2col kernel (csrc/split_bf16.hip) lays every pixel's KH*KW neighbourhood out as one row
-    [hi taps | hi taps | lo taps], so the convolution is ONE bf16 GEMM with fp32 accumulation over 3*KH*KW*C, the data
-    gradient the same thing on dY with the rotated kernel, and the weight gradient three M-contracting GEMMs of dY^T
-    against the saved rows.  ~2x MIOpen's fp32 implicit-GEMM kernels on the res5 3x3 (which sit at ~115 TFLOP/s of
-    the 157 TFLOP/s fp32 matrix peak), relative error ~4e-6."""
-
-    @staticmethod
-    def forward(ctx, x, w):
-        r, h, wd, c = x.shape
-        n, _, kh, kw = w.shape
-        rows = _C.im2col_split_bf16x3(x, kh, kw)                                    # [M, 3*T*C]
-        wm = w.permute(0, 2, 3, 1).reshape(n, kh * kw * c)                           # [N, T*C], tap-major like rows
-        y = torch.mm(rows, _C.split_bf16x3(wm, 1).t(), out_dtype=torch.float32)
-        ctx.save_for_backward(rows, w)
-        ctx.shape = (r, h, wd, c, n, kh, kw)
-        return y  # [R*H*W, N]: no view is created inside the Function, so callers may finish it in place
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, dy):
-        rows, w = ctx.saved_tensors
-        r, h, wd, c, n, kh, kw = ctx.shape
-        t = kh * kw
-        dy = dy.contiguous().view(r, h, wd, n)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            # dX[p, c] = sum_{tap, n} dY[p - tap, n] W[n, c, tap]: the same im2col on dY with the taps reversed
-            wt = w.permute(1, 2, 3, 0).reshape(c, t * n)                             # [C, T*N]
-            dx = torch.mm(_C.im2col_split_bf16x3(dy, kh, kw, flip=True), _C.split_bf16x3(wt, 1).t(),
-                          out_dtype=torch.float32).view(r, h, wd, c)
-        if ctx.needs_input_grad[1]:
-            dys = _C.split_bf16x3(dy.view(-1, n), 0)                                 # [M, 3N] = [hi | hi | lo]
-            tc = t * c
-            # one M-contracting GEMM for all four hi/lo products: [dY_hi | dY_lo]^T [rows_hi | rows_lo] -> quadrants
-            q = torch.mm(dys[:, n:].t(), rows[:, tc:], out_dtype=torch.float32)      # [2N, 2*T*C]
-            dwm = (q[:n, :tc] + q[:n, tc:]) + (q[n:, :tc] + q[n:, tc:])
-            dw = dwm.view(n, kh, kw, c).permute(0, 3, 1, 2)
-        return dx, dw
-
-
-def split_conv_same(x, w):
-    """NHWC stride-1 "same" convolution (odd kernel, groups = 1, dilation 1) of x [R,H,W,C] as bf16 hi/lo split
-    GEMMs; returns the fp32 result as the [R*H*W, N] matrix (view it as [R,H,W,N]); bias / activation are left to
-    ``bias_relu_``."""
-    return _SplitConvSame.apply(x, w)
-
-
-class _BiasActInplace(Function):
-    """y <- relu(y + bias (+ residual)) in one pass over y (csrc/split_bf16.hip::bias_act_kernel); the backward is the
-    ReLU gate on the saved output, shared by y and the residual."""
-
-    @staticmethod
-    def forward(ctx, y, bias, residual):
-        _C.bias_act_(y, bias, residual, relu=True)
-        ctx.mark_dirty(y)
-        ctx.save_for_backward(y)
-        ctx.has = (bias is not None, residual is not None)
-        return y
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        (out,) = ctx.saved_tensors
-        gi = torch.ops.aten.threshold_backward(g, out, 0.0)
-        db = gi.sum(0) if (ctx.has[0] and ctx.needs_input_grad[1]) else None
-        return gi, db, (gi if ctx.has[1] else None)
-
-
-def bias_relu_(y, bias=None, residual=None):
-    """In place on the contiguous [rows, cols] f32 tensor y: relu(y + bias[col] (+ residual)).  y must be a tensor
-    autograd allows to be modified in place (the fresh output of a GEMM)."""
-    return _BiasActInplace.apply(y, bias, residual)
-
-
-def split_linear(x, *weights_and_biases):
-    """(x @ w0^T + b0, x @ w1^T + b1, ...) with x [M,K] and w_i [N_i,K] f32: bf16 hi/lo split GEMMs, fp32 results."""
-    return _SplitLinearMulti.apply(x, *weights_and_biases)
-
-
 def text_logits(region_emb, class_emb):
     """einsum('pe,ce->pc'): region embeddings [P,E] against the class / vocabulary matrix [C,E]."""
     return linear_mfma(region_emb, class_emb, None)

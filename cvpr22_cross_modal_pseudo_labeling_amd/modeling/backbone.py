@@ -6,15 +6,23 @@ maskrcnn_benchmark/modeling/backbone/resnet.py:81-152 (``ResNet``), :155-204 (``
 checkpoints (``backbone.body.*``, ``roi_heads.box.feature_extractor.head.layer4.*``) load by name.
 
 MI355X-first difference: the reference runs ``x * scale + shift`` as a separate memory-bound
-pass after every convolution (layers/batch_norm.py:19-31).  Here each conv+FrozenBN pair is one
-MIOpen call with the affine folded into the weights (``w * scale``) and bias (``shift``); the fold
-is a weight-sized op, differentiable w.r.t. the conv weight, and cached for frozen modules.
+pass after every convolution (layers/batch_norm.py:19-31).  Here the affine is folded into the
+convolutions, and a bottleneck has two routes:
+
+* the pair route (``Bottleneck.pair_supported()`` on a device tensor): the whole block is one
+  autograd node on the pair-layout split GEMM (layers/pair_bottleneck.py), NHWC, with the fold
+  inside its weight preparation;
+* the reference route (``Bottleneck.forward``, NCHW): each conv+FrozenBN pair is one convolution
+  with the affine folded into the weights (``w * scale``) and bias (``shift``); the fold is a
+  weight-sized op, differentiable w.r.t. the conv weight, and cached for frozen modules.  Host
+  tensors take it, and so does a block off the pair route inside an NHWC chain (deformable,
+  grouped, a strided 3x3), between two layout copies.
 """
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..layers import Conv2d, DFConv2d, FrozenBatchNorm2d, bias_relu_, split_conv_same, split_linear
+from ..layers import Conv2d, DFConv2d, FrozenBatchNorm2d
 from ..layers.pair_bottleneck import bottleneck_pair, is_placeholder, pair_weight
 
 
@@ -86,11 +94,6 @@ class Bottleneck(nn.Module):
         self._f2 = [ConvBN(self.conv2, self.bn2)] if not self.with_dcn else None
         self._f3 = [ConvBN(self.conv3, self.bn3)]
         self._fd = [ConvBN(self.downsample[0], self.downsample[1])] if self.downsample is not None else None
-        self.conv3x3_nchw = None  # None = by autograd mode (see forward_nhwc)
-        # pair-layout split GEMM with fused epilogues and implicit 3x3 (csrc/split_gemm.hip): the NHWC route.  The other
-        # attribute combinations (K-concatenated split through a library GEMM, fp32 GEMM, per-layer 3x3) are the earlier
-        # forms of the same block, kept as cross-checks: tests/test_heads_gpu.py sets them explicitly
-        self.split_gemm = self.split_conv = self.pair_gemm = True
         # a block that hands its result on in pair layout (want_pair) does not also write it as fp32: the next block
         # takes its identity shortcut from the pair form (hi + lo).  False = fp32 + pair (cross-check in the tests)
         self.pair_only_chain = True
@@ -107,15 +110,10 @@ class Bottleneck(nn.Module):
         out += identity
         return F.relu_(out)
 
-    def nhwc_supported(self):
-        c1, c2, c3 = self.conv1, self.conv2, self.conv3
-        return (not self.with_dcn and c1.kernel_size == (1, 1) and c3.kernel_size == (1, 1) and c1.groups == 1 and c3.groups == 1
-                and c1.padding == (0, 0) and c3.padding == (0, 0) and c3.stride == (1, 1))
-
     def pair_supported(self):
         c1, c2, c3 = self.conv1, self.conv2, self.conv3
         d = self.downsample[0] if self.downsample is not None else None
-        return (self.nhwc_supported() and c2.stride == (1, 1) and c2.dilation == (1, 1) and c2.groups == 1
+        return (not self.with_dcn and c2.stride == (1, 1) and c2.dilation == (1, 1) and c2.groups == 1
                 and c2.kernel_size[0] % 2 == 1 and c2.kernel_size[1] % 2 == 1
                 and c2.padding == (c2.kernel_size[0] // 2, c2.kernel_size[1] // 2)
                 and all(ch % 32 == 0 for ch in (c1.in_channels, c1.out_channels, c2.out_channels, c3.out_channels))
@@ -126,7 +124,7 @@ class Bottleneck(nn.Module):
     def prep_plan_convs(self):
         """[(weight, scale)] of conv1, conv2, conv3 (, downsample) for ``prepare_weights_ahead`` when this block trains on the
         pair GEMM of a device; the scales are the very tensors ``_pair_node`` passes on (``FrozenBatchNorm2d.fold``)."""
-        if not (self.pair_gemm and self.pair_supported()):
+        if not self.pair_supported():
             return None
         ws = [self.conv1.weight, self.conv2.weight, self.conv3.weight] + ([self.downsample[0].weight] if self.downsample is not None else [])
         if not (any(w.requires_grad for w in ws) and all(w.is_cuda and w.is_contiguous() for w in ws)):
@@ -137,7 +135,7 @@ class Bottleneck(nn.Module):
     def takes_pair_only_input(self):
         """This block can consume an input that exists in pair layout only (conv1 operand and shortcut from the pair form):
         what a producer must check before it drops the fp32 copy of its output (``pair_only``)."""
-        return bool(self.pair_gemm and self.pair_supported())
+        return self.pair_supported()
 
     def _forward_pair(self, x, prestrided, xp, want_pair, pool=False, select=None, pair_only=False, pool_only_ok=False):
         """The block as ONE autograd node on the pair-layout split GEMM (layers/pair_bottleneck.py): bias, shortcut,
@@ -205,107 +203,47 @@ class Bottleneck(nn.Module):
 
     def forward_nhwc(self, x, prestrided=False, xp=None, want_pair=False, pool=False, select=None, pair_only=False,
                      pool_only_ok=False):
-        """Same block on an NHWC tensor ``x`` [R, H, W, C] (contiguous); ``prestrided``: x already holds only the
-        positions conv1 / the shortcut read (the pooler applied their common stride).  The 1x1 convolutions -- 53 % of the
-        res5 FLOPs -- become ONE row-major GEMM over all R*H*W positions each ([R*H*W, Cin] x [Cin, Cout], bias
-        = the folded FrozenBN shift) instead of R batched [Cout, Cin] x [Cin, 49] products behind layout
-        transposes; a stride-2 1x1 (STRIDE_IN_1X1) first drops the rows it never reads.  By default the GEMMs run as
-        bf16 hi/lo split products on the bf16 matrix pipe (~4e-6 relative error, ``split_gemm = False`` selects
-        the fp32 GEMM); the 3x3 goes through MIOpen.  Values equal ``forward`` up to that error.
-        ``xp``: the pair-layout form of x when the producer already wrote it; ``want_pair``: also return the pair
-        form of the result (or None) for the next block -- both only used by the pair-layout route.  ``pair_only``: the
+        """Same block on an NHWC tensor ``x`` [R, H, W, C].  On a device tensor a block that is ``pair_supported()``
+        takes the pair route (``_forward_pair``).  ``prestrided``: x already holds only the positions conv1 / the
+        shortcut read (the pooler applied their common stride); ``xp``: the pair-layout form of x when the producer
+        already wrote it; ``want_pair``: also return the pair form of the result for the next block; ``pair_only``: the
         consumer of the result ``takes_pair_only_input()``, so the fp32 copy may be dropped (the caller looks ahead:
-        ``chain_nhwc``); a block that is NOT on the pair route never receives such an input."""
-        if self.pair_gemm and x.is_cuda and self.pair_supported():
+        ``chain_nhwc``); ``pool`` / ``select`` / ``pool_only_ok``: see ``bottleneck_pair``.
+        Otherwise (a host tensor, a block off the pair route) the reference route: ``forward`` between two layout
+        copies.  It refuses a pre-strided or pair-only input, ignores ``xp``, ``pool``, ``select`` and ``pool_only_ok``
+        (callers fall back when ``_ovis_pooled`` / ``_ovis_selected`` are absent) and hands on no pair form:
+        ``(y, None)`` with ``want_pair``."""
+        if x.is_cuda and self.pair_supported():
             return self._forward_pair(x, prestrided, xp, want_pair, pool, select, pair_only, pool_only_ok)
         if is_placeholder(x):
             raise RuntimeError("Bottleneck.forward_nhwc: the input exists in pair layout only (its fp32 handle is a "
                                "placeholder) but this block is not on the pair-GEMM route; the producer must keep the "
                                "fp32 copy (pair_only=False)")
-        r, h, w, c = x.shape
-        sy, sx = self.conv1.stride
         if prestrided:
-            assert self._fd is None or self.downsample[0].stride == (sy, sx)
-            xs = x
-        else:
-            xs = x[:, ::sy, ::sx, :].contiguous() if (sy, sx) != (1, 1) else x
-        hs, ws = xs.shape[1], xs.shape[2]
-        x2d = xs.view(-1, c)
-        # raw products (no bias): bf16 hi/lo split GEMMs on the bf16 matrix pipe (layers/cross_modal.py::split_linear)
-        # or fp32 GEMMs; every bias / shortcut add / ReLU below is ONE fused in-place pass (bias_relu_)
-        if self.split_gemm:
-            def products(a, *ws):
-                return split_linear(a, *[t for w_ in ws for t in (w_, None)])
-        else:
-            def products(a, *ws):
-                return tuple(torch.mm(a, w_.t()) for w_ in ws)
-        w1, b1 = self._f1[0].folded()
-        w1 = w1.view(w1.shape[0], -1)
-        idn, bd = None, None
-        if self._fd is not None:
-            wd, bd = self._fd[0].folded()
-            wd = wd.view(wd.shape[0], -1)
-            dy, dx = self.downsample[0].stride
-            if prestrided or (dy, dx) == (sy, sx):  # conv1 and the projection shortcut read the same rows
-                out, idn = products(x2d, w1, wd)
-            else:
-                (out,) = products(x2d, w1)
-                (idn,) = products(x[:, ::dy, ::dx, :].contiguous().view(-1, c), wd)
-        else:
-            (out,) = products(x2d, w1)
-        out = bias_relu_(out, b1)
-        w2, b2 = self._f2[0].folded()
-        c2 = self.conv2
-        if (self.split_conv and c2.stride == (1, 1) and c2.dilation == (1, 1) and c2.groups == 1
-                and c2.kernel_size[0] % 2 == 1 and c2.kernel_size[1] % 2 == 1
-                and c2.padding == (c2.kernel_size[0] // 2, c2.kernel_size[1] // 2)):
-            # the 3x3 as a bf16 hi/lo split GEMM over its im2col rows (layers/cross_modal.py::split_conv_same)
-            out = split_conv_same(out.view(r, hs, ws, out.shape[-1]), w2)  # [r*hs*ws, Cout]
-            ho, wo = hs, ws
-        else:
-            nchw = self.conv3x3_nchw
-            if nchw is None:
-                # MIOpen's NCHW fp32 Winograd is its fastest 3x3 forward for these shapes (the NHWC pick at R = 2000
-                # is a 50 TFLOP/s grouped-conv kernel), worth two 0.1 ms layout copies around it; under autograd
-                # MIOpen runs NHWC implicit-GEMM kernels for all three directions: the tensor stays channels_last
-                nchw = not (torch.is_grad_enabled() and (out.requires_grad or w2.requires_grad))
-            if nchw:
-                out = F.conv2d(out.view(r, hs, ws, out.shape[-1]).permute(0, 3, 1, 2).contiguous(), w2, None, c2.stride,
-                               c2.padding, c2.dilation, c2.groups)
-                out = out.permute(0, 2, 3, 1).contiguous()
-            else:
-                out = F.conv2d(out.view(r, hs, ws, out.shape[-1]).permute(0, 3, 1, 2),
-                               w2.contiguous(memory_format=torch.channels_last), None, c2.stride, c2.padding,
-                               c2.dilation, c2.groups)
-                out = out.permute(0, 2, 3, 1)
-                if not out.is_contiguous():
-                    out = out.contiguous()
-            ho, wo = out.shape[1], out.shape[2]
-            out = out.view(-1, out.shape[3])
-        out = bias_relu_(out, b2)
-        w3, b3 = self._f3[0].folded()
-        (out,) = products(out, w3.view(w3.shape[0], -1))
-        out = bias_relu_(out, b3 if bd is None else b3 + bd, idn if idn is not None else x.view(-1, c))
-        out = out.view(r, ho, wo, out.shape[-1])
-        return (out, None) if want_pair else out
+            raise RuntimeError("Bottleneck.forward_nhwc: a pre-strided input needs the pair-GEMM route (the reference "
+                               "forward applies conv1's stride itself)")
+        y = self(x.permute(0, 3, 1, 2).contiguous()).permute(0, 2, 3, 1).contiguous()
+        return (y, None) if want_pair else y
 
 
 def chain_nhwc(blocks, y, yp=None, first=None, last=None, then=None):
-    """Run consecutive bottlenecks on an NHWC activation.  Every block but the last hands its result on in pair layout;
-    it drops the fp32 copy (``pair_only``) only when the NEXT block can take a pair-only input -- otherwise (e.g.
-    STRIDE_IN_1X1 False: the stage's first block has a strided 3x3 and runs the per-layer route) both forms are
-    written.  ``first`` / ``last``: extra keyword arguments of the first / last block's ``forward_nhwc``.  ``then``: the
-    block a LATER call continues the chain with -- the last block then hands on ``(y, yp)`` exactly as it would inside
-    one chain (the frozen prefix of the trunk, run ahead on a side stream: ``ResNetC4.forward_prefix``)."""
+    """Run consecutive bottlenecks on an NHWC activation.  A block hands its result on in pair layout, and may drop the
+    fp32 copy (``pair_only``), when the NEXT block is on the pair route (``takes_pair_only_input()``); otherwise it hands
+    on the fp32 result alone, e.g. to a deformable block or, with STRIDE_IN_1X1 False, to a stage's first block (a strided
+    3x3): those run the reference ``forward`` between two layout copies.  ``first`` / ``last``: extra keyword arguments
+    of the first / last block's ``forward_nhwc``.  ``then``: the block a LATER call continues the chain with -- the last
+    block then hands on ``(y, yp)`` exactly as it would inside one chain (the frozen prefix of the trunk, run ahead on a
+    side stream: ``ResNetC4.forward_prefix``)."""
     n = len(blocks)
     for i, b in enumerate(blocks):
         kw = dict(first or {}) if i == 0 else {}
         nxt = blocks[i + 1] if i + 1 < n else then
-        if nxt is not None:
-            y, yp = b.forward_nhwc(y, xp=yp, want_pair=True, pair_only=nxt.takes_pair_only_input(), **kw)
-        else:
+        if nxt is None:
             kw.update(last or {})
-            y = b.forward_nhwc(y, xp=yp, **kw)
+        if nxt is not None and nxt.takes_pair_only_input():
+            y, yp = b.forward_nhwc(y, xp=yp, want_pair=True, pair_only=True, **kw)
+        else:
+            y, yp = b.forward_nhwc(y, xp=yp, **kw), None
     return (y, yp) if then is not None else y
 
 
@@ -396,9 +334,8 @@ class ResNetC4(nn.Module):
 
     def _chain_ok(self, x, blocks):
         frozen = not any(p.requires_grad for p in self.parameters())
-        plain = [b for b in blocks if not b.with_dcn]
-        return (x.is_cuda and self.nhwc and all(b.nhwc_supported() for b in plain)
-                and (frozen or (self.train_nhwc and all(b.pair_gemm and b.pair_supported() for b in plain))))
+        return (x.is_cuda and self.nhwc
+                and (frozen or (self.train_nhwc and all(b.pair_supported() for b in blocks if not b.with_dcn))))
 
     def forward_prefix(self, x):
         """Stem and the FROZEN leading blocks (FREEZE_CONV_BODY_AT) on the NHWC chain: ``(y, yp, n_blocks)`` for
@@ -424,14 +361,12 @@ class ResNetC4(nn.Module):
             y, yp, k = prefix
             return [chain_nhwc(blocks[k:], y, yp).permute(0, 3, 1, 2)]
         x = self.stem.forward_gemm(x) if (self.nhwc and self.stem.gemm_supported(x)) else self.stem(x)
-        plain = [b for b in blocks if not b.with_dcn]
         if self._chain_ok(x, blocks):
-            if len(plain) != len(blocks):
-                return [self._forward_mixed(x, blocks)]
             # layer1-3 in NHWC with the split-GEMM bottlenecks of the res5 head (1x1 = row-major GEMM, 3x3 = implicit
-            # GEMM).  Frozen trunk (student-teacher configuration): always.
-            # Trainable stages (teacher training): through the pair-layout autograd nodes as well -- 39.4 vs 42.2 ms per
-            # step against MIOpen's NCHW kernels (both with a warm MIOpen kernel cache; ``train_nhwc = False``
+            # GEMM); a block off the pair route (deformable, or a strided 3x3) runs its reference forward between two
+            # layout copies.  Frozen trunk (student-teacher configuration): always.
+            # Trainable stages (teacher training): when every non-deformable block is on the pair route -- 39.4 vs 42.2 ms
+            # per step against MIOpen's NCHW kernels (both with a warm MIOpen kernel cache; ``train_nhwc = False``
             # selects MIOpen).
             y = chain_nhwc(blocks, x.permute(0, 2, 3, 1).contiguous())
             # the C4 map stays in NHWC memory (an NCHW-shaped view of it): the poolers read channels-last maps in place
@@ -441,25 +376,6 @@ class ResNetC4(nn.Module):
         for name in self.stages:
             x = getattr(self, name)(x)
         return [x]
-
-    @staticmethod
-    def _forward_mixed(x, blocks):
-        """A trunk with deformable stages (STAGE_WITH_DCN): runs of ordinary bottlenecks stay on the NHWC pair-GEMM chain,
-        a deformable block runs its own NCHW forward (``_C`` deformable ops take the reference's NCHW tensors) between two
-        layout copies.  Returns the NCHW-shaped view of NHWC memory the poolers / RPN head read."""
-        y = x.permute(0, 2, 3, 1).contiguous()
-        run = []
-        for b in blocks:
-            if not b.with_dcn:
-                run.append(b)
-                continue
-            if run:
-                y = chain_nhwc(run, y)
-                run = []
-            y = b(y.permute(0, 3, 1, 2).contiguous()).permute(0, 2, 3, 1).contiguous()
-        if run:
-            y = chain_nhwc(run, y)
-        return y.permute(0, 3, 1, 2)
 
 
 class Backbone(nn.Sequential):
@@ -486,20 +402,19 @@ class ResNetHead(nn.Module):
         self.nhwc = self.fuse_pooler = True  # False = per-layer NCHW convolutions / full 14x14 pooling (cross-checks)
 
     def forward(self, x):
-        """x [R, C, 14, 14] -> [R, 2048, 7, 7].  On the GPU the stage runs in NHWC with GEMM 1x1s
-        (``Bottleneck.forward_nhwc``) and returns the channels_last view of the result; ``nhwc = False``
-        keeps the plain per-layer convolution path (also taken for grouped / exotic configurations)."""
-        if x.is_cuda and self.nhwc and all(b.nhwc_supported() for b in self.layer4):
+        """x [R, C, 14, 14] -> [R, 2048, 7, 7].  On the GPU the stage runs as an NHWC chain (``chain_nhwc``) and returns
+        the channels_last view of the result; ``nhwc = False`` keeps the plain per-layer convolution path."""
+        if x.is_cuda and self.nhwc:
             # the first block's stride-2 slice makes this the only NCHW -> NHWC copy
             return chain_nhwc(list(self.layer4), x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
         return self.layer4(x)
 
     def pooler_stride(self):
         """Stride the pooler may apply itself (``ROIAlign.forward_strided_nhwc``): the common stride of the first
-        block's conv1 and projection shortcut when the NHWC path is on, else 0."""
+        block's conv1 and projection shortcut when the NHWC path is on and that block on the pair route, else 0."""
         b0 = self.layer4[0]
         s = b0.conv1.stride
-        ok = (self.nhwc and self.fuse_pooler and all(b.nhwc_supported() for b in self.layer4) and s[0] == s[1] and s[0] > 1
+        ok = (self.nhwc and self.fuse_pooler and b0.pair_supported() and s[0] == s[1] and s[0] > 1
               and (b0.downsample is None or b0.downsample[0].stride == s))
         return s[0] if ok else 0
 
@@ -507,7 +422,7 @@ class ResNetHead(nn.Module):
         """The pooler may hand its bins over in pair layout only (no fp32 rows): the first block runs on the pair GEMM
         route and has a projection shortcut."""
         b0 = self.layer4[0]
-        return bool(self.pooler_stride()) and b0.pair_gemm and b0.pair_supported() and b0._fd is not None
+        return bool(self.pooler_stride()) and b0.pair_supported() and b0._fd is not None
 
     def forward_pooled_nhwc(self, y, yp=None, shape=None, select=None, pooled_only=False):
         """y [R, 7, 7, C]: the pooled bins conv1 reads, NHWC (from ``forward_strided_nhwc``) -> [R, 2048, 7, 7] view;

@@ -438,8 +438,9 @@ def test_pair_only_output_feeds_exactly_one_block():
 
 def test_frozen_trunk_with_stride_in_3x3_keeps_fp32_between_routes():
     """MODEL.RESNETS.STRIDE_IN_1X1 False: the first block of layer2 / layer3 has a strided 3x3 and is not on the pair-GEMM
-    route, so the block in front of it must NOT drop the fp32 copy of its output (look-ahead in ``chain_nhwc``; a pair-only
-    hand-over would feed that block a placeholder).  Frozen trunk, NHWC chain vs the per-layer NCHW convolutions."""
+    route (it runs its reference forward inside the chain), so the block in front of it must NOT drop the fp32 copy of its
+    output (look-ahead in ``chain_nhwc``; a pair-only hand-over would feed that block a placeholder).  Frozen trunk, NHWC
+    chain vs the per-layer NCHW convolutions."""
     from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults
     from cvpr22_cross_modal_pseudo_labeling_amd.layers.pair_bottleneck import is_placeholder
     from cvpr22_cross_modal_pseudo_labeling_amd.modeling.backbone import ResNetC4, chain_nhwc
