@@ -5,8 +5,12 @@ Restates the forward sampling rule of maskrcnn_benchmark/csrc/cuda/deform_conv_k
 :475-575,578-640) as vectorised torch ops, followed by the grouped product with the weight
 (deform_conv_cuda.cu:232-245).  Backward is obtained by autograd of this forward, i.e. the exact gradient of the
 same function -- what the reference's hand-written col2im / col2im_coord kernels (:287-443, :643-774) compute.
-PARITY UNPINNED by reference tests: the reference has no CPU implementation of these ops (csrc/deform_conv.h:41)
-and no tests; the pins are analytic (zero offsets == F.conv2d, mask == 1 == v1; see tests/test_dcn*.py).
+PINNED by tests/test_dcn_pins.py against tests/dcn_scalar_reference.py, an independent scalar restatement of those CUDA
+kernels (forward, and the backward kernels as they are written): forward and every gradient within 1e-10 of the maximum,
+over groups / deformable groups / stride / dilation / unequal kernels, with smooth offsets and with offsets on a 0.25 grid
+that put samples exactly on integer lines and on the border lines -1, H, W.  The reference has no CPU implementation of
+these ops (csrc/deform_conv.h:41) and no tests, so no reference OUTPUT exists; the analytic identities (zero offsets ==
+F.conv2d, mask == 1 == v1) remain in tests/test_dcn.py.
 """
 import torch
 
@@ -65,9 +69,13 @@ def deform_psroi_pool(data, rois, trans, spatial_scale, out_size, output_dim, no
     ``- 0.5``, ``max(.., 0.1)``, border tests and clamp use double literals there), so that floor / ceil cells, the
     inside-the-map test and the sample count are the reference's; sample values and their mean are fp64.  The backward
     of the reference (:141-263) is autograd of this function: the clamp is straight-through, which is exactly the
-    reference's offset gradient (it differentiates the bilinear weights at the clamped position and ignores the clamp).
-    PARITY UNPINNED by reference tests (the reference has no CPU kernel and no tests for this op); pins are analytic
-    (constant and linear maps, offset == shifted RoI, finite differences: tests/test_dcn.py)."""
+    reference's offset gradient (it differentiates the bilinear weights at the clamped position and ignores the clamp);
+    the trans gradient runs through an fp64 term of its own, so it carries no float32 round-off.
+    PINNED by tests/test_dcn_pins.py against the scalar restatement of the forward and of the backward accumulation kernel
+    in tests/dcn_scalar_reference.py: counts exact, output and both gradients within 1e-10 of the maximum, RoIs outside
+    the map and samples exactly on -0.5, W - 0.5, 0 and W - 1 included.  The reference has no CPU kernel and no tests for
+    this op; the analytic identities (constant and linear maps, offset == shifted RoI, finite differences) remain in
+    tests/test_dcn.py."""
     f32, f64 = torch.float32, torch.float64
     P = out_size
     part_size = P if part_size is None else part_size
@@ -102,8 +110,8 @@ def deform_psroi_pool(data, rois, trans, spatial_scale, out_size, output_dim, no
     if no_trans:
         tx = ty = torch.zeros(n, output_dim, P, P, dtype=f32, device=dev)
     else:
-        t = trans.to(f32).view(n, num_classes, 2, part_size, part_size)[:, class_id]      # [n, od, 2, ps, ps]
-        t = t[:, :, :, part][:, :, :, :, part]                                             # [n, od, 2, P(ph), P(pw)]
+        pick = lambda a: a.view(n, num_classes, 2, part_size, part_size)[:, class_id][:, :, :, part][:, :, :, :, part]
+        t = pick(trans.detach().to(f32))                                                   # [n, od, 2, P(ph), P(pw)]
         std = torch.tensor(trans_std, dtype=f32, device=dev)
         tx, ty = t[:, :, 0] * std, t[:, :, 1] * std
     v = lambda a: a.view(n, 1, 1, 1)
@@ -117,11 +125,18 @@ def deform_psroi_pool(data, rois, trans, spatial_scale, out_size, output_dim, no
     w, h = w.expand(n, output_dim, P, P, spp, spp), h.expand(n, output_dim, P, P, spp, spp)
     wd, hd = w.detach().to(f64), h.detach().to(f64)
     inside = ~((wd < -0.5) | (wd > W - 0.5) | (hd < -0.5) | (hd > H - 0.5))
-    wc = w + (wd.clamp(0.0, W - 1.0).to(f32) - w.detach())     # straight-through clamp
-    hc = h + (hd.clamp(0.0, H - 1.0).to(f32) - h.detach())
-    x1, x2 = torch.floor(wc.detach()).long(), torch.ceil(wc.detach()).long()
-    y1, y2 = torch.floor(hc.detach()).long(), torch.ceil(hc.detach()).long()
+    wc, hc = wd.clamp(0.0, W - 1.0).to(f32), hd.clamp(0.0, H - 1.0).to(f32)
+    x1, x2 = torch.floor(wc).long(), torch.ceil(wc).long()
+    y1, y2 = torch.floor(hc).long(), torch.ceil(hc).long()
     dx, dy = (wc - x1.to(f32)).to(f64), (hc - y1.to(f32)).to(f64)
+    if not no_trans:
+        # The positions above are float32 VALUES without a graph.  Their dependence on trans enters here, as an fp64 term of
+        # value zero and slope trans_std * roi_width (height): the clamp is straight-through, and the trans gradient is
+        # accumulated in fp64 like the data gradient (through the float32 graph it carried float32 round-off, 1e-7).
+        t64 = pick(trans.to(f64))
+        t64 = t64 - t64.detach()
+        dx = dx + (t64[:, :, 0] * (std.to(f64) * v(roi_w).to(f64)))[..., None, None]
+        dy = dy + (t64[:, :, 1] * (std.to(f64) * v(roi_h).to(f64)))[..., None, None]
     c = (torch.arange(output_dim, device=dev).view(-1, 1, 1) * group_size + grp.view(1, P, 1)) * group_size + grp.view(1, 1, P)
     b = r[:, 0].long().view(n, 1, 1, 1, 1, 1).expand_as(x1)
     cc = c.view(1, output_dim, P, P, 1, 1).expand_as(x1)

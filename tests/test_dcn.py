@@ -1,6 +1,8 @@
-"""Deformable convolution: CPU pins of the fp64 oracle (analytic identities) and GPU parity of the HIP path
-(im2col / col2im / col2im_coord kernels + MFMA GEMMs, through the reference's `_C` signatures and autograd
-functions) against that oracle."""
+"""Deformable convolution: CPU pins of the fp64 oracle (analytic identities; the pins against an independent scalar
+restatement of the reference's kernels are in tests/test_dcn_pins.py) and GPU parity of the HIP path (im2col / col2im /
+col2im_coord kernels + MFMA GEMMs, through the reference's `_C` signatures and autograd functions) against that oracle:
+smooth offsets, offsets on a 0.25 grid that put samples exactly on the borders, and the degenerate maps, on each of the
+three routes (columns, implicit-GEMM forward, rows backward)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -8,12 +10,17 @@ import torch.nn.functional as F
 from oracle import dcn as O
 
 
-def _case(g, B=2, C=8, Cout=6, H=9, W=11, k=3, stride=1, pad=1, dil=1, groups=1, dg=1, dtype=torch.float64):
+def _case(g, B=2, C=8, Cout=6, H=9, W=11, k=3, stride=1, pad=1, dil=1, groups=1, dg=1, dtype=torch.float64, offsets="smooth"):
+    """offsets="grid": multiples of 0.25 in [-4, 4] -- exact in fp32 and fp64, so both arithmetics make the same floor and
+    inside decisions; many samples then lie on integer rows / columns and some exactly on the border lines -1, H, W."""
     x = torch.randn(B, C, H, W, generator=g, dtype=dtype)
     w = torch.randn(Cout, C // groups, k, k, generator=g, dtype=dtype) * 0.2
     Ho = (H + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
     Wo = (W + 2 * pad - (dil * (k - 1) + 1)) // stride + 1
-    off = torch.randn(B, dg * 2 * k * k, Ho, Wo, generator=g, dtype=dtype) * 1.5
+    if offsets == "grid":
+        off = torch.randint(-16, 17, (B, dg * 2 * k * k, Ho, Wo), generator=g).to(dtype) * 0.25
+    else:
+        off = torch.randn(B, dg * 2 * k * k, Ho, Wo, generator=g, dtype=dtype) * 1.5
     mask = torch.sigmoid(torch.randn(B, dg * k * k, Ho, Wo, generator=g, dtype=dtype))
     bias = torch.randn(Cout, generator=g, dtype=dtype)
     return x, w, off, mask, bias
@@ -178,6 +185,240 @@ def test_deform_conv_backward_on_rows_vs_oracle(kw):
             assert (got - col).abs().max().item() <= 3e-5 * s_
 
 
+# ---------------------------------------------------------------- the borders, on every route
+def _edge_counts(off, H, W, k, stride, pad, dil, dg):
+    """(samples with an integer row or column coordinate, samples exactly on one of the lines -1, H, W of the inside rule);
+    the offset layout is the one tests/test_dcn_pins.py pins: plane (g * K + tap) * 2 is the row offset, + 1 the column's."""
+    B, _, Ho, Wo = off.shape
+    o = off.view(B, dg, k * k, 2, Ho, Wo)
+    tap = torch.arange(k * k)
+    h = (torch.arange(Ho) * stride - pad).view(1, 1, 1, Ho, 1) + (tap // k * dil).view(1, 1, -1, 1, 1) + o[:, :, :, 0]
+    w = (torch.arange(Wo) * stride - pad).view(1, 1, 1, 1, Wo) + (tap % k * dil).view(1, 1, -1, 1, 1) + o[:, :, :, 1]
+    on_line = (h == h.floor()) | (w == w.floor())
+    on_border = (h == -1) | (h == H) | (w == -1) | (w == W)
+    return int(on_line.sum()), int(on_border.sum())
+
+
+def _oracle_run(x, w, off, mask, bias, modulated, st, pd, dl, gr, dg, g):
+    """fp64 oracle forward + autograd backward: (output, grad_output, [dX, dW, dOffset (, dMask, dBias)]); the graph is freed."""
+    leaves = [t.clone().requires_grad_(True) for t in ((x, w, off) + ((mask, bias) if modulated else ()))]
+    want = O.deform_conv2d(leaves[0], leaves[2], leaves[1], leaves[3] if modulated else None, leaves[4] if modulated else None,
+                           st, pd, dl, gr, dg)
+    go = torch.randn(want.shape, generator=g, dtype=torch.float64)
+    want.backward(go)
+    return want.detach(), go, [t.grad for t in leaves]
+
+
+def _hip_run(x, w, off, mask, bias, go, modulated, st, pd, dl, gr, dg, implicit=True):
+    """The HIP path through the autograd functions, fp32: (output, gradients as _oracle_run orders them) on the host in fp64.
+    implicit=False forces the column route where the implicit-GEMM / rows routes would apply."""
+    from cvpr22_cross_modal_pseudo_labeling_amd import _C
+    from cvpr22_cross_modal_pseudo_labeling_amd.layers import deform_conv, modulated_deform_conv
+
+    leaves = [t.detach().float().cuda().requires_grad_(True) for t in ((x, w, off) + ((mask, bias) if modulated else ()))]
+    _C.dcn_implicit = implicit
+    try:
+        if modulated:
+            y = modulated_deform_conv(leaves[0], leaves[2], leaves[3], leaves[1], leaves[4], st, pd, dl, gr, dg)
+        else:
+            y = deform_conv(leaves[0], leaves[2], leaves[1], st, pd, dl, gr, dg, 2 if x.shape[0] % 2 == 0 else 1)
+        y.backward(go.float().cuda())
+    finally:
+        _C.dcn_implicit = True
+    return y.detach().cpu().double(), [t.grad.cpu().double() for t in leaves]
+
+
+class _count_calls:
+    """Counts the calls of the named entry points of the HIP library while the block runs."""
+
+    def __init__(self, *names):
+        self.names, self.n = names, {n: 0 for n in names}
+
+    def __enter__(self):
+        from cvpr22_cross_modal_pseudo_labeling_amd import _C
+
+        self.lib, self.orig = _C._L, {n: getattr(_C._L, n) for n in self.names}
+        for n in self.names:
+            setattr(self.lib, n, (lambda n_: lambda *a: (self.n.__setitem__(n_, self.n[n_] + 1), self.orig[n_](*a))[1])(n))
+        return self.n
+
+    def __exit__(self, *exc):
+        for n in self.names:
+            setattr(self.lib, n, self.orig[n])
+
+
+_IMPLICIT, _ROWS = "ovis_deform_conv_implicit_f32", ("ovis_deform_col2im_rows_f32", "ovis_deform_im2col_pair_rows_f32")
+
+
+def _compare(got, grads, want, want_grads, fwd_tol, grad_tol, what=""):
+    scale = want.abs().max().item()
+    err = (got - want).abs().max().item()
+    print(f"{what} forward: err {err:.3e}, bound {fwd_tol:g} * {scale:.3e}")
+    assert err <= fwd_tol * scale
+    for name, dev_g, ref_g in zip(("dX", "dW", "dOffset", "dMask", "dBias"), grads, want_grads):
+        s = ref_g.abs().max().item() + 1e-12
+        err = (dev_g - ref_g).abs().max().item()
+        print(f"{what} {name}: err {err:.3e}, bound {grad_tol:g} * {s:.3e}")
+        assert err <= grad_tol * s, name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kw", [dict(), dict(stride=2, pad=2, dil=2), dict(groups=2, dg=2, C=8, Cout=4),
+                                dict(B=3, C=4, Cout=5, H=7, W=6, k=1, pad=0), dict(B=4, C=6, Cout=6, H=12, W=10, dg=3)])
+def test_deform_conv_grid_offsets_column_route_vs_oracle(kw):
+    """The parameter sets of test_deform_conv_v1_v2_vs_oracle with offsets on the 0.25 grid: samples exactly on integer
+    lines and on -1 / H / W, where a `<` for a `<=` in the im2col, col2im or coordinate kernel shows.  The bilinear weights
+    are exact multiples of 1/16 there, so the bounds are the smooth test's (1e-5 forward, 2e-5 gradients)."""
+    g = torch.Generator().manual_seed(43)
+    x, w, off, mask, bias = _case(g, offsets="grid", **kw)
+    st, pd, dl = (kw.get("stride", 1),) * 2, (kw.get("pad", 1),) * 2, (kw.get("dil", 1),) * 2
+    gr, dg = kw.get("groups", 1), kw.get("dg", 1)
+    on_line, on_border = _edge_counts(off, x.shape[2], x.shape[3], kw.get("k", 3), st[0], pd[0], dl[0], dg)
+    assert on_line > 0 and on_border > 0, (on_line, on_border)
+    for modulated in (False, True):
+        want, go, want_grads = _oracle_run(x, w, off, mask, bias, modulated, st, pd, dl, gr, dg, g)
+        with _count_calls(_IMPLICIT, *_ROWS) as n:
+            got, grads = _hip_run(x, w, off, mask, bias, go, modulated, st, pd, dl, gr, dg)
+        assert sum(n.values()) == 0   # the column route
+        _compare(got, grads, want, want_grads, 1e-5, 2e-5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kw", [dict(C=64, Cout=12), dict(C=64, Cout=64, dg=2, stride=2, pad=2, dil=2),
+                                dict(B=3, C=96, Cout=8, H=7, W=6, k=1, pad=0, dg=3), dict(B=1, C=32, Cout=132, H=21, W=19)])
+def test_deform_conv_grid_offsets_implicit_forward_vs_oracle(kw):
+    """The parameter sets of test_deform_conv_forward_without_column_buffer_vs_oracle with grid offsets: the in-kernel
+    sampling of the split GEMM's DEFORM mode at the borders, 3e-5 of the maximum (the three-term product's bound); the
+    backward of these calls against the oracle at the route's bound (rows route where C_out % 32 == 0, else columns)."""
+    g = torch.Generator().manual_seed(8)
+    x, w, off, mask, bias = _case(g, offsets="grid", **kw)
+    st, pd, dl = (kw.get("stride", 1),) * 2, (kw.get("pad", 1),) * 2, (kw.get("dil", 1),) * 2
+    dg = kw.get("dg", 1)
+    on_line, on_border = _edge_counts(off, x.shape[2], x.shape[3], kw.get("k", 3), st[0], pd[0], dl[0], dg)
+    assert on_line > 0 and on_border > 0, (on_line, on_border)
+    rows = w.shape[0] % 32 == 0
+    for modulated in (False, True):
+        want, go, want_grads = _oracle_run(x, w, off, mask, bias, modulated, st, pd, dl, 1, dg, g)
+        with _count_calls(_IMPLICIT, *_ROWS) as n:
+            got, grads = _hip_run(x, w, off, mask, bias, go, modulated, st, pd, dl, 1, dg)
+        assert n[_IMPLICIT] == 1 and n[_ROWS[0]] == n[_ROWS[1]] == int(rows)   # the forward really took the implicit route
+        _compare(got, grads, want, want_grads, 3e-5, 3e-5 if rows else 2e-5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kw", [dict(C=64, Cout=64, dg=2, stride=2, pad=2, dil=2), dict(C=128, Cout=128, H=12, W=10),
+                                dict(B=3, C=96, Cout=32, H=7, W=6, k=1, pad=0, dg=3), dict(B=1, C=32, Cout=160, H=21, W=19),
+                                dict(B=1, C=256, Cout=32, H=9, W=8), dict(B=2, C=512, Cout=32, H=6, W=7, dg=2, stride=2)])
+def test_deform_conv_grid_offsets_backward_on_rows_vs_oracle(kw):
+    """The parameter sets of test_deform_conv_backward_on_rows_vs_oracle with grid offsets: the scatter / gather pass of
+    csrc/deform_conv_rows.hip (narrow and wide form) and its sampled pair rows at the borders, 3e-5 of the maximum."""
+    g = torch.Generator().manual_seed(20)
+    x, w, off, mask, bias = _case(g, offsets="grid", **kw)
+    st, pd, dl = (kw.get("stride", 1),) * 2, (kw.get("pad", 1),) * 2, (kw.get("dil", 1),) * 2
+    dg = kw.get("dg", 1)
+    on_line, on_border = _edge_counts(off, x.shape[2], x.shape[3], kw.get("k", 3), st[0], pd[0], dl[0], dg)
+    assert on_line > 0 and on_border > 0, (on_line, on_border)
+    for modulated in (False, True):
+        want, go, want_grads = _oracle_run(x, w, off, mask, bias, modulated, st, pd, dl, 1, dg, g)
+        with _count_calls(*_ROWS) as n:
+            got, grads = _hip_run(x, w, off, mask, bias, go, modulated, st, pd, dl, 1, dg)
+        assert n[_ROWS[0]] == 1 and n[_ROWS[1]] == 1   # the backward really took the rows route
+        _compare(got, grads, want, want_grads, 3e-5, 3e-5)
+
+
+def _route_case(route, g, **kw):
+    """route "columns": 8 -> 6 channels (no other route applies); "columns64" / "rows": 64 -> 64 channels in two deformable
+    groups, forced onto the column route / left to the implicit-GEMM forward and the rows backward."""
+    if route == "columns":
+        return _case(g, C=8, Cout=6, dg=2, offsets="grid", **kw), 2, True
+    return _case(g, C=64, Cout=64, dg=2, offsets="grid", **kw), 2, route == "rows"
+
+
+def _run_route(route, case, dg, implicit, modulated, g, pd=(1, 1)):
+    x, w, off, mask, bias = case
+    want, go, want_grads = _oracle_run(x, w, off, mask, bias, modulated, (1, 1), pd, (1, 1), 1, dg, g)
+    with _count_calls(_IMPLICIT, *_ROWS) as n:
+        got, grads = _hip_run(x, w, off, mask, bias, go, modulated, (1, 1), pd, (1, 1), 1, dg, implicit=implicit)
+    assert all(v == (1 if route == "rows" else 0) for v in n.values()), n   # the route under test is the one that ran
+    tol = (3e-5, 3e-5) if route == "rows" else (1e-5, 2e-5)
+    _compare(got, grads, want, want_grads, *tol, what=route)
+    return got, grads, want_grads
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["columns", "columns64", "rows"])
+def test_deform_conv_image_with_every_sample_outside(route):
+    """Offsets (+/- 64 on top of the grid family, exact) push every sample of image 1 of 3 outside the map: its output is
+    exactly the bias (0 for v1) and its dX, dOffset and dMask are exactly zero; everything else within the route's bound."""
+    g = torch.Generator().manual_seed(31)
+    (x, w, off, mask, bias), dg, implicit = _route_case(route, g, B=3, H=6, W=7)
+    sign = torch.where(torch.rand(off[1].shape, generator=g) < 0.5, -1.0, 1.0).double()
+    off[1] += 64.0 * sign
+    for modulated in (False, True):
+        got, grads, _ = _run_route(route, (x, w, off, mask, bias), dg, implicit, modulated, g)
+        expect = bias.float().double().view(-1, 1, 1) if modulated else torch.zeros(1, 1, 1, dtype=torch.float64)
+        assert torch.equal(got[1], expect.expand_as(got[1]))
+        for i in (0, 2) + ((3,) if modulated else ()):   # dX, dOffset, dMask
+            assert float(grads[i][1].abs().max()) == 0.0 and float(grads[i][0].abs().max()) > 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["columns", "columns64", "rows"])
+def test_deform_conv_mask_with_exact_zeros(route):
+    """Taps whose mask is exactly 0 get an offset gradient of exactly 0, while their mask gradient is still the sampled value
+    times the column gradient (the oracle's, within the route's bound, and not zero)."""
+    g = torch.Generator().manual_seed(32)
+    (x, w, off, mask, bias), dg, implicit = _route_case(route, g, B=2, H=6, W=7)
+    zero = torch.rand(mask.shape, generator=g) < 0.4
+    mask = torch.where(zero, torch.zeros_like(mask), mask)
+    _, grads, want_grads = _run_route(route, (x, w, off, mask, bias), dg, implicit, True, g)
+    B, _, Ho, Wo = mask.shape
+    z = zero.view(B, dg, 9, Ho, Wo)
+    doff = grads[2].view(B, dg, 9, 2, Ho, Wo)
+    assert float(doff[:, :, :, 0][z].abs().max()) == 0.0 and float(doff[:, :, :, 1][z].abs().max()) == 0.0
+    assert float(want_grads[3].view(B, dg, 9, Ho, Wo)[z].abs().max()) > 0.0 and float(grads[3].view(B, dg, 9, Ho, Wo)[z].abs().max()) > 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", ["smooth", "grid"])
+@pytest.mark.parametrize("route", ["columns", "columns64", "rows"])
+def test_deform_conv_on_a_1x2_map(route, family):
+    """H = 1, W = 2, 3x3, pad 1: every tap of every output touches the border (rows -1 and 1 of the window are never cells,
+    columns only partly)."""
+    g = torch.Generator().manual_seed(33)
+    kw = dict(B=2, H=1, W=2, offsets=family)
+    case = _case(g, C=8, Cout=6, dg=2, **kw) if route == "columns" else _case(g, C=64, Cout=64, dg=2, **kw)
+    if family == "grid":
+        on_line, on_border = _edge_counts(case[2], 1, 2, 3, 1, 1, 1, 2)
+        assert on_line > 0 and on_border > 0, (on_line, on_border)
+    for modulated in (False, True):
+        _, grads, _ = _run_route(route, case, 2, route == "rows", modulated, g)
+        assert float(grads[0].abs().max()) > 0.0   # some samples are inside
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("modulated", [False, True], ids=["v1", "v2"])
+def test_deform_conv_at_full_stage_size_vs_oracle(modulated):
+    """A layer3 block of the 800 x 1333 step: B = 2, 256 -> 256 channels, 50 x 84, 3x3, one deformable group, smooth offsets --
+    the first case whose column buffer (2304 x 2 x 4200) and index products are not tiny.  Forward and every gradient
+    against the oracle, on the column route (1e-5 / 2e-5: 2304 fp32 products per output) and on the implicit-GEMM forward +
+    rows backward that this shape takes by default (3e-5)."""
+    import gc
+
+    g = torch.Generator().manual_seed(50)
+    x, w, off, mask, bias = _case(g, B=2, C=256, Cout=256, H=50, W=84)
+    want, go, want_grads = _oracle_run(x, w, off, mask, bias, modulated, (1, 1), (1, 1), (1, 1), 1, 1, g)
+    gc.collect()
+    with _count_calls(_IMPLICIT, *_ROWS) as n:
+        got, grads = _hip_run(x, w, off, mask, bias, go, modulated, (1, 1), (1, 1), (1, 1), 1, 1, implicit=False)
+    assert sum(n.values()) == 0
+    _compare(got, grads, want, want_grads, 1e-5, 2e-5, what="columns")
+    with _count_calls(_IMPLICIT, *_ROWS) as n:
+        got, grads = _hip_run(x, w, off, mask, bias, go, modulated, (1, 1), (1, 1), (1, 1), 1, 1)
+    assert all(v == 1 for v in n.values()), n
+    _compare(got, grads, want, want_grads, 3e-5, 3e-5, what="implicit + rows")
+
+
 @pytest.mark.gpu
 def test_dcn_modules_and_dfconv():
     from cvpr22_cross_modal_pseudo_labeling_amd.layers import DFConv2d, ModulatedDeformConvPack
@@ -306,6 +547,35 @@ def test_deform_psroi_pooling_vs_oracle(kw):
         assert (t1.grad.cpu().double() - gw[1].double()).abs().max().item() <= 2e-4 * max(1.0, gw[1].abs().max().item())
     if kw.get("far"):
         assert float(want_cnt[0].sum()) == 0 and float(got[0].abs().sum()) == 0
+
+
+@pytest.mark.gpu
+def test_deform_psroi_pooling_on_the_boundary_vs_oracle():
+    """The boundary case of tests/test_dcn_pins.py (every position exact in float32; samples exactly on -0.5 and W - 0.5, on
+    0 and W - 1, and beyond): sample counts exact, values and both gradients at the bounds of the test above."""
+    from cvpr22_cross_modal_pseudo_labeling_amd import _C
+    from cvpr22_cross_modal_pseudo_labeling_amd.layers import deform_roi_pooling
+    from oracle.dcn import deform_psroi_pool
+
+    from .test_dcn_pins import _boundary_pool_case
+
+    data, rois, trans, p = _boundary_pool_case()
+    scale, P, od, gs, spp, std = p["scale"], p["P"], p["od"], p["gs"], p["spp"], p["std"]
+    d0, t0 = data.clone().requires_grad_(True), trans.clone().requires_grad_(True)
+    want, want_cnt = deform_psroi_pool(d0, rois, t0, scale, P, od, False, gs, None, spp, std)
+    gout = torch.randn(want.shape, generator=torch.Generator().manual_seed(5))
+    gw = torch.autograd.grad(want, [d0, t0], gout.double())
+    d1, t1 = data.float().cuda().requires_grad_(True), trans.float().cuda().requires_grad_(True)
+    out, cnt = torch.empty(want.shape, device="cuda"), torch.empty(want.shape, device="cuda")
+    _C.deform_psroi_pooling_forward(d1.detach(), rois.cuda(), t1.detach(), out, cnt, False, scale, od, gs, P, P, spp, std)
+    assert torch.equal(cnt.cpu().double(), want_cnt)
+    assert int((want_cnt < spp * spp).sum()) > 0 and int((want_cnt == spp * spp).sum()) > 0
+    got = deform_roi_pooling(d1, rois.cuda(), t1, scale, P, od, False, gs, None, spp, std)
+    assert torch.equal(got.detach(), out)
+    assert torch.allclose(got.detach().cpu().double(), want.detach(), rtol=1e-5, atol=1e-5)
+    got.backward(gout.cuda())
+    assert (d1.grad.cpu().double() - gw[0]).abs().max().item() <= 1e-4 * max(1.0, gw[0].abs().max().item())
+    assert (t1.grad.cpu().double() - gw[1]).abs().max().item() <= 2e-4 * max(1.0, gw[1].abs().max().item())
 
 
 @pytest.mark.gpu
