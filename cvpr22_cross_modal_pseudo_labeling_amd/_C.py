@@ -44,11 +44,15 @@ def _on(device):
     return _SAME if device.index == torch.cuda.current_device() else torch.cuda.device(device)
 
 
-def _dev(t, name, dtype=torch.float32):
+def _check_dev(t, name, dtype=torch.float32):
     if not t.is_cuda:
         raise RuntimeError(f"{name} must be a HIP device tensor: this op has no host implementation (as in the reference)")
     if t.dtype != dtype:
         raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
+
+
+def _dev(t, name, dtype=torch.float32):
+    _check_dev(t, name, dtype)
     t = t.contiguous()
     if t.data_ptr() % 16:
         t = t.clone()
@@ -95,75 +99,52 @@ def roi_align_forward_mfma(input, rois, spatial_scale, pooled_height, pooled_wid
     return _roi_align_forward(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, False)
 
 
-def _channels_last_map(input, channel_multiple):
-    """An [N, C, H, W] HIP tensor whose MEMORY is NHWC-contiguous (the NCHW view of the trunk's NHWC result) with a channel
-    count the NHWC-input pooler takes: no layout copy is needed."""
-    return (input.is_cuda and input.dtype == torch.float32 and input.dim() == 4 and input.shape[1] % channel_multiple == 0
-            and not input.is_contiguous() and input.permute(0, 2, 3, 1).is_contiguous() and input.data_ptr() % 16 == 0)
-
-
-def _strided_from_nhwc(input, rois, out, spatial_scale, pooled_height, pooled_width, sampling_ratio, bin_stride, pair):
+def _roi_align_forward_strided(name, input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, bin_stride, pair):
+    """The one strided pooler, ``ovis_roi_align_forward_strided_from_nhwc_f32``.  It reads NHWC memory: a channels-last
+    ``input`` (the NCHW view of the trunk's NHWC result) is pooled in place, any other layout is copied to channels-last
+    first.  Returns (fp32 NHWC bins or pair rows, (oh, ow))."""
+    _check_dev(input, "input")
+    rois = _dev(rois, "rois")
+    if rois.dim() != 2 or rois.size(1) != 5 or input.dim() != 4:
+        raise RuntimeError(f"{name}: expected input [N,C,H,W] and rois [R,5]")
     n, c, h, w = input.shape
-    with _on(input.device):
-        rc = _L.ovis_roi_align_forward_strided_from_nhwc_f32(input.data_ptr(), rois.data_ptr(), out.data_ptr(), rois.size(0), n, c,
-                                                             h, w, pooled_height, pooled_width, bin_stride, spatial_scale,
-                                                             sampling_ratio, int(pair), _stream())
-    _lib.check(rc, "roi_align_forward_strided_from_nhwc")
+    r = rois.size(0)
+    s = bin_stride
+    oh, ow = -(-pooled_height // s), -(-pooled_width // s)
+    if not pair and c % 4:
+        # the kernels pool float4 channel groups; other channel counts (tests only) take the definition of the op
+        full = roi_align_forward(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio)
+        return full[:, :, ::s, ::s].permute(0, 2, 3, 1).contiguous(), (oh, ow)
+    if pair:
+        out = torch.empty((r * oh * ow, 2 * c), dtype=torch.bfloat16, device=input.device)
+    else:
+        out = torch.empty((r, oh, ow, c), dtype=input.dtype, device=input.device)
+    if out.numel():
+        if not (input.permute(0, 2, 3, 1).is_contiguous() and input.data_ptr() % 16 == 0):
+            input = input.contiguous(memory_format=torch.channels_last)
+            if input.data_ptr() % 16:
+                input = input.clone()
+        with _on(input.device):
+            rc = _L.ovis_roi_align_forward_strided_from_nhwc_f32(input.data_ptr(), rois.data_ptr(), out.data_ptr(), r, n, c, h, w,
+                                                                 pooled_height, pooled_width, s, spatial_scale,
+                                                                 sampling_ratio, int(pair), _stream())
+        _lib.check(rc, name)   # pair rows need channels % 32 == 0: OVIS_ERANGE otherwise
+    return out, (oh, ow)
 
 
 def roi_align_forward_strided_nhwc(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, bin_stride):
     """Extension: bins (bin_stride*i, bin_stride*j) only, as [R, ceil(PH/s), ceil(PW/s), C] (NHWC); bit-identical to
-    ``roi_align_forward(...)[:, :, ::s, ::s].permute(0, 2, 3, 1)``.  A channels-last ``input`` is pooled in place (no
-    window staging: ``ovis_roi_align_forward_strided_from_nhwc_f32``), an NCHW one through the window-staging kernel."""
-    if _channels_last_map(input, 4):
-        rois = _dev(rois, "rois")
-        oh, ow = -(-pooled_height // bin_stride), -(-pooled_width // bin_stride)
-        out = torch.empty((rois.size(0), oh, ow, input.shape[1]), dtype=input.dtype, device=input.device)
-        if out.numel():
-            _strided_from_nhwc(input, rois, out, spatial_scale, pooled_height, pooled_width, sampling_ratio, bin_stride, False)
-        return out
-    input, rois = _dev(input, "input"), _dev(rois, "rois")
-    if rois.dim() != 2 or rois.size(1) != 5 or input.dim() != 4:
-        raise RuntimeError("roi_align_forward_strided_nhwc: expected input [N,C,H,W] and rois [R,5]")
-    n, c, h, w = input.shape
-    r = rois.size(0)
-    oh, ow = -(-pooled_height // bin_stride), -(-pooled_width // bin_stride)
-    out = torch.empty((r, oh, ow, c), dtype=input.dtype, device=input.device)
-    if out.numel() == 0:
-        return out
-    with _on(input.device):
-        rc = _L.ovis_roi_align_forward_strided_nhwc_f32(input.data_ptr(), rois.data_ptr(), out.data_ptr(), r, n, c, h,
-                                                        w, pooled_height, pooled_width, bin_stride, spatial_scale,
-                                                        sampling_ratio, _stream())
-    _lib.check(rc, "roi_align_forward_strided_nhwc")
-    return out
+    ``roi_align_forward(...)[:, :, ::s, ::s].permute(0, 2, 3, 1)``.  A channels-last ``input`` is pooled in place, any
+    other layout through one copy to channels-last (``_roi_align_forward_strided``)."""
+    return _roi_align_forward_strided("roi_align_forward_strided_nhwc", input, rois, spatial_scale, pooled_height, pooled_width,
+                                      sampling_ratio, bin_stride, False)[0]
 
 
 def roi_align_forward_strided_pair(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, bin_stride):
     """``roi_align_forward_strided_nhwc`` written in pair layout: [R*oh*ow, 2*C] bf16 (exactly ``split_pair`` of the fp32
-    bins), the operand of the res5 head's first split GEMM.  Returns (pair rows, (oh, ow)).  Channels-last inputs are
-    pooled in place (see ``roi_align_forward_strided_nhwc``)."""
-    if _channels_last_map(input, 32):
-        rois = _dev(rois, "rois")
-        oh, ow = -(-pooled_height // bin_stride), -(-pooled_width // bin_stride)
-        out = torch.empty((rois.size(0) * oh * ow, 2 * input.shape[1]), dtype=torch.bfloat16, device=input.device)
-        if out.numel():
-            _strided_from_nhwc(input, rois, out, spatial_scale, pooled_height, pooled_width, sampling_ratio, bin_stride, True)
-        return out, (oh, ow)
-    input, rois = _dev(input, "input"), _dev(rois, "rois")
-    if rois.dim() != 2 or rois.size(1) != 5 or input.dim() != 4:
-        raise RuntimeError("roi_align_forward_strided_pair: expected input [N,C,H,W] and rois [R,5]")
-    n, c, h, w = input.shape
-    r = rois.size(0)
-    oh, ow = -(-pooled_height // bin_stride), -(-pooled_width // bin_stride)
-    out = torch.empty((r * oh * ow, 2 * c), dtype=torch.bfloat16, device=input.device)
-    if out.numel():
-        with _on(input.device):
-            rc = _L.ovis_roi_align_forward_strided_pair_f32(input.data_ptr(), rois.data_ptr(), out.data_ptr(), r, n, c, h, w,
-                                                            pooled_height, pooled_width, bin_stride, spatial_scale,
-                                                            sampling_ratio, _stream())
-        _lib.check(rc, "roi_align_forward_strided_pair")
-    return out, (oh, ow)
+    bins), the operand of the res5 head's first split GEMM.  Returns (pair rows, (oh, ow)).  C % 32 == 0."""
+    return _roi_align_forward_strided("roi_align_forward_strided_pair", input, rois, spatial_scale, pooled_height, pooled_width,
+                                      sampling_ratio, bin_stride, True)
 
 
 def roi_align_backward(grad, rois, spatial_scale, pooled_height, pooled_width, batch_size, channels, height,

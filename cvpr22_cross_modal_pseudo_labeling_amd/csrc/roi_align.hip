@@ -1,4 +1,5 @@
-// RoIAlign forward / backward for gfx950 (MI355X), fp32, NCHW.
+// RoIAlign forward / backward for gfx950 (MI355X), fp32.  The exact forward and the backward work on NCHW maps; the
+// strided pooler of the res5 head reads an NHWC map and writes NHWC bins (fp32 or bf16 pair rows).
 //
 // Semantics follow the reference kernels
 //   forward : maskrcnn_benchmark/csrc/cuda/ROIAlign_cuda.cu:16-122  (CPU twin cpu/ROIAlign_cpu.cpp:18-219)
@@ -379,20 +380,13 @@ __device__ __forceinline__ void pool_store4_pair(char* pair_r, long obin, int c,
   *(uint2*)d = make_uint2(h01, h23);
   *(uint2*)(d + 64) = make_uint2(l01, l23);
 }
-__device__ __forceinline__ void pool_store1_pair(char* pair_r, long obin, int c, int C, float o) {
-  const __bf16 h = (__bf16)o;
-  const __bf16 l = (__bf16)(o - (float)h);
-  char* d = pair_r + obin * 4L * C + (long)(c >> 5) * 128 + (c & 31) * 2;
-  *(__bf16*)d = h;
-  *(__bf16*)(d + 64) = l;
-}
 
-template <int NCS, bool FAST, int LDSF = kFwdLdsFloats>
+template <int NCS, bool FAST>
 __device__ __forceinline__ void fwd_pool4_strided(const f4* win4, int rs, const RoiGeom& g, int H, int W, int bs,
                                                   int OH, int OW, float* __restrict__ out_rc, int C,
                                                   char* pair_r = nullptr, int c_abs = 0) {
   constexpr int NG = NCS / 4;
-  constexpr int SG = LDSF / NCS;
+  constexpr int SG = kFwdLdsFloats / NCS;
   const int items = OH * OW * NG;
   for (int item = threadIdx.x; item < items; item += kThreads) {
     const int k = item % NG, obin = item / NG;
@@ -422,159 +416,14 @@ __device__ __forceinline__ void fwd_pool4_strided(const f4* win4, int rs, const 
   }
 }
 
-// Scalar-layout fallback (windows too large for four interleaved channels; `src` may be the global plane).
-template <int NCS>
-__device__ __forceinline__ void fwd_pool_strided(const float* src, int cs, int rs, int oy, int ox, const RoiGeom& g,
-                                                 int H, int W, int bs, int OH, int OW, float* __restrict__ out_rc,
-                                                 int C, char* pair_r = nullptr, int c_abs = 0) {
-  for (int obin = threadIdx.x; obin < OH * OW; obin += kThreads) {
-    const int oh = obin / OW;
-    const int ph = oh * bs, pw = (obin - oh * OW) * bs;
-    float acc[NCS];
-#pragma unroll
-    for (int c = 0; c < NCS; ++c) acc[c] = 0.f;
-    for (int iy = 0; iy < g.gh; ++iy) {
-      int yl, yh;
-      float ly, hy;
-      if (!axis_sample(sample_coord(g.start_h, ph, g.bin_h, iy, g.gh), H, yl, yh, ly, hy)) continue;
-      const int ryl = (yl - oy) * rs, ryh = (yh - oy) * rs;
-      for (int ix = 0; ix < g.gw; ++ix) {
-        int xl, xh;
-        float lx, hx;
-        if (!axis_sample(sample_coord(g.start_w, pw, g.bin_w, ix, g.gw), W, xl, xh, lx, hx)) continue;
-        const float w1 = hy * hx, w2 = hy * lx, w3 = ly * hx, w4 = ly * lx;
-        const int o1 = ryl + (xl - ox), o2 = ryl + (xh - ox), o3 = ryh + (xl - ox), o4 = ryh + (xh - ox);
-#pragma unroll
-        for (int c = 0; c < NCS; ++c) {
-          const float* p = src + c * cs;
-          acc[c] += w1 * p[o1] + w2 * p[o2] + w3 * p[o3] + w4 * p[o4];
-        }
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < NCS; ++c) {
-      if (pair_r) pool_store1_pair(pair_r, obin, c_abs + c, C, acc[c] / g.count);
-      else out_rc[(long)obin * C + c] = acc[c] / g.count;
-    }
-  }
-}
-
-template <int NCS, int LDSF = kFwdLdsFloats>
-__device__ __forceinline__ void stage_window4(float* win, const float* __restrict__ plane_c0, int HW, int W,
-                                              const RoiGeom& g, int wh, int ww) {
-  constexpr int NG = NCS / 4;
-  constexpr int SG = LDSF / NCS;
-  f4* win4 = (f4*)win;
-  const int warea = wh * ww;
-  const float inv_ww = 1.f / (float)ww;
-  for (int idx = threadIdx.x; idx < warea; idx += kThreads) {
-    const int y = (int)(((float)idx + 0.5f) * inv_ww);
-    const int x = idx - y * ww;
-    const int off = (g.wy0 + y) * W + (g.wx0 + x);
-    float v[NCS];
-#pragma unroll
-    for (int c = 0; c < NCS; ++c) v[c] = (plane_c0 + (long)c * HW)[off];
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      f4 t;
-      t.x = v[4 * k]; t.y = v[4 * k + 1]; t.z = v[4 * k + 2]; t.w = v[4 * k + 3];
-      win4[k * SG + idx] = t;
-    }
-  }
-}
-
-template <int NCS, int LDSF = kFwdLdsFloats>
-__device__ __forceinline__ void strided_batch4(float* win, const float* __restrict__ plane, int HW, int H, int W,
-                                               const RoiGeom& g, int wh, int ww, int bs, int OH, int OW,
-                                               float* __restrict__ out_rc, int C, char* pair_r, int c_abs) {
-  stage_window4<NCS, LDSF>(win, plane, HW, W, g, wh, ww);
-  __syncthreads();
-  if (g.pow2)
-    fwd_pool4_strided<NCS, true, LDSF>((const f4*)win, ww, g, H, W, bs, OH, OW, out_rc, C, pair_r, c_abs);
-  else
-    fwd_pool4_strided<NCS, false, LDSF>((const f4*)win, ww, g, H, W, bs, OH, OW, out_rc, C, pair_r, c_abs);
-  __syncthreads();
-}
-
-// Two launches share the RoIs by window size: windows of up to kSmallWindow cells (most proposals) run with the 17 KB
-// window budget and eight workgroups per CU; larger windows with a 64 KB budget, so that they still stage 8-16
-// channels per batch instead of 1-4 (a 30x40-cell window took 32 single-channel batches per workgroup and those
-// few RoIs set the kernel's duration).  A workgroup whose RoI belongs to the other launch exits after the geometry.
-constexpr int kSmallWindow = 272;      // 4352 / 16: the 17 KB budget still holds 16 channels
-constexpr int kBigLdsFloats = 16384;   // 64 KB
-
-template <int LDSF, bool BIG>
-__global__ __launch_bounds__(kThreads) void roi_align_fwd_strided_nhwc_kernel(
-    const float* __restrict__ in, const float* __restrict__ rois, float* __restrict__ out, int R, int batch, int C,
-    int H, int W, int PH, int PW, int bs, int OH, int OW, float scale, int sampling_ratio, int pair_out) {
-  __shared__ __attribute__((aligned(16))) float win[LDSF];
-  const int r = blockIdx.x % R;
-  const int ct = blockIdx.x / R;
-  const int c_begin = ct * kCPB;
-  const int c_end = min(C, c_begin + kCPB);
-  const int HW = H * W;
-  const RoiGeom g = make_geom(rois + (long)r * 5, scale, H, W, PH, PW, sampling_ratio, batch);
-  float* out_r = out + (long)r * OH * OW * C;   // both layouts take 4*C bytes per bin
-  char* pair_r = pair_out ? (char*)out_r : nullptr;
-  if (g.empty) {
-    if (BIG) return;
-    for (int i = threadIdx.x; i < OH * OW * (c_end - c_begin); i += kThreads) {
-      const long obin = i / (c_end - c_begin);
-      const int c = c_begin + i % (c_end - c_begin);
-      if (pair_r) pool_store1_pair(pair_r, obin, c, C, 0.f);
-      else out_r[obin * C + c] = 0.f;
-    }
-    return;
-  }
-  const int wh = g.wy1 - g.wy0 + 1, ww = g.wx1 - g.wx0 + 1;
-  const int warea = wh * ww;
-  if ((warea > kSmallWindow) != BIG) return;  // the other launch owns this RoI (empty RoIs: handled above, by the small one)
-  // small windows (most proposals: <= 136 cells): all 32 channels of the block in ONE batch -- half the barriers, and
-  // every bin is written as a whole 128-byte line (fp32: 32 channels; pair layout: 64 B hi | 64 B lo)
-  const int cs_max = min(2 * kMaxBatch, LDSF / warea);
-  const float* img = in + (long)g.b * C * HW;
-  const bool vec_ok = (C & 3) == 0;  // float4 stores need 16-byte aligned channel groups
-  int c = c_begin;
-  while (c < c_end) {
-    const int left = c_end - c;
-    const float* plane = img + (long)c * HW;
-    float* o = out_r + c;
-    const int n = min(left, cs_max);
-    if (n >= 32 && vec_ok) {
-      strided_batch4<32, LDSF>(win, plane, HW, H, W, g, wh, ww, bs, OH, OW, o, C, pair_r, c);
-      c += 32;
-    } else if (n >= 16 && vec_ok) {
-      strided_batch4<16, LDSF>(win, plane, HW, H, W, g, wh, ww, bs, OH, OW, o, C, pair_r, c);
-      c += 16;
-    } else if (n >= 8 && vec_ok) {
-      strided_batch4<8, LDSF>(win, plane, HW, H, W, g, wh, ww, bs, OH, OW, o, C, pair_r, c);
-      c += 8;
-    } else if (n >= 4 && vec_ok) {
-      strided_batch4<4, LDSF>(win, plane, HW, H, W, g, wh, ww, bs, OH, OW, o, C, pair_r, c);
-      c += 4;
-    } else if (n >= 1) {  // one channel through LDS in the plain layout
-      for (int idx = threadIdx.x; idx < warea; idx += kThreads) {
-        const int y = idx / ww, x = idx - (idx / ww) * ww;
-        win[idx] = plane[(g.wy0 + y) * W + (g.wx0 + x)];
-      }
-      __syncthreads();
-      fwd_pool_strided<1>(win, warea, ww, g.wy0, g.wx0, g, H, W, bs, OH, OW, o, C, pair_r, c);
-      __syncthreads();
-      c += 1;
-    } else {  // window larger than the LDS budget: gather from global
-      fwd_pool_strided<1>(plane, HW, W, 0, 0, g, H, W, bs, OH, OW, o, C, pair_r, c);
-      c += 1;
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------
 // Strided pooler on an NHWC (channels-last) map.  The trunk computes in NHWC; read in that layout every bilinear tap
 // of a sample is one contiguous C-vector, so the pooler needs no LDS window staging at all: lanes run over channel
 // groups of 4 (one 16-byte load per tap, a whole 4 KB line per wave-pair at C = 1024), the 256 threads of a workgroup
 // own one RoI and walk its OH x OW bins together.  Per (bin, channel) the samples are visited in the reference's order
 // with the reference's expressions (fwd_pool4_strided above, the exact kernel's arithmetic), so the result is
-// BIT-IDENTICAL to the NCHW kernels; neighbouring samples' taps are served by L1 / L2 (the map is 17 MB per image).
+// BIT-IDENTICAL to the exact kernel's bins (roi_align_fwd_kernel on the same map in NCHW); neighbouring samples' taps
+// are served by L1 / L2 (the map is 17 MB per image).
 // ---------------------------------------------------------------------------------------
 template <bool FAST>
 __device__ __forceinline__ void pool_nhwc_strided(const f4* __restrict__ img4, const RoiGeom& g, int H, int W, int C4,
@@ -702,11 +551,13 @@ __global__ __launch_bounds__(kThreads) void roi_align_fwd_nhwc_in_strided_kernel
 // workgroup per RoI was tried: the few large RoIs then run on a few workgroups and set the duration -- 289 us in the step
 // against 176 us for this form and 248 us for the direct form alone).
 // ---------------------------------------------------------------------------------------
-template <int NCS, int LDSF = kFwdLdsFloats>
+constexpr int kSmallWindow = 272;      // 4352 / 16: the 17 KB budget still holds 16 channels
+
+template <int NCS>
 __device__ __forceinline__ void stage_window4_nhwc(float* win, const float* __restrict__ img_c0, int C, int W,
                                                    const RoiGeom& g, int wh, int ww) {
   constexpr int NG = NCS / 4;
-  constexpr int SG = LDSF / NCS;
+  constexpr int SG = kFwdLdsFloats / NCS;
   f4* win4 = (f4*)win;
   const int n = wh * ww * NG;
   const float inv_ww = 1.f / (float)ww;
@@ -1023,7 +874,7 @@ extern "C" int ovis_roi_align_backward_ws_f32(const float* grad_output, const fl
                                      pooled_h, pooled_w, spatial_scale, sampling_ratio, stream);
 }
 
-// Backward of the strided pooler (ovis_roi_align_forward_strided_nhwc_f32): grad_output holds only the bins
+// Backward of the strided pooler (ovis_roi_align_forward_strided_from_nhwc_f32): grad_output holds only the bins
 // (bin_stride * i, bin_stride * j) as [num_rois, channels, ceil(pooled_h / bin_stride), ceil(pooled_w / bin_stride)]
 // tiles -- a quarter of the bytes of the zero-scattered full tile at bin_stride 2.  Plane-owner kernel only: shapes it
 // does not cover return OVIS_ERANGE (the caller scatters into a full tile and uses ovis_roi_align_backward_ws_f32).
@@ -1090,27 +941,6 @@ extern "C" int ovis_roi_align_forward_ws_f32(const float* input, const float* ro
                                     spatial_scale, sampling_ratio, stream);
 }
 
-static int strided_nhwc_launch(const float* input, const float* rois, float* output, int num_rois, int batch,
-                               int channels, int height, int width, int pooled_h, int pooled_w, int bin_stride,
-                               float spatial_scale, int sampling_ratio, int pair_out, void* stream);
-
-extern "C" int ovis_roi_align_forward_strided_nhwc_f32(const float* input, const float* rois, float* output,
-                                                       int num_rois, int batch, int channels, int height, int width,
-                                                       int pooled_h, int pooled_w, int bin_stride,
-                                                       float spatial_scale, int sampling_ratio, void* stream) {
-  return strided_nhwc_launch(input, rois, output, num_rois, batch, channels, height, width, pooled_h, pooled_w, bin_stride,
-                             spatial_scale, sampling_ratio, 0, stream);
-}
-
-extern "C" int ovis_roi_align_forward_strided_pair_f32(const float* input, const float* rois, void* output_pair,
-                                                       int num_rois, int batch, int channels, int height, int width,
-                                                       int pooled_h, int pooled_w, int bin_stride,
-                                                       float spatial_scale, int sampling_ratio, void* stream) {
-  if (channels % 32 != 0 || ((uintptr_t)output_pair & 15)) return OVIS_ERANGE;
-  return strided_nhwc_launch(input, rois, (float*)output_pair, num_rois, batch, channels, height, width, pooled_h,
-                             pooled_w, bin_stride, spatial_scale, sampling_ratio, 1, stream);
-}
-
 // input in NHWC ([batch, height, width, channels] contiguous); output NHWC fp32 (pair_out == 0) or pair rows
 extern "C" int ovis_roi_align_forward_strided_from_nhwc_f32(const float* input_nhwc, const float* rois, void* output,
                                                             int num_rois, int batch, int channels, int height,
@@ -1144,29 +974,5 @@ extern "C" int ovis_roi_align_forward_strided_from_nhwc_f32(const float* input_n
                        input_nhwc, rois, (float*)output, num_rois, batch, channels, height, width, pooled_h, pooled_w,
                        bin_stride, oh, ow, spatial_scale, sampling_ratio, pair_out);
   OVIS_LAUNCH_CHECK();
-  return OVIS_OK;
-}
-
-static int strided_nhwc_launch(const float* input, const float* rois, float* output, int num_rois, int batch,
-                               int channels, int height, int width, int pooled_h, int pooled_w, int bin_stride,
-                               float spatial_scale, int sampling_ratio, int pair_out, void* stream) {
-  if (num_rois < 0 || batch < 0 || channels < 0 || height <= 0 || width <= 0 || pooled_h <= 0 || pooled_w <= 0 ||
-      bin_stride <= 0)
-    return OVIS_EINVAL;
-  if (num_rois == 0 || channels == 0) return OVIS_OK;
-  if (!input || !rois || !output) return OVIS_EINVAL;
-  const int oh = (pooled_h + bin_stride - 1) / bin_stride, ow = (pooled_w + bin_stride - 1) / bin_stride;
-  const long blocks = (long)ovis_ceil_div(channels, kCPB) * num_rois;
-  if (blocks > 0x7fffffffL) return OVIS_ERANGE;
-  hipLaunchKernelGGL((roi_align_fwd_strided_nhwc_kernel<kFwdLdsFloats, false>), dim3((unsigned)blocks), dim3(kThreads), 0,
-                     (hipStream_t)stream, input, rois, output, num_rois, batch, channels, height, width, pooled_h,
-                     pooled_w, bin_stride, oh, ow, spatial_scale, sampling_ratio, pair_out);
-  OVIS_LAUNCH_CHECK();
-  if ((long)height * width > kSmallWindow) {  // larger windows can exist at all
-    hipLaunchKernelGGL((roi_align_fwd_strided_nhwc_kernel<kBigLdsFloats, true>), dim3((unsigned)blocks), dim3(kThreads), 0,
-                       (hipStream_t)stream, input, rois, output, num_rois, batch, channels, height, width, pooled_h,
-                       pooled_w, bin_stride, oh, ow, spatial_scale, sampling_ratio, pair_out);
-    OVIS_LAUNCH_CHECK();
-  }
   return OVIS_OK;
 }

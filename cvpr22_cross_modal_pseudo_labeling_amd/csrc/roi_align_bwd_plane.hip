@@ -77,7 +77,7 @@ __global__ __launch_bounds__(kPlanThreads) void roi_bwd_plan_kernel(
   // the data operand carries its hi halves in groups 0, 1 and its lo halves in groups 2, 3, so ONE K = 16 product against the
   // table's hi halves (in every group) is hi.hi + lo.hi, and one against its lo halves is hi.lo + lo.lo.
   // bin_stride > 1: grad_output holds only the bins (bin_stride * i, bin_stride * j) the strided pooler produced
-  // (roi_align_fwd_strided_nhwc_kernel), as [R, C, TH, TW] tiles; the tables carry those bins' weights, every other
+  // (roi_align_fwd_nhwc_in_strided_lds_kernel), as [R, C, TH, TW] tiles; the tables carry those bins' weights, every other
   // bin's gradient is zero by construction and is never read.
   const int TH = (PH + bin_stride - 1) / bin_stride, TW = (PW + bin_stride - 1) / bin_stride;
   __shared__ int wave_total[kPlanThreads / 64];

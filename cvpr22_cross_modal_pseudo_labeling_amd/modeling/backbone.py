@@ -369,8 +369,9 @@ class ResNetC4(nn.Module):
             # per step against MIOpen's NCHW kernels (both with a warm MIOpen kernel cache; ``train_nhwc = False``
             # selects MIOpen).
             y = chain_nhwc(blocks, x.permute(0, 2, 3, 1).contiguous())
-            # the C4 map stays in NHWC memory (an NCHW-shaped view of it): the poolers read channels-last maps in place
-            # (csrc/roi_align.hip::roi_align_fwd_nhwc_in_strided_kernel) and the RPN head wants NHWC rows anyway
+            # the C4 map stays in NHWC memory (an NCHW-shaped view of it): the strided pooler reads channels-last maps in
+            # place (csrc/roi_align.hip::roi_align_fwd_nhwc_in_strided_lds_kernel; it has no other form, ``_C`` copies a
+            # map of the per-layer route below to this layout) and the RPN head wants NHWC rows anyway
             return [y.permute(0, 3, 1, 2)]
         x = x.contiguous()  # the GEMM stem hands over channels_last memory; MIOpen's NCHW kernels are the faster ones here
         for name in self.stages:

@@ -69,28 +69,18 @@ int ovis_roi_align_forward_ws_f32(const float* input, const float* rois, float* 
                                   int sampling_ratio, void* workspace, size_t workspace_bytes,
                                   void* stream);
 
-/* Forward fused with the consumer's stride (extension): pools only bins (bin_stride*i,
- * bin_stride*j) and writes output [num_rois, ceil(pooled_h/bin_stride),
- * ceil(pooled_w/bin_stride), channels] (NHWC).  The res5 head's first 1x1 convolution has
- * stride 2 (mb/modeling/backbone/resnet.py:258-275, STRIDE_IN_1X1), so it never reads the other
- * three quarters of the 14x14 tile.  Per-bin arithmetic is ovis_roi_align_forward_f32's:
- * out[r,i,j,c] is bit-identical to that kernel's [r,c,bin_stride*i,bin_stride*j]. */
-int ovis_roi_align_forward_strided_nhwc_f32(const float* input, const float* rois, float* output,
-                                            int num_rois, int batch, int channels, int height,
-                                            int width, int pooled_h, int pooled_w, int bin_stride,
-                                            float spatial_scale, int sampling_ratio, void* stream);
-
-/* The same bins written in PAIR layout (see ovis_split_pair_f32 below: per 32 channels 64 B bf16 hi | 64 B bf16 lo;
- * the values are the exact split of the fp32 results above), [num_rois * oh * ow, channels] pair rows: the operand of
- * the res5 head's first split GEMM without an fp32 copy and a split pass.  channels % 32 == 0. */
-int ovis_roi_align_forward_strided_pair_f32(const float* input, const float* rois, void* output_pair,
-                                            int num_rois, int batch, int channels, int height, int width,
-                                            int pooled_h, int pooled_w, int bin_stride,
-                                            float spatial_scale, int sampling_ratio, void* stream);
-/* The same two poolers for a feature map that is already NHWC ([batch, height, width, channels] contiguous: what the
- * trunk of this library computes in): no window staging, every bilinear tap is one contiguous channel vector; samples
- * are visited in the reference's order, so the bins are bit-identical to the forms above.  pair_out != 0: pair rows
- * (channels % 32 == 0), else NHWC fp32 (channels % 4 == 0). */
+/* Forward fused with the consumer's stride (extension): pools only bins (bin_stride*i, bin_stride*j) of a feature map
+ * given in NHWC memory ([batch, height, width, channels] contiguous: what the trunk of this library computes in; other
+ * layouts are copied to it by the caller).  The res5 head's first 1x1 convolution has stride 2
+ * (mb/modeling/backbone/resnet.py:258-275, STRIDE_IN_1X1), so it never reads the other three quarters of the 14x14
+ * tile.  Per-bin arithmetic is ovis_roi_align_forward_f32's, samples visited in the reference's order: out[r,i,j,c] is
+ * bit-identical to that kernel's [r,c,bin_stride*i,bin_stride*j] on the same map in NCHW.  With oh, ow =
+ * ceil(pooled / bin_stride):
+ *   pair_out == 0: output [num_rois, oh, ow, channels] fp32 (NHWC); channels % 4 == 0.
+ *   pair_out != 0: the same bins in PAIR layout (see ovis_split_pair_f32 below: per 32 channels 64 B bf16 hi | 64 B bf16
+ *                  lo, the exact split of the fp32 results), [num_rois * oh * ow, channels] pair rows: the operand of the
+ *                  res5 head's first split GEMM without an fp32 copy and a split pass; channels % 32 == 0.
+ * input_nhwc and output must be 16-byte aligned.  OVIS_ERANGE when a channel or alignment constraint is not met. */
 int ovis_roi_align_forward_strided_from_nhwc_f32(const float* input_nhwc, const float* rois, void* output, int num_rois,
                                                  int batch, int channels, int height, int width, int pooled_h,
                                                  int pooled_w, int bin_stride, float spatial_scale, int sampling_ratio,
@@ -121,7 +111,7 @@ int ovis_roi_align_backward_ws_f32(const float* grad_output, const float* rois,
                                    int height, int width, int pooled_h, int pooled_w,
                                    float spatial_scale, int sampling_ratio, void* workspace,
                                    size_t workspace_bytes, void* stream);
-/* Backward of ovis_roi_align_forward_strided_nhwc_f32 (the pooler fused with the stride of the res5 head's first
+/* Backward of ovis_roi_align_forward_strided_from_nhwc_f32 (the pooler fused with the stride of the res5 head's first
  * convolution): grad_output [num_rois, channels, ceil(pooled_h / bin_stride), ceil(pooled_w / bin_stride)] holds the
  * gradient of the bins (bin_stride * i, bin_stride * j) only -- the other bins were never computed, their gradient is
  * zero -- so a quarter of the bytes of the full tile are read at bin_stride 2.  Same workspace as the form above.

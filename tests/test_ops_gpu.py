@@ -26,6 +26,34 @@ def _rois(g, r, n_img, img_w, img_h, wmin, wmax):
     return torch.cat([b, x1, y1, (x1 + w).clamp(max=img_w - 1), (y1 + h).clamp(max=img_h - 1)], 1)
 
 
+def _channels_last(x):
+    """Same values and shape, NHWC memory: what the trunk hands to the poolers."""
+    return x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+
+
+def _window_cells(rois, scale, n_img, h, w, p, sampling_ratio):
+    """Cells of each RoI's feature-map window (0: no sample inside the map) -- the host twin of ``make_geom`` in
+    csrc/roi_geom.h, in float32 like the kernel."""
+    f = np.float32
+    cells = []
+    for b, x1, y1, x2, y2 in rois.numpy().astype(f):
+        size = []
+        for lo, hi, n in ((y1, y2, h), (x1, x2, w)):
+            start = f(lo * f(scale))
+            roi = max(f(f(hi * f(scale)) - start), f(1))
+            bin_ = f(roi / f(p))
+            grid = sampling_ratio if sampling_ratio > 0 else int(np.ceil(bin_))
+            first = f(start + f(f(0.5) * bin_) / f(grid))
+            last = f(f(start + f(f(p - 1) * bin_)) + f(f(f(grid - 1) + f(0.5)) * bin_) / f(grid))
+            if not (np.isfinite(first) and np.isfinite(last)) or last < -1 or first > n:
+                size.append(0)
+                continue
+            low = lambda v: 0 if v <= 0 else min(int(v), n - 1)
+            size.append(min(low(min(last, f(n))) + 1, n - 1) - low(max(first, f(-1))) + 1)
+        cells.append(size[0] * size[1] if 0 <= int(b) < n_img else 0)
+    return np.array(cells)
+
+
 # ---------------------------------------------------------------- RoIAlign forward
 def test_roi_align_forward_golden_bit_exact(C, golden_dir):
     z = np.load(os.path.join(golden_dir, "roi_align_forward.npz"))
@@ -78,8 +106,11 @@ def test_roi_align_forward_matrix_core_edge_rois(C, oracle_mod):
 
 def test_roi_align_forward_strided_nhwc_bit_exact(C, golden_dir):
     """The pooler fused with the consumer's stride: bins (2i, 2j) only, NHWC -- bit-identical to the same bins of the
-    bit-exact forward (all staging paths: 16/8/4-channel LDS batches, one-channel LDS, global gather; 70 channels =
-    two full 32-channel tiles + a partial one), and its backward equals the zero-scattered full backward to round-off."""
+    bit-exact forward, and its backward equals the zero-scattered full backward to round-off.  Contiguous NCHW maps reach
+    the NHWC kernels through one layout copy; channel counts that are no multiple of 4 (70, 5, 6 below) take the
+    definition of the op (the exact kernel's slice).  The same cases run on channels-last maps with channel counts the
+    kernels take: 72 (no multiple of 32: the direct kernel, one workgroup per RoI), 64 (two whole 32-channel tiles: the
+    LDS kernel) and the golden map's own 8."""
     from cvpr22_cross_modal_pseudo_labeling_amd.layers import ROIAlign
 
     z = np.load(os.path.join(golden_dir, "roi_align_forward.npz"))
@@ -88,15 +119,28 @@ def test_roi_align_forward_strided_nhwc_bit_exact(C, golden_dir):
         full = C.roi_align_forward(x, rois, scale, ph, ph, sr)
         got = C.roi_align_forward_strided_nhwc(x, rois, scale, ph, ph, sr, s)
         assert torch.equal(got, full[:, :, ::s, ::s].permute(0, 2, 3, 1)), (ph, sr, s)
+        for rep in (1, 9, 8):   # 8, 72, 64 channels: the golden channels repeated, channels-last memory
+            got = C.roi_align_forward_strided_nhwc(_channels_last(x.repeat(1, rep, 1, 1)), rois, scale, ph, ph, sr, s)
+            assert torch.equal(got, full.repeat(1, rep, 1, 1)[:, :, ::s, ::s].permute(0, 2, 3, 1)), (ph, sr, s, rep)
     g = torch.Generator().manual_seed(8)
     xb = torch.randn(2, 70, 50, 84, generator=g).cuda()
     rb = torch.cat([_rois(g, 40, 2, 1333, 800, 8, 900), torch.tensor([[0, 0.0, 0.0, 1332.0, 799.0]])]).cuda()
     full = C.roi_align_forward(xb, rb, 1 / 16, 14, 14, 0)
     assert torch.equal(C.roi_align_forward_strided_nhwc(xb, rb, 1 / 16, 14, 14, 0, 2), full[:, :, ::2, ::2].permute(0, 2, 3, 1))
-    big = torch.randn(1, 5, 120, 160, generator=g).cuda()  # whole-map RoI: 19200-cell window -> global gather path
+    big = torch.randn(1, 5, 120, 160, generator=g).cuda()  # whole-map RoI: 19200-cell window
     rbig = torch.tensor([[0, 0.0, 0.0, 2559.0, 1919.0], [0, 30.0, 40.0, 900.0, 700.0]]).cuda()
     assert torch.equal(C.roi_align_forward_strided_nhwc(big, rbig, 1 / 16, 14, 14, 0, 2),
                        C.roi_align_forward(big, rbig, 1 / 16, 14, 14, 0)[:, :, ::2, ::2].permute(0, 2, 3, 1))
+    g2 = torch.Generator().manual_seed(9)   # its own stream: the draws from `g` below stay what they were
+    xw = torch.randn(2, 72, 50, 84, generator=g2).cuda()
+    for c in (72, 64):      # the random RoIs on channels-last maps: direct kernel / LDS kernel
+        full = C.roi_align_forward(xw[:, :c].contiguous(), rb, 1 / 16, 14, 14, 0)
+        assert torch.equal(C.roi_align_forward_strided_nhwc(_channels_last(xw[:, :c]), rb, 1 / 16, 14, 14, 0, 2),
+                           full[:, :, ::2, ::2].permute(0, 2, 3, 1)), c
+    big = torch.randn(1, 32, 120, 160, generator=g2).cuda()
+    for c in (32, 8):       # 32: the direct form inside the LDS kernel (window above kSmallWindow); 8: the direct kernel
+        assert torch.equal(C.roi_align_forward_strided_nhwc(_channels_last(big[:, :c]), rbig, 1 / 16, 14, 14, 0, 2),
+                           C.roi_align_forward(big[:, :c].contiguous(), rbig, 1 / 16, 14, 14, 0)[:, :, ::2, ::2].permute(0, 2, 3, 1)), c
     # autograd: same gradient as slicing the full layer's output
     layer = ROIAlign((14, 14), 1 / 16, 0)
     xa = xb[:, :6].clone().requires_grad_(True)
@@ -112,15 +156,24 @@ def test_roi_align_forward_strided_nhwc_bit_exact(C, golden_dir):
 @pytest.mark.parametrize("c", [64, 100, 1024])
 def test_roi_align_strided_poolers_on_channels_last_map_bit_exact(C, c):
     """A channels-last feature map (NCHW view of NHWC memory: what the trunk hands over) is pooled in place by the
-    NHWC-input kernel; bins bit-identical to the NCHW window-staging kernel and to the exact kernel's, fp32 and pair output,
-    RoIs of every size incl. one outside the map and non-power-of-two sampling grids."""
+    NHWC-input kernels; bins bit-identical to the exact kernel's and to what a contiguous NCHW map gives (which reaches the
+    same kernels through one layout copy), fp32 and pair output, RoIs of every size incl. one outside the map and
+    non-power-of-two sampling grids.  The RoI set is checked on the host to hold every window class of the LDS kernel
+    (C = 64, 1024): empty, whole tile in one batch (<= 136 cells), two 16-channel batches (137-272), direct form (> 272)."""
     g = torch.Generator().manual_seed(c)
     n, h, w = 2, 50, 84
     x = torch.randn(n, c, h, w, generator=g).cuda()
-    x_cl = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)          # same values, NHWC memory
+    x_cl = _channels_last(x)
     assert not x_cl.is_contiguous()
     rois = torch.cat([_rois(g, 60, n, 1333, 800, 8, 1200), torch.tensor([[0, 0.0, 0.0, 1332.0, 799.0], [1, 5000.0, 5000.0, 5100.0, 5100.0],
-                                                                        [1, 100.0, 50.0, 820.0, 700.0]])]).cuda()
+                                                                        [1, 100.0, 50.0, 820.0, 700.0], [0, 100.0, 100.0, 200.0, 180.0],
+                                                                        [1, 300.0, 200.0, 520.0, 420.0]])])
+    for sr in (0, 2, 3):   # the sampling grids used below
+        cells = _window_cells(rois, 1 / 16, n, h, w, 14, sr)
+        classes = {"empty": int((cells == 0).sum()), "<= 136": int(((cells > 0) & (cells <= 136)).sum()),
+                   "137-272": int(((cells > 136) & (cells <= 272)).sum()), "> 272": int((cells > 272).sum())}
+        assert all(classes.values()), f"RoIs per window class at sampling_ratio {sr}: {classes}"
+    rois = rois.cuda()
     want = C.roi_align_forward(x, rois, 1 / 16, 14, 14, 0)[:, :, ::2, ::2].permute(0, 2, 3, 1)
     got = C.roi_align_forward_strided_nhwc(x_cl, rois, 1 / 16, 14, 14, 0, 2)
     assert torch.equal(got, want)

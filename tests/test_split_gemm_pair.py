@@ -564,7 +564,8 @@ def test_bottleneck_pair_pooled_output_and_fused_pool_gradient():
 
 def test_strided_pooler_pair_output_is_split_of_fp32_output():
     """roi_align_forward_strided_pair == split_pair(roi_align_forward_strided_nhwc) bit for bit (small, large, clipped and
-    empty RoIs), and the res5 head gives identical results from either hand-over."""
+    empty RoIs), and the res5 head gives identical results from either hand-over.  The contiguous map reaches the NHWC
+    kernels through one layout copy per call."""
     C = _C()
     g = torch.Generator().manual_seed(21)
     x = torch.randn(2, 64, 50, 84, generator=g).cuda()
