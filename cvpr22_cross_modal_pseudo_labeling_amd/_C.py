@@ -730,6 +730,24 @@ def project_pasted_masks(mask_probs, gt_boxes, gt_index, boxes, image_size, reso
     return out
 
 
+def paste_masks(probs, boxes, image_size, threshold=0.5):
+    """bool [P, H, W]: the masks ``Masker(threshold, padding=1)`` pastes for probs [P, M, M] and boxes [P, 4] xyxy
+    (``ovis_paste_masks_u8``; mask_head/inference.py:100-205), image_size = (height, width).  One launch, no host read;
+    the kernel writes every byte, so the canvas is not filled first."""
+    probs, boxes = _dev(probs, "probs"), _dev(boxes, "boxes")
+    if probs.dim() != 3 or probs.shape[1] != probs.shape[2] or boxes.shape != (probs.shape[0], 4):
+        raise RuntimeError("paste_masks: expected probs [P,M,M] and boxes [P,4]")
+    p, h, w = probs.shape[0], int(image_size[0]), int(image_size[1])
+    out = torch.empty((p, h, w), dtype=torch.bool, device=probs.device)
+    if p == 0:
+        return out
+    with _on(probs.device):
+        rc = _L.ovis_paste_masks_u8(probs.data_ptr(), boxes.data_ptr(), p, probs.shape[1], h, w, float(threshold),
+                                    out.data_ptr(), _stream())
+    _lib.check(rc, "paste_masks")
+    return out
+
+
 def split_pair(x):
     """x [rows, cols] f32 (row-strided view ok, cols % 32 == 0) -> pair layout [rows, 2*cols] bf16: per 32 values
     [hi(32) | lo(32)].  See include/ovis_hip.h."""
@@ -1218,6 +1236,27 @@ def project_polygon_masks(coords, polygon_start, instance_start, gt_index, boxes
                                                    int(image_size[0]), int(image_size[1]), int(resolution), out.data_ptr(),
                                                    _stream())
         _lib.check(rc, "project_polygon_masks")
+    return out
+
+
+def polygons_to_masks(coords, polygon_start, instance_start, size):
+    """uint8 [G, height, width]: every polygon instance rasterised over the whole image (``ovis_polygons_to_masks_u8``;
+    segmentation_mask.py:326-334), any image size.  The layout of ``project_polygon_masks``; size = (width, height).
+    Device tensors only: host polygons are ``_cpu.polygons_to_masks``."""
+    polygon_start = _dev(polygon_start, "polygon_start", torch.int32)
+    instance_start = _dev(instance_start, "instance_start", torch.int32)
+    coords = _dev(coords, "coords") if coords.numel() else coords
+    g, npoly = instance_start.numel() - 1, polygon_start.numel() - 1
+    w, h = int(size[0]), int(size[1])
+    out = torch.empty((g, h, w), dtype=torch.uint8, device=polygon_start.device)
+    if g:
+        with _on(out.device):
+            nbytes = _L.ovis_polygons_to_masks_workspace_bytes(npoly, w, h)
+            ws = torch.empty((nbytes,), dtype=torch.uint8, device=out.device)
+            rc = _L.ovis_polygons_to_masks_u8(coords.data_ptr() if coords.numel() else 0, polygon_start.data_ptr(),
+                                              instance_start.data_ptr(), g, npoly, w, h, ws.data_ptr() if nbytes else 0, nbytes,
+                                              out.data_ptr(), _stream())
+        _lib.check(rc, "polygons_to_masks")
     return out
 
 

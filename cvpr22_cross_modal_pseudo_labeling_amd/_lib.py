@@ -36,6 +36,7 @@ SIGNATURES = {
     "ovis_nms_grouped_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _vp, _sz, _vp, _vp, _vp]),
     "ovis_sample_fg_bg": (_i, [_vp, _i, _i, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "ovis_project_pasted_masks_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "ovis_paste_masks_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "ovis_nms_presorted_workspace_bytes": (_sz, [_i, _i]),
     "ovis_nms_presorted_batched_f32": (_i, [_vp, _vp, _i, _i, _f, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "ovis_box_decode_f32": (_i, [_vp, _l, _vp, _l, _l, _i, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
@@ -85,6 +86,8 @@ SIGNATURES = {
     "ovis_region_noun_align_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ovis_text_embed_f32": (_i, [_vp, _l, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "ovis_project_polygon_masks_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ovis_polygons_to_masks_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ovis_polygons_to_masks_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "ovis_sgd_momentum_multi_f32": (_i, [_vp, _vp, _i, _f, _f, _f, _i, _vp]),
     "ovis_bottleneck_identity_backward_workspace_bytes": (_sz, [_l, _i, _i, _i, _i, _i, _i]),
     "ovis_bottleneck_identity_backward": (_i, [_vp, _l] * 7 + [_vp] * 3 + [_l, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_sz, _i, _vp, _vp]),

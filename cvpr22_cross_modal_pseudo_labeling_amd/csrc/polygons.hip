@@ -126,6 +126,140 @@ __global__ __launch_bounds__(64) void project_polygons_kernel(
   }
 }
 
+// ---- whole-image masks: SegmentationMask(mode='poly').convert('mask') (segmentation_mask.py:326-334) at any canvas size ------
+// The device twin of ovis_cpu_polygons_to_masks_u8 (csrc/cpu/ovis_cpu.cpp): no crop, no resize, w x h positions instead of
+// M x M.  A million positions do not fit the LDS toggle array above, so the toggles live in the caller's workspace as ONE
+// BIT per column-major position and polygon:
+//   1. toggle : every boundary point xors its bit (global atomic; xor commutes, so the result does not depend on the order);
+//   2. parity : the parity of every chunk of kChunkWords words;
+//   3. fill   : per chunk, the xor of the earlier chunks' parities is the carry in; inside the chunk a word's bits become their
+//               running parity (shift-xor ladder), words and lanes are chained by ballots -- in place;
+//   4. expand : out[g][y][x] = OR over the instance's polygons of bit x * h + y (column-major -> row-major): a lane owns a
+//               column and 64 rows (three words, funnel-shifted), a wave writes 64 consecutive bytes per row.
+// The parity runs over ALL w * h positions, not per column: a point clamped to y = h toggles the next column's first position.
+constexpr int kChunkThreads = 256;
+constexpr int kChunkWords = 8 * kChunkThreads;  // 65 536 positions per chunk
+
+__global__ __launch_bounds__(256) void polygon_toggle_kernel(const float* __restrict__ coords, const int* __restrict__ poly_start,
+                                                            int w, int h, long words_per_poly, unsigned* __restrict__ bits) {
+  const int poly = blockIdx.x;
+  const int c0 = poly_start[poly];
+  const int k = (poly_start[poly + 1] - c0) / 2;   // vertices
+  if (k < 3) return;                                // PolygonInstance.__init__ drops polygons with < 6 numbers
+  unsigned* b = bits + (long)poly * words_per_poly;
+  const long npos = (long)w * h;
+  for (int j = blockIdx.y; j < k; j += gridDim.y) {
+    const int jn = j + 1 == k ? 0 : j + 1;
+    // rleFrPoly's scale-by-5 rounding in double (_mask.pyx hands the float32 coordinates over as doubles: exact)
+    const int xs = (int)(5.0 * (double)coords[c0 + 2 * j] + .5), ys = (int)(5.0 * (double)coords[c0 + 2 * j + 1] + .5);
+    const int xe = (int)(5.0 * (double)coords[c0 + 2 * jn] + .5), ye = (int)(5.0 * (double)coords[c0 + 2 * jn + 1] + .5);
+    const int steps = max(abs(xe - xs), abs(ye - ys));
+    for (int d = 1 + (int)threadIdx.x; d <= steps; d += 256) {
+      int u0, v0, u1, v1;
+      edge_point(xs, ys, xe, ye, d - 1, &u0, &v0);
+      edge_point(xs, ys, xe, ye, d, &u1, &v1);
+      if (u1 == u0) continue;
+      double xd = (double)(u1 < u0 ? u1 : u1 - 1);
+      xd = (xd + .5) / 5.0 - .5;
+      if (floor(xd) != xd || xd < 0 || xd > w - 1) continue;
+      double yd = (double)(v1 < v0 ? v1 : v0);
+      yd = (yd + .5) / 5.0 - .5;
+      if (yd < 0) yd = 0; else if (yd > h) yd = h;
+      yd = ceil(yd);
+      const long pos = (long)xd * h + (long)yd;   // <= w * h; position w * h is behind the last pixel
+      if (pos < npos) atomicXor(&b[pos >> 5], 1u << (pos & 31));
+    }
+  }
+}
+
+// parity (0 / 1) of `v` xor-ed over the workgroup's kChunkThreads threads
+__device__ __forceinline__ unsigned block_parity(unsigned v, unsigned* sh) {
+  const unsigned long long m = __ballot(v & 1u);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = (unsigned)__popcll(m) & 1u;
+  __syncthreads();
+  unsigned r = 0;
+#pragma unroll
+  for (int i = 0; i < kChunkThreads / 64; ++i) r ^= sh[i];
+  __syncthreads();
+  return r;
+}
+
+__global__ __launch_bounds__(kChunkThreads) void polygon_chunk_parity_kernel(const unsigned* __restrict__ bits, int chunks,
+                                                                            long words_per_poly,
+                                                                            unsigned* __restrict__ chunk_parity) {
+  __shared__ unsigned sh[kChunkThreads / 64];
+  const int c = blockIdx.x, poly = blockIdx.y;
+  const uint4* src = (const uint4*)(bits + (long)poly * words_per_poly + (long)c * kChunkWords) + 2 * threadIdx.x;
+  const uint4 a = src[0], b = src[1];
+  const unsigned x = a.x ^ a.y ^ a.z ^ a.w ^ b.x ^ b.y ^ b.z ^ b.w;
+  const unsigned par = block_parity((unsigned)__popc(x), sh);
+  if (threadIdx.x == 0) chunk_parity[(long)poly * chunks + c] = par;
+}
+
+__global__ __launch_bounds__(kChunkThreads) void polygon_fill_kernel(unsigned* __restrict__ bits, int chunks, long words_per_poly,
+                                                                    const unsigned* __restrict__ chunk_parity) {
+  __shared__ unsigned sh[kChunkThreads / 64];
+  const int c = blockIdx.x, poly = blockIdx.y, tid = threadIdx.x;
+  // carry into the chunk: parity of everything in front of it
+  unsigned before = 0;
+  for (int i = tid; i < c; i += kChunkThreads) before ^= chunk_parity[(long)poly * chunks + i];
+  unsigned carry = block_parity(before, sh);
+  uint4* dst = (uint4*)(bits + (long)poly * words_per_poly + (long)c * kChunkWords) + 2 * tid;
+  const uint4 a = dst[0], b = dst[1];
+  unsigned wd[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  unsigned mine = 0;   // parity of the thread's eight words
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    unsigned v = wd[i];   // bit i := parity of bits 0 .. i
+    v ^= v << 1;
+    v ^= v << 2;
+    v ^= v << 4;
+    v ^= v << 8;
+    v ^= v << 16;
+    wd[i] = v;
+    mine ^= v >> 31;
+  }
+  // threads in front of this one: lower lanes of the wave, then the earlier waves
+  const unsigned long long m = __ballot(mine & 1u);
+  const int lane = tid & 63, wave = tid >> 6;
+  if (lane == 0) sh[wave] = (unsigned)__popcll(m) & 1u;
+  __syncthreads();
+  carry ^= (unsigned)__popcll(m & ((1ull << lane) - 1ull)) & 1u;
+#pragma unroll
+  for (int i = 0; i < kChunkThreads / 64; ++i) carry ^= i < wave ? sh[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const unsigned v = wd[i] ^ (0u - carry);
+    carry ^= wd[i] >> 31;
+    wd[i] = v;
+  }
+  dst[0] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+  dst[1] = make_uint4(wd[4], wd[5], wd[6], wd[7]);
+}
+
+__global__ __launch_bounds__(256) void polygon_expand_kernel(const unsigned* __restrict__ filled, const int* __restrict__ inst_start,
+                                                            int num_polygons, int w, int h, long words_per_poly,
+                                                            unsigned char* __restrict__ out) {
+  const int x = blockIdx.x * 256 + threadIdx.x, y0 = blockIdx.y * 64, g = blockIdx.z;
+  if (x >= w) return;
+  const int rows = min(64, h - y0);
+  const long pos = (long)x * h + y0;
+  const long wi = pos >> 5;
+  const int sh = (int)(pos & 31);
+  unsigned long long m = 0;
+  const int q0 = max(inst_start[g], 0), q1 = min(inst_start[g + 1], num_polygons);
+  for (int q = q0; q < q1; ++q) {
+    const unsigned* b = filled + (long)q * words_per_poly;
+    const unsigned long long a0 = b[wi];
+    const unsigned long long a1 = wi + 1 < words_per_poly ? b[wi + 1] : 0u;
+    const unsigned long long a2 = wi + 2 < words_per_poly ? b[wi + 2] : 0u;
+    const unsigned lo = (unsigned)(((a1 << 32) | a0) >> sh), hi = (unsigned)(((a2 << 32) | a1) >> sh);
+    m |= ((unsigned long long)hi << 32) | lo;
+  }
+  unsigned char* o = out + ((long)g * h + y0) * w + x;
+  for (int r = 0; r < rows; ++r) o[(long)r * w] = (unsigned char)((m >> r) & 1ull);
+}
+
 }  // namespace
 
 extern "C" int ovis_project_polygon_masks_f32(const float* coords, const int32_t* polygon_start,
@@ -139,6 +273,49 @@ extern "C" int ovis_project_polygon_masks_f32(const float* coords, const int32_t
   if (((uintptr_t)boxes & 15) != 0) return OVIS_EINVAL;
   hipLaunchKernelGGL(project_polygons_kernel, dim3((unsigned)num), dim3(64), 0, (hipStream_t)stream, coords, polygon_start,
                      instance_start, (const long*)gt_index, boxes, num, image_width, image_height, resolution, out);
+  OVIS_LAUNCH_CHECK();
+  return OVIS_OK;
+}
+
+static long polygon_words(int width, int height) {   // bit words per polygon, whole chunks
+  const long words = ((long)width * height + 31) / 32;
+  return (words + kChunkWords - 1) / kChunkWords * kChunkWords;
+}
+
+extern "C" size_t ovis_polygons_to_masks_workspace_bytes(int num_polygons, int width, int height) {
+  if (num_polygons <= 0 || width <= 0 || height <= 0) return 0;
+  const long words = polygon_words(width, height);
+  return (size_t)num_polygons * (size_t)(words + words / kChunkWords) * sizeof(uint32_t);
+}
+
+extern "C" int ovis_polygons_to_masks_u8(const float* coords, const int32_t* polygon_start, const int32_t* instance_start,
+                                         int num_instances, int num_polygons, int width, int height, void* workspace,
+                                         size_t workspace_bytes, uint8_t* out, void* stream) {
+  if (num_instances < 0 || num_polygons < 0 || width <= 0 || height <= 0) return OVIS_EINVAL;
+  if (num_instances == 0) return OVIS_OK;
+  if (!polygon_start || !instance_start || !out || (num_polygons > 0 && !workspace)) return OVIS_EINVAL;
+  if ((long)width * height > (1L << 30) || num_polygons > 65535 || num_instances > 65535) return OVIS_ERANGE;
+  if (((uintptr_t)workspace & 15) != 0) return OVIS_EINVAL;
+  if (workspace_bytes < ovis_polygons_to_masks_workspace_bytes(num_polygons, width, height)) return OVIS_ENOSPC;
+  hipStream_t s = (hipStream_t)stream;
+  const long words = polygon_words(width, height);
+  const int chunks = (int)(words / kChunkWords);
+  unsigned* bits = (unsigned*)workspace;
+  unsigned* chunk_parity = bits + (long)num_polygons * words;
+  if (num_polygons > 0) {
+    OVIS_HIP_TRY(hipMemsetAsync(bits, 0, sizeof(uint32_t) * (size_t)num_polygons * (size_t)words, s));
+    hipLaunchKernelGGL(polygon_toggle_kernel, dim3((unsigned)num_polygons, 8), dim3(256), 0, s, coords, polygon_start, width,
+                       height, words, bits);
+    OVIS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(polygon_chunk_parity_kernel, dim3((unsigned)chunks, (unsigned)num_polygons), dim3(kChunkThreads), 0, s, bits,
+                       chunks, words, chunk_parity);
+    OVIS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(polygon_fill_kernel, dim3((unsigned)chunks, (unsigned)num_polygons), dim3(kChunkThreads), 0, s, bits, chunks,
+                       words, chunk_parity);
+    OVIS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(polygon_expand_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)((height + 63) / 64), (unsigned)num_instances),
+                     dim3(256), 0, s, bits, instance_start, num_polygons, width, height, words, (unsigned char*)out);
   OVIS_LAUNCH_CHECK();
   return OVIS_OK;
 }

@@ -20,6 +20,7 @@
 //                  reference builds with Masker (mask_head/inference.py:100-160: pad by 1, expand the box, bilinear
 //                  resize to the integer box, > 0.5, paste) is evaluated on the fly, so the H x W canvases never exist.
 #include "ovis_common.h"
+#include "pasted_geom.h"
 
 namespace {
 __global__ __launch_bounds__(256) void match_encode_kernel(const float* __restrict__ gt, const long* __restrict__ gt_labels,
@@ -434,27 +435,8 @@ __global__ __launch_bounds__(kSampThreads) void sample_fg_bg_kernel(const long* 
 }
 
 // ---- mask targets from (probability map, box) pairs ---------------------------------------------------------------------
-// Pixel (Y, X) of the binary image mask Masker would paste for ground truth g (mask_head/inference.py:100-160 with
-// padding 1): the M x M map, zero-padded to (M+2)^2, is resized bilinearly (align_corners=False) to the integer box
-// obtained by expanding the box by (M+2)/M about its centre and truncating, thresholded, and pasted clipped to the image.
-__device__ __forceinline__ float pasted_pixel(const float* __restrict__ prob, int M, int4 bx, int bw, int bh, float thr,
-                                              int im_h, int im_w, int Y, int X) {
-  if (Y < 0 || X < 0 || Y >= im_h || X >= im_w || Y < bx.y || Y > bx.w || X < bx.x || X > bx.z) return 0.f;
-  const int S = M + 2;
-  // upsample_bilinear2d, align_corners=False: src = scale * (dst + 0.5) - 0.5 clamped at 0, scale = in / out
-  const float scale_y = (float)S / (float)bh, scale_x = (float)S / (float)bw;
-  const float sy = fmaxf(scale_y * ((float)(Y - bx.y) + 0.5f) - 0.5f, 0.f);
-  const float sx = fmaxf(scale_x * ((float)(X - bx.x) + 0.5f) - 0.5f, 0.f);
-  const int y0 = (int)sy, x0 = (int)sx;
-  const int y1 = y0 + (y0 < S - 1), x1 = x0 + (x0 < S - 1);
-  const float ly = sy - (float)y0, lx = sx - (float)x0;
-  auto at = [&](int y, int x) {  // the padded map: a zero border of one pixel
-    return (y >= 1 && y <= M && x >= 1 && x <= M) ? prob[(y - 1) * M + (x - 1)] : 0.f;
-  };
-  const float v = (1.f - ly) * ((1.f - lx) * at(y0, x0) + lx * at(y0, x1)) + ly * ((1.f - lx) * at(y1, x0) + lx * at(y1, x1));
-  return v > thr ? 1.f : 0.f;
-}
-
+// pasted_pixel() / pasted_box() (pasted_geom.h): pixel (Y, X) of the binary image mask Masker would paste for ground truth g
+// (mask_head/inference.py:100-160 with padding 1) and the integer box it is pasted into.
 __global__ __launch_bounds__(256) void project_pasted_masks_kernel(const float* __restrict__ probs,
                                                                   const float* __restrict__ gt_boxes,
                                                                   const long* __restrict__ gt_index,
@@ -481,11 +463,9 @@ __global__ __launch_bounds__(256) void project_pasted_masks_kernel(const float* 
   // the ground truth's pasted mask: integer box of the expanded pseudo box (Masker: scale (M+2)/M, truncation)
   const long g = gt_index[p];
   const float4 gb = *(const float4*)(gt_boxes + 4 * g);
-  const float scale = (float)(Mp + 2) / (float)Mp;
-  const float w_half = (gb.z - gb.x) * 0.5f * scale, h_half = (gb.w - gb.y) * 0.5f * scale;
-  const float x_c = (gb.z + gb.x) * 0.5f, y_c = (gb.w + gb.y) * 0.5f;
-  const int4 bx = make_int4((int)(x_c - w_half), (int)(y_c - h_half), (int)(x_c + w_half), (int)(y_c + h_half));
-  const int bw = max(bx.z - bx.x + 1, 1), bh = max(bx.w - bx.y + 1, 1);
+  const PastedBox pb = pasted_box(gb, Mp);
+  const int4 bx = pb.bx;
+  const int bw = pb.bw, bh = pb.bh;
   const float* pr = probs + g * Mp * Mp;
   const int Y0 = (int)(y0 + ymin), Y1 = (int)(y1 + ymin), X0 = (int)(x0 + xmin), X1 = (int)(x1 + xmin);
   const float v00 = pasted_pixel(pr, Mp, bx, bw, bh, thr, H, W, Y0, X0), v01 = pasted_pixel(pr, Mp, bx, bw, bh, thr, H, W, Y0, X1);

@@ -684,10 +684,20 @@ class Masker:
         self.threshold, self.padding = threshold, padding
 
     def __call__(self, masks, boxlist):
-        """masks [P,1,M,M], boxlist -> bool [P,1,H,W].  Same arithmetic per mask as ``paste_mask_in_image`` (the
+        """masks [P,1,M,M], boxlist -> bool [P,1,H,W] (mask_head/inference.py:124-205).  Device tensors: ONE launch of
+        ``_C.paste_masks`` for all masks -- no host read, no per-mask resize; host tensors: ``_loop``.  Same masks either
+        way (tests/test_device_masks_gpu.py: bit-equal on the device)."""
+        if masks.is_cuda and self.padding == 1:
+            im_w, im_h = boxlist.size
+            return _C.paste_masks(masks[:, 0].float(), boxlist.bbox.float(), (im_h, im_w), self.threshold)[:, None]
+        return self._loop(masks, boxlist)
+
+    def _loop(self, masks, boxlist):
+        """Same arithmetic per mask as ``paste_mask_in_image`` (the
         reference's loop, mask_head/inference.py:124-205), restructured for the device: the expanded integer boxes of ALL
         masks come back in one host read instead of one per mask, padding and the image-size canvas are one fill each,
-        and only the resize to the box size (a data-dependent shape) stays per mask."""
+        and only the resize to the box size (a data-dependent shape) stays per mask.  Runs on any device: the host route of
+        ``__call__`` and the baseline the one-launch paste is held equal to."""
         im_w, im_h = boxlist.size
         P = masks.shape[0]
         if P == 0:

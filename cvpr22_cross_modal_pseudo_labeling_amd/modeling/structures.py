@@ -126,7 +126,8 @@ class PolygonMasks:
     in floats) and ``instance_start`` int32 [G + 1] (polygon ranges of the G instances).  ``size`` = (width, height).
     Polygons with fewer than 3 vertices are dropped at construction, as ``PolygonInstance.__init__`` does.  The mask
     head's targets come from ``_C.project_polygon_masks`` (crop -> resize -> rasterise per positive, one launch);
-    ``convert_to_binarymask`` rasterises whole-image masks with the same kernel."""
+    ``convert_to_binarymask`` rasterises whole-image masks at any image size (``_C.polygons_to_masks`` on the device,
+    ``_cpu.polygons_to_masks`` on the host)."""
 
     def __init__(self, instances, size, _flat=None):
         self.size = tuple(size)
@@ -182,20 +183,10 @@ class PolygonMasks:
     def convert_to_binarymask(self):
         """uint8 [G, height, width]: every instance rasterised over the whole image (segmentation_mask.py:326-334)."""
         from .. import _C
-        w, h = self.size
-        g = len(self)
         if not self.coords.is_cuda:  # host polygons (dataset side, MODEL.DEVICE cpu): any image size, libovis_cpu.so
             from .. import _cpu
             return _cpu.polygons_to_masks(self.coords, self.polygon_start, self.instance_start, self.size)
-        if max(w, h) > 64:
-            raise NotImplementedError("whole-image rasterisation of DEVICE polygons is wired for maps up to 64 x 64 (the training "
-                                      "path rasterises per positive at the mask resolution); convert on the host: "
-                                      "``masks.to('cpu').convert_to_binarymask()``")
-        if w != h:
-            raise NotImplementedError("square maps only (crop + resize to M x M is the training path)")
-        boxes = torch.tensor([[0.0, 0.0, float(w), float(h)]], device=self.coords.device).expand(g, 4).contiguous()
-        idx = torch.arange(g, device=self.coords.device)
-        return _C.project_polygon_masks(self.coords, self.polygon_start, self.instance_start, idx, boxes, self.size, w).to(torch.uint8)
+        return _C.polygons_to_masks(self.coords, self.polygon_start, self.instance_start, self.size)
 
 
 def cat_boxlist(boxlists):  # boxlist_ops.py:107-129

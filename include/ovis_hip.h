@@ -506,6 +506,14 @@ int ovis_sample_fg_bg(const int64_t* labels, int num, int batch_size, int max_po
 int ovis_project_pasted_masks_f32(const float* mask_probs, const float* gt_boxes, const int64_t* gt_index,
                                   const float* boxes, int num, int image_height, int image_width, int prob_resolution,
                                   int resolution, float threshold, float* out, void* stream);
+/* ovis_paste_masks_u8: the image-size binary masks themselves -- Masker.forward_single_image / paste_mask_in_image
+ * (mb/modeling/roi_heads/mask_head/inference.py:100-205, padding 1) for ALL masks of an image in one launch, with the
+ * per-pixel arithmetic of ovis_project_pasted_masks_f32 (csrc/pasted_geom.h).  mask_probs [num, prob_resolution,
+ * prob_resolution] f32, boxes [num, 4] xyxy (16-byte aligned), out [num, image_height, image_width] uint8 in {0, 1}
+ * (the storage of a bool tensor); EVERY byte of out is written exactly once, so out needs no fill.  Enqueues only.
+ * prob_resolution <= 120, num <= 65535, image_height * image_width < 2^31, else OVIS_ERANGE. */
+int ovis_paste_masks_u8(const float* mask_probs, const float* boxes, int num, int prob_resolution, int image_height,
+                        int image_width, float threshold, uint8_t* out, void* stream);
 /* ovis_gather_rows: out[i] = src[index[i]] for up to two [P, 4] f32 arrays and two [P] int64 arrays at once (a NULL source
  * is skipped) -- the sampled proposals' boxes, regression targets, labels and matched ground truths
  * (mb/modeling/roi_heads/box_head/loss.py:112-121 indexes every field of the BoxList separately).  One launch. */
@@ -642,6 +650,18 @@ int ovis_text_embed_f32(const float* table, long table_rows, int dim, const int3
 int ovis_project_polygon_masks_f32(const float* coords, const int32_t* polygon_start, const int32_t* instance_start,
                                    const int64_t* gt_index, const float* boxes, int num, int image_width,
                                    int image_height, int resolution, float* out, void* stream);
+
+/* Whole-image masks of polygon instances: SegmentationMask(mode='poly').convert('mask') (mb/structures/
+ * segmentation_mask.py:326-334: frPyObjects -> merge -> decode at the image size, no crop / resize), the device twin of
+ * ovis_cpu_polygons_to_masks_u8 (include/ovis_cpu.h) with the polygon layout of ovis_project_polygon_masks_f32; any canvas
+ * with width * height <= 2^30.  num_polygons = entries of polygon_start - 1.  out [num_instances, height, width] uint8 in
+ * {0, 1}, every byte written.  workspace: ovis_polygons_to_masks_workspace_bytes(num_polygons, width, height) bytes,
+ * 16-byte aligned (one bit per position and polygon; may be NULL when num_polygons == 0); too small: OVIS_ENOSPC.
+ * Enqueues a memset and four kernels on `stream`; xor toggles and a parity scan, so the result is order independent. */
+size_t ovis_polygons_to_masks_workspace_bytes(int num_polygons, int width, int height);
+int ovis_polygons_to_masks_u8(const float* coords, const int32_t* polygon_start, const int32_t* instance_start,
+                              int num_instances, int num_polygons, int width, int height, void* workspace,
+                              size_t workspace_bytes, uint8_t* out, void* stream);
 
 /* Deformable convolution BACKWARD on NHWC rows (csrc/deform_conv_rows.hip; mb/csrc/cuda/deform_conv_cuda.cu:271-497,
  * 580-694): rows m = (image, h_out, w_out), k = (tap, channel), the layout of ovis_deform_conv_implicit_f32.

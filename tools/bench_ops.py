@@ -2,6 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
+Opt-in ops outside the default list: topk, paste, polygons (``--ops paste,polygons``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -254,6 +255,54 @@ def main():
                     "backward_ms": ms_fb_col - ms_col})
         res.append({"op": "deform_conv forward+backward (rows route)", "shape": "[2,512,100,168] 3x3 -> 512", "ms": ms_fb,
                     "backward_ms": ms_fb - ms, "backward_over_forward": (ms_fb - ms) / ms})
+    if "paste" in ops:  # opt-in: the evaluation pass's Masker paste, 100 detections of one 800 x 1333 image, M = 14
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.roi_heads import Masker
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import BoxList
+        p_, m_, h_, w_ = 100, 14, 800, 1333
+        probs = torch.rand(p_, m_, m_, generator=g).to(dev)
+        boxes = bench_rois(p_, 1, g, "rpn_like")[:, 1:].contiguous().to(dev)
+        masks, boxlist, masker = probs[:, None], BoxList(boxes, (w_, h_)), Masker(0.5, 1)
+        equal = torch.equal(_C.paste_masks(probs, boxes, (h_, w_)), masker._loop(masks, boxlist)[:, 0])
+        k_ms, l_ms = [], []
+        for _ in range(3):  # the two routes alternate inside this one call
+            k_ms.append(timeit(lambda: _C.paste_masks(probs, boxes, (h_, w_)), args.iters))
+            l_ms.append(timeit(lambda: masker._loop(masks, boxlist), max(3, args.iters // 4)))
+        ms, ms_loop, nbytes = sorted(k_ms)[1], sorted(l_ms)[1], p_ * h_ * w_
+        res.append({"op": "paste_masks (one launch)", "shape": "P=100 M=14 800x1333 rpn_like boxes", "ms": ms, "rounds_ms": [round(v, 4) for v in k_ms],
+                    "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6, "frac_hbm_write_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS,
+                    "masker_loop_ms": ms_loop, "masker_loop_rounds_ms": [round(v, 4) for v in l_ms], "loop_over_kernel": ms_loop / ms,
+                    "outputs_equal": equal})
+    if "polygons" in ops:  # opt-in: whole-image ground-truth masks, 20 instances of 30-200 vertices at 800 x 1333
+        import math
+        import time
+
+        from cvpr22_cross_modal_pseudo_labeling_amd import _cpu
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import PolygonMasks
+        g_, h_, w_ = 20, 800, 1333
+        inst = []
+        for k in torch.randint(30, 201, (g_,), generator=g).tolist():
+            cx, cy = float(torch.rand(1, generator=g)) * w_, float(torch.rand(1, generator=g)) * h_
+            rad = (torch.rand(k, generator=g) * 0.6 + 0.4) * (40 + 260 * float(torch.rand(1, generator=g)))
+            inst.append([[v for i in range(k) for v in (cx + float(rad[i]) * math.cos(2 * math.pi * i / k),
+                                                        cy + float(rad[i]) * math.sin(2 * math.pi * i / k))]])
+        pm = PolygonMasks(inst, (w_, h_))
+        pd = pm.to(dev)
+        host = torch.empty((g_, h_, w_), dtype=torch.uint8)
+
+        def on_host():
+            _cpu.load().ovis_cpu_polygons_to_masks_u8(pm.coords.data_ptr(), pm.polygon_start.data_ptr(), pm.instance_start.data_ptr(),
+                                                      g_, w_, h_, host.data_ptr(), 16)
+
+        ms = timeit(lambda: _C.polygons_to_masks(pd.coords, pd.polygon_start, pd.instance_start, pd.size), args.iters)
+        on_host()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            on_host()
+        ms_host = (time.perf_counter() - t0) / 3 * 1e3
+        equal = torch.equal(_C.polygons_to_masks(pd.coords, pd.polygon_start, pd.instance_start, pd.size).cpu(), host)
+        res.append({"op": "polygons_to_masks (memset + 4 kernels)", "shape": "G=20 x 30-200 vertices, 800x1333", "ms": ms,
+                    "out_MB": g_ * h_ * w_ / 1e6, "host_16_threads_ms": ms_host, "host_over_device": ms_host / ms,
+                    "outputs_equal": equal})
     for r_ in res:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r_.items()}))
 
