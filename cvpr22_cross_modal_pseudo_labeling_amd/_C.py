@@ -1260,6 +1260,31 @@ def polygons_to_masks(coords, polygon_start, instance_start, size):
     return out
 
 
+def transform_images(data, desc, mean, std, to_bgr255, pad_hw, max_in_hw=None):
+    """float32 [B, 3, pad_h, pad_w]: B raw RGB images resized (PIL bilinear, bit for bit), flipped, normalised and zero
+    padded (``ovis_transform_images_u8``; data/transforms/transforms.py:27-120, structures/image_list.py:29-70).  data uint8
+    [bytes]: the images HWC back to back; desc int32 [B, 7] = (byte offset, in_h, in_w, out_h, out_w, flip_h, flip_v); mean,
+    std: three python floats each; pad_hw = (pad_h, pad_w).  Device tensors: max_in_hw = (largest in_h, largest in_w) of
+    the batch -- the descriptors stay on the device, the caller that packed them knows it.  Two launches, every element of
+    the result written once, no host read.  Host tensors: ``libovis_cpu.so``, same bits."""
+    if not data.is_cuda:
+        return _cpu.transform_images(data, desc, mean, std, to_bgr255, pad_hw)
+    data, desc = _dev(data, "data", torch.uint8), _dev(desc, "desc", torch.int32)
+    if data.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 7 or max_in_hw is None:
+        raise RuntimeError("transform_images: expected data [bytes] uint8, desc [B,7] int32 and max_in_hw")
+    b, (pad_h, pad_w), (max_h, max_w) = desc.shape[0], (int(pad_hw[0]), int(pad_hw[1])), (int(max_in_hw[0]), int(max_in_hw[1]))
+    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    with _on(data.device):
+        nbytes = _L.ovis_transform_images_workspace_bytes(b, max_h, pad_w)
+        out = torch.empty((b, 3, pad_h, pad_w), dtype=torch.float32, device=data.device)
+        if b:
+            ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=data.device)
+            rc = _L.ovis_transform_images_u8(data.data_ptr(), data.numel(), desc.data_ptr(), b, max_h, max_w, m3, s3,
+                                             int(bool(to_bgr255)), pad_h, pad_w, ws.data_ptr(), nbytes, out.data_ptr(), _stream())
+            _lib.check(rc, "transform_images")
+    return out
+
+
 def weighted_ce_fwd_bwd(logits, labels, bg_weight, need_grad=True):
     """-> (loss scalar tensor, dlogits or None)"""
     if not logits.is_cuda:

@@ -21,6 +21,7 @@ SIGNATURES = {
     "ovis_cpu_nms_f32": (_i, [_vp, _vp, _i, _f, _vp]),
     "ovis_cpu_project_polygon_masks_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i]),
     "ovis_cpu_polygons_to_masks_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i]),
+    "ovis_cpu_transform_images_u8": (_i, [_vp, ctypes.c_long, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i]),
     "ovis_cpu_version": (ctypes.c_char_p, []),
 }
 _lib = None
@@ -50,6 +51,8 @@ def _host(t, name, dtype=torch.float32):
 
 
 def _check(rc, what):
+    if rc == -3:
+        raise RuntimeError(f"{what}: OVIS_ERANGE (problem size not supported by the kernel)")
     if rc < 0:
         raise RuntimeError(f"{what}: bad argument (a RoI's batch index outside the batch, or a null / negative size)")
 
@@ -174,6 +177,21 @@ def polygons_to_masks(coords, polygon_start, instance_start, image_size):
     if g:
         _check(load().ovis_cpu_polygons_to_masks_u8(coords.data_ptr() if coords.numel() else 0, polygon_start.data_ptr(),
                                                    instance_start.data_ptr(), g, w, h, out.data_ptr(), 0), "polygons_to_masks")
+    return out
+
+
+# ---- data/transforms/transforms.py:27-62,65-85,105-120 + structures/image_list.py:29-70 on packed uint8 images ---------------------
+def transform_images(data, desc, mean, std, to_bgr255, pad_hw):
+    """float32 [B, 3, pad_h, pad_w] from B packed RGB HWC uint8 images (``ovis_cpu_transform_images_u8``)."""
+    data, desc = _host(data, "data", torch.uint8), _host(desc, "desc", torch.int32)
+    if data.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 7:
+        raise RuntimeError("transform_images: expected data [bytes] uint8 and desc [B,7] int32")
+    b, (pad_h, pad_w) = desc.shape[0], (int(pad_hw[0]), int(pad_hw[1]))
+    out = torch.empty((b, 3, pad_h, pad_w), dtype=torch.float32)
+    if b:
+        m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+        _check(load().ovis_cpu_transform_images_u8(data.data_ptr(), data.numel(), desc.data_ptr(), b, m3, s3, int(bool(to_bgr255)),
+                                                   pad_h, pad_w, out.data_ptr(), 0), "transform_images")
     return out
 
 

@@ -88,6 +88,8 @@ SIGNATURES = {
     "ovis_project_polygon_masks_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ovis_polygons_to_masks_workspace_bytes": (_sz, [_i, _i, _i]),
     "ovis_polygons_to_masks_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "ovis_transform_images_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ovis_transform_images_u8": (_i, [_vp, _l, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "ovis_sgd_momentum_multi_f32": (_i, [_vp, _vp, _i, _f, _f, _f, _i, _vp]),
     "ovis_bottleneck_identity_backward_workspace_bytes": (_sz, [_l, _i, _i, _i, _i, _i, _i]),
     "ovis_bottleneck_identity_backward": (_i, [_vp, _l] * 7 + [_vp] * 3 + [_l, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_sz, _i, _vp, _vp]),

@@ -147,6 +147,8 @@ def get_defaults():
         "INPUT": {  # :54-76
             "MIN_SIZE_TRAIN": (800,), "MAX_SIZE_TRAIN": 1333, "MIN_SIZE_TEST": 800, "MAX_SIZE_TEST": 1333,
             "PIXEL_MEAN": [102.9801, 115.9465, 122.7717], "PIXEL_STD": [1.0, 1.0, 1.0], "TO_BGR255": True,
+            "BRIGHTNESS": 0.0, "CONTRAST": 0.0, "SATURATION": 0.0, "HUE": 0.0,
+            "HORIZONTAL_FLIP_PROB_TRAIN": 0.5, "VERTICAL_FLIP_PROB_TRAIN": 0.0,
         },
         "DATASETS": {"TRAIN": (), "TEST": (), "DATASET_CLASS": "COCODataset",
                      "DATASET_ARGS": {"LOAD_EMBEDDINGS": False, "EMB_KEY": "GloVE", "EMB_DIM": 300}},

@@ -18,6 +18,9 @@
 #include <omp.h>
 #endif
 
+#define OVIS_HD static inline
+#include "../resample_geom.h"
+
 namespace {
 
 struct AxisSample {  // one sampling coordinate along one axis
@@ -337,4 +340,69 @@ extern "C" int ovis_cpu_project_polygon_masks_f32(const float* coords, const int
   return OVIS_CPU_OK;
 }
 
-extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 3 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets; fp32, OpenMP)"; }
+// ---- the input transform: host twin of ovis_transform_images_u8 (csrc/image_transform.hip), the arithmetic of resample_geom.h --
+extern "C" int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch,
+                                            const float* mean, const float* std, int to_bgr255, int pad_h, int pad_w,
+                                            float* out, int threads) {
+  if (batch < 0 || pad_h <= 0 || pad_w <= 0 || data_bytes < 0) return OVIS_CPU_EINVAL;
+  if (batch == 0) return OVIS_CPU_OK;
+  if (!data || !desc || !mean || !std || !out) return OVIS_CPU_EINVAL;
+  if (pad_h > kResampleMaxDim || pad_w > kResampleMaxDim || batch > 65535) return OVIS_CPU_ERANGE;
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* d = desc + (long)b * kImageDescInts;
+    if (d[1] > kResampleMaxDim || d[2] > kResampleMaxDim) return OVIS_CPU_ERANGE;  // out_h, out_w <= pad_h, pad_w
+    if (!image_desc_valid(ImageDesc{d[0], d[1], d[2], d[3], d[4], d[5], d[6]}, data_bytes, kResampleMaxDim, kResampleMaxDim,
+                          pad_h, pad_w))
+      return OVIS_CPU_EINVAL;
+  }
+  const long plane = (long)pad_h * pad_w;
+  const int nt = thread_count(threads);
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* dd = desc + (long)b * kImageDescInts;
+    const ImageDesc d{dd[0], dd[1], dd[2], dd[3], dd[4], dd[5], dd[6]};
+    const uint8_t* src = data + d.offset;
+    // horizontal pass -> uint8 [in_h, out_w, 3]; skipped when the width does not change (Resample.c: need_horizontal)
+    std::vector<uint8_t> rows;
+    long stride = 3L * d.in_w;
+    if (d.out_w != d.in_w) {
+      rows.resize(3UL * d.in_h * d.out_w);
+      stride = 3L * d.out_w;
+      const ResampleAxis ax = resample_axis(d.in_w, d.out_w);
+#pragma omp parallel for schedule(static) num_threads(nt)
+      for (int x = 0; x < d.out_w; ++x) {  // a column's weights are the same in every row; the values do not depend on the order
+        for (int y = 0; y < d.in_h; ++y) {
+          const uint8_t* row = src + 3L * y * d.in_w;
+          int u[3];
+          resample_position([&](int i, int c) { return (int)row[3 * i + c]; }, ax, d.in_w, x, u);
+          for (int c = 0; c < 3; ++c) rows[y * stride + 3L * x + c] = (uint8_t)u[c];
+        }
+      }
+      src = rows.data();
+    }
+    const ResampleAxis ay = resample_axis(d.in_h, d.out_h);
+    float* o = out + (long)b * 3 * plane;
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (int Y = 0; Y < pad_h; ++Y) {
+      const int yy = d.flip_v ? d.out_h - 1 - Y : Y;
+      for (int X = 0; X < pad_w; ++X) {
+        float* px = o + (long)Y * pad_w + X;
+        if (Y >= d.out_h || X >= d.out_w) {
+          px[0] = px[plane] = px[2 * plane] = 0.f;
+          continue;
+        }
+        const int xx = d.flip_h ? d.out_w - 1 - X : X;
+        const uint8_t* col = src + 3L * xx;
+        int u[3];
+        if (d.out_h != d.in_h) {
+          resample_position([&](int i, int c) { return (int)col[i * stride + c]; }, ay, d.in_h, yy, u);
+        } else {
+          for (int c = 0; c < 3; ++c) u[c] = col[yy * stride + c];
+        }
+        for (int c = 0; c < 3; ++c) px[c * plane] = normalized_channel(u, c, to_bgr255, mean, std);
+      }
+    }
+  }
+  return OVIS_CPU_OK;
+}
+
+extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 4 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets, input transform; fp32, OpenMP)"; }

@@ -25,6 +25,8 @@ def _map(obj, fn):
         for k, v in obj.extra_fields.items():
             out.add_field(k, _map(v, fn))
         return out
+    if hasattr(obj, "polygon_start") and hasattr(obj, "instance_start"):  # PolygonMasks
+        return type(obj)(None, obj.size, (fn(obj.coords), fn(obj.polygon_start), fn(obj.instance_start)))
     return obj
 
 
@@ -43,14 +45,18 @@ def copy_stream(device):
 
 
 class DevicePrefetcher:
-    """Iterates ``source`` (host batches: tensors / BoxLists / nested lists, tuples, dicts of them) ``depth`` batches
+    """Iterates ``source`` (host batches: tensors / BoxLists / PolygonMasks / nested lists, tuples, dicts of them; a
+    ``PolygonMasks`` field is staged and rebuilt on the device like a BoxList, whether or not ``transform`` is given) ``depth`` batches
     ahead on a worker thread and yields the same structures on ``device``.  On a CPU device it is a plain look-ahead
-    queue.  Exceptions of the source are re-raised in the consumer."""
+    queue.  Exceptions of the source are re-raised in the consumer.  ``transform`` (optional) is applied to every staged
+    batch in the CONSUMER's thread, on its current stream, once that stream waits for the batch's copies -- the device half
+    of ``data/transforms.py`` turns the staged raw uint8 images into the padded float batch there."""
 
     _END = object()
 
-    def __init__(self, source, device, depth=2):
+    def __init__(self, source, device, depth=2, transform=None):
         self.device = torch.device(device)
+        self.transform = transform
         self.cuda = self.device.type == "cuda"
         if self.cuda and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -135,7 +141,7 @@ class DevicePrefetcher:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             _map(item, lambda t: (t.record_stream(cur), t)[1] if t.is_cuda else t)  # allocated on the copy stream
-        return item
+        return item if self.transform is None else self.transform(item)
 
     def close(self, timeout=10.0):
         """Stop the staging thread and wait for it: no copy is issued on the copy stream after this returns (the caller

@@ -91,6 +91,45 @@ class BoxList:
             return self[keep]
         return self
 
+    def _fields_follow(self, out, what, *args):
+        """Fields of a resized / flipped copy: per-box tensors (labels, ids) and strings are geometry-free and carried over,
+        as bounding_box.py:105-108 does; an object follows through its own ``resize`` / ``transpose``.  A dense [G, H, W]
+        mask tensor is tied to the old pixel grid and has neither: it raises instead of going stale."""
+        for k, v in self.extra_fields.items():
+            if torch.is_tensor(v):
+                if v.dim() == 3 and v.shape[0] == len(self) and tuple(v.shape[1:]) == (self.size[1], self.size[0]):
+                    raise NotImplementedError(f"BoxList.{what}: field '{k}' is a dense mask tensor; use PolygonMasks")
+            elif not isinstance(v, str):
+                if not hasattr(v, what):
+                    raise NotImplementedError(f"BoxList.{what}: field '{k}' ({type(v).__name__}) has no {what}()")
+                v = getattr(v, what)(*args)
+            out.add_field(k, v)
+        return out
+
+    def resize(self, size):
+        """A copy scaled to ``size`` = (width, height): bounding_box.py:91-127 (one ratio when both axes agree, else one
+        per axis)."""
+        size = tuple(int(s) for s in size)
+        ratios = tuple(float(s) / float(s_orig) for s, s_orig in zip(size, self.size))
+        if ratios[0] == ratios[1]:
+            scaled = self.bbox * ratios[0]
+        else:
+            xmin, ymin, xmax, ymax = self.bbox.split(1, dim=-1)
+            scaled = torch.cat((xmin * ratios[0], ymin * ratios[1], xmax * ratios[0], ymax * ratios[1]), dim=-1)
+        return self._fields_follow(BoxList(scaled, size), "resize", size)
+
+    def transpose(self, method):
+        """FLIP_LEFT_RIGHT (0): x -> width - x - 1; FLIP_TOP_BOTTOM (1): y -> height - y (bounding_box.py:129-166)."""
+        if method not in (0, 1):
+            raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
+        width, height = self.size
+        xmin, ymin, xmax, ymax = self.bbox.split(1, dim=-1)
+        if method == 0:
+            flipped = torch.cat((width - xmax - TO_REMOVE, ymin, width - xmin - TO_REMOVE, ymax), dim=-1)
+        else:
+            flipped = torch.cat((xmin, height - ymax, xmax, height - ymin), dim=-1)
+        return self._fields_follow(BoxList(flipped, self.size), "transpose", method)
+
     def __repr__(self):
         return f"BoxList(num_boxes={len(self)}, image_width={self.size[0]}, image_height={self.size[1]})"
 
@@ -179,6 +218,18 @@ class PolygonMasks:
         c = self.coords.clone()
         c[method::2] = self.size[method] - self.coords[method::2] - TO_REMOVE
         return PolygonMasks(None, self.size, (c, self.polygon_start, self.instance_start))
+
+    def resize(self, size):
+        """Polygons scaled to ``size`` = (width, height): segmentation_mask.py:301-324 (one ratio when both axes agree)."""
+        size = tuple(int(s) for s in size)
+        ratios = tuple(float(s) / float(s_orig) for s, s_orig in zip(size, self.size))
+        if ratios[0] == ratios[1]:
+            c = self.coords * ratios[0]
+        else:
+            c = self.coords.clone()
+            c[0::2] *= ratios[0]
+            c[1::2] *= ratios[1]
+        return PolygonMasks(None, size, (c, self.polygon_start, self.instance_start))
 
     def convert_to_binarymask(self):
         """uint8 [G, height, width]: every instance rasterised over the whole image (segmentation_mask.py:326-334)."""

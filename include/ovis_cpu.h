@@ -18,6 +18,7 @@ extern "C" {
 
 #define OVIS_CPU_OK 0
 #define OVIS_CPU_EINVAL (-1)
+#define OVIS_CPU_ERANGE (-3) /* problem size not supported; the value of OVIS_ERANGE (include/ovis_hip.h) */
 
 /* csrc/cpu/ROIAlign_cpu.cpp:114-219 (ROIAlignForward_cpu_kernel): out [R, C, PH, PW]; rois [R, 5] = (batch index, x1, y1, x2, y2)
  * in image pixels; sampling_ratio <= 0 = adaptive ceil(roi extent / bins).  Bit-identical to the reference kernel (same
@@ -51,6 +52,14 @@ int ovis_cpu_project_polygon_masks_f32(const float* coords, const int32_t* polyg
  * pycocotools frPyObjects -> merge -> decode at the image size).  out [num_instances, height, width] uint8 (1 inside). */
 int ovis_cpu_polygons_to_masks_u8(const float* coords, const int32_t* polygon_start, const int32_t* instance_start, int num_instances,
                                   int width, int height, uint8_t* out, int threads);
+
+/* The input transform on host tensors: twin of ovis_transform_images_u8 (include/ovis_hip.h, same layout of `data`, `desc`
+ * and `out`, same bits) -- Resize (PIL bilinear, two 8-bit passes), flips, ToTensor, Normalize and to_image_list's zero
+ * padding (mb/data/transforms/transforms.py:27-62,65-85,105-120; mb/structures/image_list.py:29-70).  A descriptor that
+ * leaves `data` or the canvas: OVIS_CPU_EINVAL.  pad_h, pad_w or an image dimension above 16384, or batch above 65535:
+ * OVIS_CPU_ERANGE, as the device entry answers. */
+int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch, const float* mean,
+                                 const float* std, int to_bgr255, int pad_h, int pad_w, float* out, int threads);
 
 const char* ovis_cpu_version(void);
 

@@ -663,6 +663,24 @@ int ovis_polygons_to_masks_u8(const float* coords, const int32_t* polygon_start,
                               int num_instances, int num_polygons, int width, int height, void* workspace,
                               size_t workspace_bytes, uint8_t* out, void* stream);
 
+/* The input transform: B raw RGB images -> the padded batch the step reads, what the reference does per image on the host
+ * (mb/data/transforms/transforms.py:27-62 Resize = PIL Image.resize(BILINEAR), :65-85 RandomHorizontalFlip / VerticalFlip,
+ * :105-120 ToTensor + Normalize; mb/structures/image_list.py:29-70 zero padding), bit for bit (csrc/resample_geom.h, shared
+ * with the host twin ovis_cpu_transform_images_u8).  data: `data_bytes` bytes holding the images HWC uint8 back to back;
+ * desc [batch, 7] int32 ON THE DEVICE = (byte offset, in_h, in_w, out_h, out_w, flip_h, flip_v) per image, never read back;
+ * mean[3], std[3] HOST arrays in output-channel order (INPUT.PIXEL_MEAN / PIXEL_STD); to_bgr255: channels reversed and
+ * left at 0..255, else RGB / 255.  out [batch, 3, pad_h, pad_w] f32: EVERY element is written exactly once, the zeros
+ * right of out_w and below out_h included, so out needs no fill.  max_in_h / max_in_w bound the descriptors' in_h /
+ * in_w (they size the first launch and the workspace); an image whose descriptor breaks a bound, the canvas or the byte
+ * buffer comes out as NaN and nothing outside the buffers is touched.  workspace:
+ * ovis_transform_images_workspace_bytes(batch, max_in_h, pad_w) bytes (the 8-bit image between PIL's two passes); too
+ * small: OVIS_ENOSPC.  Two launches whatever the batch, enqueue only.  Any of max_in_h, max_in_w, pad_h, pad_w above
+ * 16384 or batch above 65535: OVIS_ERANGE. */
+size_t ovis_transform_images_workspace_bytes(int batch, int max_in_h, int pad_w);
+int ovis_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch, int max_in_h,
+                             int max_in_w, const float* mean, const float* std, int to_bgr255, int pad_h, int pad_w,
+                             void* workspace, size_t workspace_bytes, float* out, void* stream);
+
 /* Deformable convolution BACKWARD on NHWC rows (csrc/deform_conv_rows.hip; mb/csrc/cuda/deform_conv_cuda.cu:271-497,
  * 580-694): rows m = (image, h_out, w_out), k = (tap, channel), the layout of ovis_deform_conv_implicit_f32.
  * ovis_deform_im2col_pair_rows_f32: the sampled (x mask) rows col[m, (t, c)] written ONCE, in pair layout (row stride

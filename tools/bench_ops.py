@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, polygons (``--ops paste,polygons``).
+Opt-in ops outside the default list: topk, paste, polygons, transform (``--ops paste,polygons,transform``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -303,6 +303,25 @@ def main():
         res.append({"op": "polygons_to_masks (memset + 4 kernels)", "shape": "G=20 x 30-200 vertices, 800x1333", "ms": ms,
                     "out_MB": g_ * h_ * w_ / 1e6, "host_16_threads_ms": ms_host, "host_over_device": ms_host / ms,
                     "outputs_equal": equal})
+    if "transform" in ops:  # opt-in: the input transform, 2 x (480 x 640 -> 800 x 1066), against its 16-thread host twin
+        import time
+
+        b_, ih, iw, oh, ow = 2, 480, 640, 800, 1066
+        data = torch.randint(0, 256, (b_ * ih * iw * 3,), dtype=torch.uint8, generator=g)
+        desc = torch.tensor([[i * ih * iw * 3, ih, iw, oh, ow, i % 2, 0] for i in range(b_)], dtype=torch.int32)
+        mean, std = (102.9801, 115.9465, 122.7717), (1.0, 1.0, 1.0)
+        dd, dc = data.to(dev), desc.to(dev)
+        ms = timeit(lambda: _C.transform_images(dd, dc, mean, std, True, (oh, ow), (ih, iw)), args.iters)
+        _C.transform_images(data, desc, mean, std, True, (oh, ow))
+        t0 = time.perf_counter()
+        for _ in range(3):
+            host = _C.transform_images(data, desc, mean, std, True, (oh, ow))
+        ms_host = (time.perf_counter() - t0) / 3 * 1e3
+        equal = torch.equal(_C.transform_images(dd, dc, mean, std, True, (oh, ow), (ih, iw)).cpu(), host)
+        nbytes = b_ * 3 * oh * ow * 4 + 2 * b_ * ih * ow * 3 + b_ * ih * iw * 3  # output + intermediate (written, read) + input
+        res.append({"op": "transform_images (2 launches)", "shape": "2 x (480x640 -> 800x1066) uint8 -> f32", "ms": ms,
+                    "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6, "frac_hbm_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS,
+                    "host_twin_ms": ms_host, "host_over_device": ms_host / ms, "outputs_equal": equal})
     for r_ in res:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r_.items()}))
 

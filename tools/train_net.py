@@ -29,14 +29,15 @@ import torch.distributed as dist  # noqa: E402
 
 from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (SyntheticBatches, calibrate_stem_bn, make_batch,  # noqa: E402
-                                                                       make_embeddings)
+from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (RawSyntheticBatches, SyntheticBatches,  # noqa: E402
+                                                                       calibrate_stem_bn, make_batch, make_embeddings)
+from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, solver, trainer  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
 
-def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False):
+def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False):
     device = torch.device(cfg.MODEL.DEVICE, local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
     model = build_detection_model(cfg).to(device)
     e_vocab, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
@@ -64,11 +65,16 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
 
     # host batches come from DATALOADER.NUM_WORKERS worker processes (the training process' interpreter lock is busy feeding
     # two HIP streams) and are staged through pinned memory on a copy stream, two batches ahead
-    loader = torch.utils.data.DataLoader(SyntheticBatches(ims_per_gpu, seed0=1234, rank=comm.get_rank()), batch_size=None,
+    # --raw-input: the workers hand over raw uint8 images at their own sizes with polygon ground truth and only decide the
+    # size and the flips (data/transforms.py); resize, flip, normalisation and padding run on the device behind the copy
+    transform = build_transforms(cfg, is_train=True) if raw_input else None
+    source = (RawSyntheticBatches(ims_per_gpu, transform, seed0=1234, rank=comm.get_rank()) if raw_input
+              else SyntheticBatches(ims_per_gpu, seed0=1234, rank=comm.get_rank()))
+    loader = torch.utils.data.DataLoader(source, batch_size=None,
                                          num_workers=cfg.DATALOADER.NUM_WORKERS,
                                          prefetch_factor=2 if cfg.DATALOADER.NUM_WORKERS > 0 else None,
                                          persistent_workers=cfg.DATALOADER.NUM_WORKERS > 0)
-    data = DevicePrefetcher(loader, device, depth=2)
+    data = DevicePrefetcher(loader, device, depth=2, transform=transform)
     if not cfg.MODEL.WEIGHT and not checkpointer.has_checkpoint():  # random init only: give the frozen BN usable statistics
         images, _ = make_batch(1, device=device, seed=7)
         calibrate_stem_bn(model, images)
@@ -90,6 +96,10 @@ def main():
                         help="do not write model_<iter>.pth / model_final.pth / last_checkpoint under OUTPUT_DIR and do not "
                              "resume from them (the reference always does both, tools/train_net.py:76-88)")
     parser.add_argument("--save-checkpoints", action="store_true", help="accepted for compatibility: saving is the default")
+    parser.add_argument("--raw-input", action="store_true",
+                        help="feed raw uint8 images at COCO-like sizes with polygon ground truth through the device input "
+                             "transform (INPUT.* resize / flip / normalise, DATALOADER.SIZE_DIVISIBILITY) instead of "
+                             "ready-made float32 800x1333 batches")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args()
 
@@ -120,7 +130,7 @@ def main():
     logging.getLogger("ovis.trainer").info("%d images per GPU and iteration (SOLVER.IMS_PER_BATCH %d / %d GPUs)", ims_per_gpu,
                                            cfg.SOLVER.IMS_PER_BATCH, num_gpus)
     train(cfg, args.local_rank, distributed, args.max_iter or cfg.SOLVER.MAX_ITER, ims_per_gpu,
-          save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints)
+          save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input)
     if distributed:
         dist.destroy_process_group()
 
