@@ -1,0 +1,99 @@
+"""Inference over the user's COCO-format files, with the command line of ``tools/test_net.py`` plus the catalog:
+
+    python -m torch.distributed.run --nproc-per-node N tools/infer_net.py --config-file CFG --dataset-catalog FILE
+        [--data-dir DIR] [--ckpt FILE] KEY VALUE ...
+
+One process per GPU; the weights come from ``--ckpt`` / ``MODEL.WEIGHT`` / the last checkpoint of OUTPUT_DIR
+(utils/checkpoint.py).  Every name of DATASETS.TEST is resolved through the catalog (data/catalog.py), read through the raw
+input path (data/build.py: loader workers decode and pack, the device makes the pixels), classified against the class
+embeddings of its own annotation file (maskrcnn_benchmark/engine/inference.py:124-131), gathered on rank 0 and saved as
+``<OUTPUT_DIR>/inference/<name>/predictions.pth``: a list of BoxLists in dataset-index order, at the transformed image
+sizes.  ``tools/test_net.py`` stays the synthetic-stream tool; the COCO / LVIS scoring of ``evaluate`` is outside this build.
+"""
+import argparse
+import logging
+import os
+import sys
+
+import torch
+import torch.distributed as dist
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.build import build_dataset, make_data_loader  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem_bn, make_batch, make_embeddings  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, inference  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
+
+
+def run_datasets(cfg, model, catalog, device, logger=None):
+    """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}."""
+    transform = build_transforms(cfg, is_train=False)
+    results = {}
+    for name in cfg.DATASETS.TEST:
+        dataset = build_dataset(cfg, name, catalog)
+        loader = make_data_loader(cfg, dataset, transform, False, comm.get_rank(), comm.get_world_size())
+        batches = DevicePrefetcher(loader, device, depth=2, transform=transform)
+        out = os.path.join(cfg.OUTPUT_DIR, "inference", name) if cfg.OUTPUT_DIR else None
+        try:  # the zero-shot heads classify against THIS dataset's class embeddings
+            results[name] = inference.inference(model, batches, name, device, out,
+                                                class_embeddings=getattr(dataset, "class_emb_mtx", None), logger=logger)
+        finally:
+            batches.close()
+    return results
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="MI355X-native detection inference over COCO-format files")
+    parser.add_argument("--config-file", default="", metavar="FILE", help="path to config file")
+    parser.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", 0)))
+    parser.add_argument("--ckpt", default=None, help="checkpoint to test instead of MODEL.WEIGHT / the last one of OUTPUT_DIR")
+    parser.add_argument("--dataset-catalog", required=True, metavar="FILE",
+                        help="JSON catalog {name: {img_dir, ann_file, ann_file_cap?, vocab_file?}} of the DATASETS.TEST names")
+    parser.add_argument("--data-dir", default="", help="where the catalog's relative paths are taken from")
+    parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
+    args = parser.parse_args(argv)
+
+    world = int(os.environ.get("WORLD_SIZE", 1))
+    cfg = get_defaults()
+    if args.config_file:
+        cfg.merge_from_file(args.config_file)
+    cfg.merge_from_list(args.opts or [])
+    cfg.freeze()
+    device = torch.device(cfg.MODEL.DEVICE, args.local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
+    if cfg.MODEL.DEVICE == "cuda":
+        torch.cuda.set_device(args.local_rank)
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group(backend="nccl" if cfg.MODEL.DEVICE == "cuda" else "gloo", init_method="env://")
+        comm.synchronize()
+    logging.basicConfig(level=logging.INFO if comm.get_rank() == 0 else logging.WARNING,
+                        format="%(asctime)s %(name)s %(levelname)s: %(message)s")
+    logger = logging.getLogger("ovis.inference")
+    logger.info("Using %d GPUs\n%s", world, args)
+
+    catalog = DatasetCatalog(args.dataset_catalog, args.data_dir)
+    model = build_detection_model(cfg).to(device)
+    checkpointer = DetectronCheckpointer(cfg, model, save_dir=cfg.OUTPUT_DIR)
+    weight = args.ckpt or cfg.MODEL.WEIGHT
+    extra = checkpointer.load(weight, use_latest=args.ckpt is None)
+    if not weight and not extra and not checkpointer.has_checkpoint():
+        images, _ = make_batch(1, device=device, seed=7)
+        calibrate_stem_bn(model, images)  # random init only: give the frozen BN usable statistics
+    _, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
+    model.set_class_embeddings(e_seen)  # stands until a dataset brings its own (DATASETS.DATASET_ARGS.LOAD_EMBEDDINGS)
+    for name, preds in run_datasets(cfg, model, catalog, device, logger).items():
+        if preds is not None:
+            logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+if __name__ == "__main__":
+    main()

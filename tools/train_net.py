@@ -3,8 +3,9 @@
     python -m torch.distributed.run --nproc-per-node N tools/train_net.py --config-file CFG [--skip-test] KEY VALUE ...
 
 One process per GPU (RCCL via torch.distributed, env:// rendezvous), config = defaults <- yaml <- trailing overrides,
-frozen before use.  There is no dataset access in this build, so the data stream is the synthetic COCO-shaped generator
-(cvpr22_cross_modal_pseudo_labeling_amd/data/synthetic.py).  MODEL.WEIGHT (a ``.pth`` in the reference's wire format),
+frozen before use.  Without ``--dataset-catalog`` the data stream is the synthetic COCO-shaped generator
+(cvpr22_cross_modal_pseudo_labeling_amd/data/synthetic.py); with it, DATASETS.TRAIN is read from the user's COCO-format
+files (data/catalog.py, data/datasets.py, data/build.py) through the raw input path.  MODEL.WEIGHT (a ``.pth`` in the reference's wire format),
 OUTPUT_DIR resume and SOLVER.CHECKPOINT_PERIOD behave as in the reference (utils/checkpoint.py: checkpoints are written and
 resumed from whenever OUTPUT_DIR is set; ``--no-checkpoints`` opts out); evaluation and
 TensorBoard are outside the hot-path scope.
@@ -28,19 +29,45 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.build import build_train_dataset, make_data_loader  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (RawSyntheticBatches, SyntheticBatches,  # noqa: E402
-                                                                       calibrate_stem_bn, make_batch, make_embeddings)
+from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (LVIS_VOCAB, RawSyntheticBatches,  # noqa: E402
+                                                                       SyntheticBatches, calibrate_stem_bn, make_batch,
+                                                                       make_embeddings)
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, solver, trainer  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
 
-def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False):
+def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter=0, max_iter=None, seed=0):
+    """-> (loader of host batches, the input transform or None).  ``dataset`` (``--dataset-catalog``): the reference's
+    batching over the user's files (data/build.py), counted from ``start_iter``, its size and flip draws seeded by ``seed``;
+    otherwise the endless synthetic streams."""
+    transform = build_transforms(cfg, is_train=True) if (raw_input or dataset is not None) else None
+    if dataset is not None:
+        return make_data_loader(cfg, dataset, transform, True, comm.get_rank(), comm.get_world_size(), start_iter=start_iter,
+                                seed=seed, max_iter=max_iter), transform
+    source = (RawSyntheticBatches(ims_per_gpu, transform, seed0=1234, rank=comm.get_rank()) if raw_input
+              else SyntheticBatches(ims_per_gpu, seed0=1234, rank=comm.get_rank()))
+    loader = torch.utils.data.DataLoader(source, batch_size=None,
+                                         num_workers=cfg.DATALOADER.NUM_WORKERS,
+                                         prefetch_factor=2 if cfg.DATALOADER.NUM_WORKERS > 0 else None,
+                                         persistent_workers=cfg.DATALOADER.NUM_WORKERS > 0)
+    return loader, transform
+
+
+def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False, dataset_catalog=None,
+          data_dir="", seed=0):
     device = torch.device(cfg.MODEL.DEVICE, local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
     model = build_detection_model(cfg).to(device)
-    e_vocab, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
+    dataset = build_train_dataset(cfg, DatasetCatalog(dataset_catalog, data_dir)) if dataset_catalog else None
+    # the caption-vocabulary matrix stays the seeded stand-in: as many rows as the dataset's vocabulary when that is larger
+    n_vocab = max(LVIS_VOCAB, len(dataset.parser.class_names) if getattr(dataset, "parser", None) else 0)
+    e_vocab, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device, n_vocab=n_vocab)
+    if dataset is not None and cfg.DATASETS.DATASET_ARGS.LOAD_EMBEDDINGS:
+        e_seen = dataset.class_emb_mtx.to(device)  # the class embeddings of the annotation file (datasets/coco.py:74-91)
     model.set_class_embeddings(e_seen)  # engine/trainer.py:85-90
     if hasattr(model, "set_caption_vocab"):
         model.set_caption_vocab(e_vocab)
@@ -67,13 +94,7 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
     # two HIP streams) and are staged through pinned memory on a copy stream, two batches ahead
     # --raw-input: the workers hand over raw uint8 images at their own sizes with polygon ground truth and only decide the
     # size and the flips (data/transforms.py); resize, flip, normalisation and padding run on the device behind the copy
-    transform = build_transforms(cfg, is_train=True) if raw_input else None
-    source = (RawSyntheticBatches(ims_per_gpu, transform, seed0=1234, rank=comm.get_rank()) if raw_input
-              else SyntheticBatches(ims_per_gpu, seed0=1234, rank=comm.get_rank()))
-    loader = torch.utils.data.DataLoader(source, batch_size=None,
-                                         num_workers=cfg.DATALOADER.NUM_WORKERS,
-                                         prefetch_factor=2 if cfg.DATALOADER.NUM_WORKERS > 0 else None,
-                                         persistent_workers=cfg.DATALOADER.NUM_WORKERS > 0)
+    loader, transform = make_data_source(cfg, ims_per_gpu, raw_input, dataset, start_iter, max_iter, seed)
     data = DevicePrefetcher(loader, device, depth=2, transform=transform)
     if not cfg.MODEL.WEIGHT and not checkpointer.has_checkpoint():  # random init only: give the frozen BN usable statistics
         images, _ = make_batch(1, device=device, seed=7)
@@ -100,6 +121,12 @@ def main():
                         help="feed raw uint8 images at COCO-like sizes with polygon ground truth through the device input "
                              "transform (INPUT.* resize / flip / normalise, DATALOADER.SIZE_DIVISIBILITY) instead of "
                              "ready-made float32 800x1333 batches")
+    parser.add_argument("--dataset-catalog", default=None, metavar="FILE",
+                        help="JSON catalog {name: {img_dir, ann_file, ann_file_cap?, vocab_file?}}: train on DATASETS.TRAIN read "
+                             "from these COCO-format files instead of the synthetic stream (implies --raw-input)")
+    parser.add_argument("--data-dir", default="", help="where the catalog's relative paths are taken from")
+    parser.add_argument("--seed", type=int, default=0,
+                        help="with --dataset-catalog: the run's seed of the input transform's random draws (sizes, flips)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args()
 
@@ -130,7 +157,8 @@ def main():
     logging.getLogger("ovis.trainer").info("%d images per GPU and iteration (SOLVER.IMS_PER_BATCH %d / %d GPUs)", ims_per_gpu,
                                            cfg.SOLVER.IMS_PER_BATCH, num_gpus)
     train(cfg, args.local_rank, distributed, args.max_iter or cfg.SOLVER.MAX_ITER, ims_per_gpu,
-          save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input)
+          save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input,
+          dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed)
     if distributed:
         dist.destroy_process_group()
 
