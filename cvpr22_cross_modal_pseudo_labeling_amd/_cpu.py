@@ -133,8 +133,9 @@ def weighted_ce_fwd_bwd(logits, labels, bg_weight, need_grad=True):
 
 def mask_bce_stochastic_fwd_bwd(mu, sigma, eps, pos_index, targets, channel, need_grad=True):
     """mask_head/loss.py:107-148 with the stochastic logits of roi_mask_predictors.py:52-63 (z = mu + eps * sigma):
-    mean binary cross entropy of the positives' selected channel -> (loss, d mu, d sigma)."""
-    z = mu if sigma is None else mu + eps * sigma
+    mean binary cross entropy of the positives' selected channel -> (loss, d mu, d sigma).  z = mu when either factor is
+    missing, like the device path: sigma without eps gets an all-zero d sigma."""
+    z = mu if (sigma is None or eps is None) else mu + eps * sigma
     sel = z[pos_index, channel]                                   # [Pp, M, M]
     npos = pos_index.numel()
     t = targets.reshape(sel.shape)
@@ -147,6 +148,7 @@ def mask_bce_stochastic_fwd_bwd(mu, sigma, eps, pos_index, targets, channel, nee
     dsigma = None
     if sigma is not None:
         dsigma = torch.zeros_like(sigma)
+    if sigma is not None and eps is not None:
         dsigma.index_put_((pos_index, torch.zeros_like(pos_index)), dsel * eps[pos_index, channel], accumulate=True)
     return loss, dmu, dsigma
 

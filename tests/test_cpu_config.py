@@ -148,6 +148,19 @@ def test_host_head_and_loss_entry_points_match_autograd_of_the_reference_formula
             assert torch.allclose(loss, want.detach(), rtol=1e-6)
             assert torch.allclose(dmu, m.grad, rtol=1e-5, atol=1e-8)
             assert (dsig is None) == (s is None) and (s is None or torch.allclose(dsig, sg.grad, rtol=1e-5, atol=1e-8))
+    # one factor missing: z = mu (and an all-zero d sigma for a sigma without eps), as the device path defines it
+    from tests import head_reference as R
+
+    upos, uchan = torch.tensor([11, 0, 7, 3]), torch.tensor([1, 0, 0, 1])
+    for s, e in ((sigma, None), (None, eps)):
+        for ch in (uchan, 1):
+            loss, dmu, dsig = _C.mask_bce_stochastic_fwd_bwd(mu, s, e, upos, tg[:4], ch)
+            want, want_dmu, want_dsig = R.mask_bce(mu.numpy(), None if s is None else s.numpy(), None if e is None else e.numpy(),
+                                                   upos.numpy(), ch.numpy() if torch.is_tensor(ch) else ch, tg[:4].numpy())
+            assert abs(loss.item() - want) <= 1e-6 * abs(want)
+            assert torch.allclose(dmu.double(), torch.from_numpy(want_dmu), rtol=1e-5, atol=1e-8)
+            assert (dsig is None) == (s is None) == (want_dsig is None)
+            assert s is None or (dsig.shape == s.shape and not dsig.any() and not want_dsig.any())
     a, b, bias = torch.randn(20, 64, generator=g), torch.randn(7, 64, generator=g), torch.randn(7, generator=g)
     assert torch.allclose(_C.gemm_nt(a, b, bias), F.linear(a, b, bias), rtol=1e-6, atol=1e-6)
     raw, prob, idx = _C.region_noun_align(a, b)

@@ -72,7 +72,7 @@ def test_mask_predictor_and_fused_loss_fixture(z):
                                    (1, 1, 1)])
 def test_gemm_and_linear_autograd_vs_torch(m, n, k):
     from cvpr22_cross_modal_pseudo_labeling_amd import _C
-    from cvpr22_cross_modal_pseudo_labeling_amd.layers import linear_mfma
+    from cvpr22_cross_modal_pseudo_labeling_amd.layers import cross_modal, linear_mfma
 
     g = torch.Generator().manual_seed(m * 7 + n)
     a, b, bias = torch.randn(m, k, generator=g), torch.randn(n, k, generator=g), torch.randn(n, generator=g)
@@ -81,15 +81,38 @@ def test_gemm_and_linear_autograd_vs_torch(m, n, k):
     tol = 2e-6 * (a.double().abs() @ b.double().abs().t() + bias.double().abs())  # fp32 round-off class bound
     assert bool(((got - want).abs() <= tol + 1e-30).all())
     # strided operands (the backward products) and autograd
-    ad, bd, biasd = a.cuda().requires_grad_(True), b.cuda().requires_grad_(True), bias.cuda().requires_grad_(True)
-    y = linear_mfma(ad, bd, biasd)
     gy = torch.randn(m, n, generator=g)
-    y.backward(gy.cuda())
     ar, br, biasr = a.double().requires_grad_(True), b.double().requires_grad_(True), bias.double().requires_grad_(True)
     (ar @ br.t() + biasr).backward(gy.double())
-    for got_g, want_g in ((ad.grad, ar.grad), (bd.grad, br.grad), (biasd.grad, biasr.grad)):
+    mags = (gy.double().abs() @ b.double().abs(), gy.double().abs().t() @ a.double().abs())
+
+    def grads(fn):
+        ad, bd, biasd = a.cuda().requires_grad_(True), b.cuda().requires_grad_(True), bias.cuda().requires_grad_(True)
+        fn(ad, bd, biasd).backward(gy.cuda())
+        return ad.grad, bd.grad, biasd.grad
+
+    def max_norm_check(got_g, want_g):
         scale = want_g.abs().max().item() + 1e-12
         assert (got_g.cpu().double() - want_g).abs().max().item() <= 1e-5 * scale * max(1.0, (m + n + k) ** 0.5 / 8)
+
+    # The fp32 GEMM's two backward layouts (dA = gy B: B read row-contiguous; dB = gy^T A: both operands row-contiguous),
+    # element-wise in the forward's round-off class: |dA - ref| <= 2e-6 |gy||B|, |dB - ref| <= 2e-6 |gy|^T|A|.
+    # ``linear_mfma`` sends K % 128 == 0, N >= 32 to the three-term bf16 split GEMM instead, whose class is 3e-5 (its own
+    # test below); there the fp32 GEMM's autograd node is held to 2e-6 directly and ``linear_mfma`` keeps its earlier bound
+    # (its dA at 1024x49x768 measures 3.2 x 2e-6 |gy||B| -- a contraction over 49 terms does not average the split's error --
+    # where the fp32 GEMM measures 0.17; the other split-routed gradients measure 0.47 .. 0.86, the fp32 ones at most 0.17).
+    pair = cross_modal._pair_ok(a.cuda(), b.cuda())
+    routes = [("linear_mfma", linear_mfma)] + ([("fp32 GEMM autograd", cross_modal._LinearMFMA.apply)] if pair else [])
+    for route, fn in routes:
+        da, db, dbias = grads(fn)
+        for name, got_g, want_g, mag in (("dA", da, ar.grad, mags[0]), ("dB", db, br.grad, mags[1])):
+            err = (got_g.cpu().double() - want_g).abs()
+            print(f"{route} {m}x{n}x{k} {name}: error / (2e-6 magnitude) = {(err / (2e-6 * mag + 1e-30)).max().item():.3f}")
+            if fn is linear_mfma and pair:
+                max_norm_check(got_g, want_g)
+            else:
+                assert bool((err <= 2e-6 * mag + 1e-30).all())
+        max_norm_check(dbias, biasr.grad)
 
 
 @pytest.mark.parametrize("m,n,k", [(1024, 776, 2048), (2000, 768, 2048), (1024, 1203, 768), (1024, 49, 768), (3, 776, 2048)])
