@@ -748,6 +748,46 @@ def paste_masks(probs, boxes, image_size, threshold=0.5):
     return out
 
 
+def render_instances(image, maps, boxes, colors, kinds=None, params=None, alpha=0.5, outline_colors=None, outline_thickness=2):
+    """uint8 [H, W, 3]: box outlines, filled masks and uncertainty heat layers composited onto ``image`` uint8 [H, W, 3]
+    (``ovis_render_instances_u8``; engine/inference.py:519-589 over the Masker paste).  Layer i is (maps[i] [M, M] f32,
+    boxes[i] xyxy, kinds[i], params[i], colors[i] [3] f32 in 0..255), applied in index order: kind 0 fills where the pasted
+    value exceeds params[i] (``p * (1 - alpha) + alpha * colour``), kind 1 blends by ``clamp(value * params[i], 0, 1)``
+    (params[i] = float32(0.2 / score)).  kinds: int32 [K], default all fill; params: a number or f32 [K], default 0.5.
+    outline_colors uint8 [K, 3] draws every box (our band rule, include/ovis_hip.h) before any layer.  One launch on the
+    device of ``image``; host tensors take the host twin (``libovis_cpu.so``), same bytes."""
+    k = maps.shape[0] if maps.dim() == 3 else -1
+    if image.dim() != 3 or image.shape[2] != 3 or image.dtype != torch.uint8:
+        raise RuntimeError("render_instances: expected image uint8 [H, W, 3]")
+    if k < 0 or maps.shape[1] != maps.shape[2] or tuple(boxes.shape) != (k, 4) or tuple(colors.shape) != (k, 3):
+        raise RuntimeError("render_instances: expected maps [K,M,M], boxes [K,4] and colors [K,3]")
+    dev = image.device
+    kinds = torch.zeros(k, dtype=torch.int32, device=dev) if kinds is None else kinds
+    if not torch.is_tensor(params):
+        params = torch.full((k,), 0.5 if params is None else float(params), dtype=torch.float32, device=dev)
+    if tuple(kinds.shape) != (k,) or tuple(params.shape) != (k,) or (outline_colors is not None and tuple(outline_colors.shape) != (k, 3)):
+        raise RuntimeError("render_instances: expected kinds [K], params [K] and outline_colors [K,3]")
+    if not image.is_cuda:
+        return _cpu.render_instances(
+            _cpu._host(image, "image", torch.uint8), _cpu._host(maps, "maps"), _cpu._host(boxes, "boxes"),
+            _cpu._host(colors, "colors"), _cpu._host(kinds, "kinds", torch.int32), _cpu._host(params, "params"), alpha,
+            None if outline_colors is None else _cpu._host(outline_colors, "outline_colors", torch.uint8), outline_thickness)
+    image = _dev(image, "image", torch.uint8)
+    maps, boxes, colors, params = _dev(maps, "maps"), _dev(boxes, "boxes"), _dev(colors, "colors"), _dev(params, "params")
+    kinds = _dev(kinds, "kinds", torch.int32)
+    if outline_colors is not None:
+        outline_colors = _dev(outline_colors, "outline_colors", torch.uint8)
+    out = torch.empty_like(image)
+    with _on(dev):
+        rc = _L.ovis_render_instances_u8(
+            image.data_ptr(), image.shape[0], image.shape[1], maps.data_ptr() if k else 0, boxes.data_ptr() if k else 0, k,
+            maps.shape[1] if k else 0, kinds.data_ptr() if k else 0, params.data_ptr() if k else 0,
+            colors.data_ptr() if k else 0, float(alpha), outline_colors.data_ptr() if (k and outline_colors is not None) else 0,
+            int(outline_thickness), out.data_ptr(), _stream())
+    _lib.check(rc, "render_instances")
+    return out
+
+
 def split_pair(x):
     """x [rows, cols] f32 (row-strided view ok, cols % 32 == 0) -> pair layout [rows, 2*cols] bf16: per 32 values
     [hi(32) | lo(32)].  See include/ovis_hip.h."""

@@ -22,6 +22,7 @@ SIGNATURES = {
     "ovis_cpu_project_polygon_masks_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i]),
     "ovis_cpu_polygons_to_masks_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i]),
     "ovis_cpu_transform_images_u8": (_i, [_vp, ctypes.c_long, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i]),
+    "ovis_cpu_render_instances_u8": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _i]),
     "ovis_cpu_version": (ctypes.c_char_p, []),
 }
 _lib = None
@@ -50,11 +51,11 @@ def _host(t, name, dtype=torch.float32):
     return t.contiguous()
 
 
-def _check(rc, what):
+def _check(rc, what, einval="bad argument (a RoI's batch index outside the batch, or a null / negative size)"):
     if rc == -3:
         raise RuntimeError(f"{what}: OVIS_ERANGE (problem size not supported by the kernel)")
     if rc < 0:
-        raise RuntimeError(f"{what}: bad argument (a RoI's batch index outside the batch, or a null / negative size)")
+        raise RuntimeError(f"{what}: {einval}")
 
 
 # ---- csrc/cpu/ROIAlign_cpu.cpp:114-219; the transpose has no host form in the reference (csrc/ROIAlign.h:44) ----------------
@@ -194,6 +195,20 @@ def transform_images(data, desc, mean, std, to_bgr255, pad_hw):
         m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
         _check(load().ovis_cpu_transform_images_u8(data.data_ptr(), data.numel(), desc.data_ptr(), b, m3, s3, int(bool(to_bgr255)),
                                                    pad_h, pad_w, out.data_ptr(), 0), "transform_images")
+    return out
+
+
+# ---- engine/inference.py:519-589 (overlay_boxes, overlay_filled_mask, overlay_uncertainty_mask) over the Masker paste ----------
+def render_instances(image, maps, boxes, colors, kinds, params, alpha, outline_colors, outline_thickness):
+    """uint8 [H, W, 3] (``ovis_cpu_render_instances_u8``); the operands as ``_C.render_instances`` prepared them."""
+    out = torch.empty_like(image)
+    k = maps.shape[0]
+    _check(load().ovis_cpu_render_instances_u8(
+        image.data_ptr(), image.shape[0], image.shape[1], maps.data_ptr() if k else 0, boxes.data_ptr() if k else 0, k,
+        maps.shape[1] if k else 0, kinds.data_ptr() if k else 0, params.data_ptr() if k else 0, colors.data_ptr() if k else 0,
+        float(alpha), outline_colors.data_ptr() if (k and outline_colors is not None) else 0, int(outline_thickness),
+        out.data_ptr(), 0), "render_instances",
+        "OVIS_EINVAL (a null or negative size, alpha outside [0, 1], an outline thickness below 1, or out overlapping image)")
     return out
 
 

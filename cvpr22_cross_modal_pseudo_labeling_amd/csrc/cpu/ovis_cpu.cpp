@@ -19,6 +19,8 @@
 #endif
 
 #define OVIS_HD static inline
+#include "../pasted_value.h"
+#include "../render_geom.h"
 #include "../resample_geom.h"
 
 namespace {
@@ -405,4 +407,70 @@ extern "C" int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes
   return OVIS_CPU_OK;
 }
 
-extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 4 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets, input transform; fp32, OpenMP)"; }
+// ---- the prediction compositor: host twin of ovis_render_instances_u8 (csrc/render.hip), the arithmetic of pasted_value.h and
+// render_geom.h.  The device kernel walks the pixels and, per pixel, the layers in order; here the layers are walked in
+// order and, per layer, the pixels of its clipped box -- the same sequence of updates for every pixel.
+extern "C" int ovis_cpu_render_instances_u8(const uint8_t* image, int height, int width, const float* maps, const float* boxes,
+                                            int num_layers, int map_resolution, const int32_t* kinds, const float* params,
+                                            const float* colors, float alpha, const uint8_t* outline_colors,
+                                            int outline_thickness, uint8_t* out, int threads) {
+  if (height <= 0 || width <= 0 || num_layers < 0 || !image || !out || !(alpha >= 0.f && alpha <= 1.f)) return OVIS_CPU_EINVAL;
+  if (num_layers > 0 && (map_resolution <= 0 || !maps || !boxes || !kinds || !params || !colors)) return OVIS_CPU_EINVAL;
+  if (num_layers > 0 && outline_colors && outline_thickness < 1) return OVIS_CPU_EINVAL;
+  if (height > kRenderMaxDim || width > kRenderMaxDim) return OVIS_CPU_ERANGE;
+  const long bytes = 3L * height * width;
+  if ((uintptr_t)image < (uintptr_t)out + bytes && (uintptr_t)out < (uintptr_t)image + bytes) return OVIS_CPU_EINVAL;
+  if (num_layers > 0 && map_resolution > 120) return OVIS_CPU_ERANGE;  // the device entry's LDS limit
+  if (num_layers > 0 && outline_colors && outline_thickness > kRenderMaxThickness) return OVIS_CPU_ERANGE;
+  std::memcpy(out, image, (size_t)bytes);
+  const int nt = thread_count(threads);
+  const int M = map_resolution, S = M + 2, W = width, H = height;
+  if (outline_colors) {
+    const int lo = outline_thickness / 2, hi = (outline_thickness + 1) / 2 - 1;
+    for (int i = 0; i < num_layers; ++i) {
+      const float* gb = boxes + 4L * i;
+      if (!render_box_sane(gb[0], gb[1], gb[2], gb[3])) continue;
+      const OutlineRect r = outline_rect(gb[0], gb[1], gb[2], gb[3]);
+      const long ya = std::max<long>((long)r.ya - lo, 0), yb = std::min<long>((long)r.yb + hi, H - 1);
+      const long xa = std::max<long>((long)r.xa - lo, 0), xb = std::min<long>((long)r.xb + hi, W - 1);
+      for (long Y = ya; Y <= yb; ++Y)
+        for (long X = xa; X <= xb; ++X)
+          if (outline_covers(r, lo, hi, (int)Y, (int)X)) std::memcpy(out + (Y * W + X) * 3, outline_colors + 3L * i, 3);
+    }
+  }
+  std::vector<float> padded((size_t)(num_layers > 0 ? S * S : 0));
+  const double a = (double)alpha;
+  for (int i = 0; i < num_layers; ++i) {
+    const int kind = kinds[i];
+    if (kind != kRenderFill && kind != kRenderHeat) continue;
+    const float* gb = boxes + 4L * i;
+    if (!render_box_sane(gb[0], gb[1], gb[2], gb[3])) continue;
+    const PastedRect r = pasted_rect(gb[0], gb[1], gb[2], gb[3], M);
+    const int cx0 = std::max(r.x0, 0), cx1 = std::min(r.x1, W - 1), cy0 = std::max(r.y0, 0), cy1 = std::min(r.y1, H - 1);
+    if (cx1 < cx0 || cy1 < cy0) continue;
+    std::fill(padded.begin(), padded.end(), 0.f);
+    for (int y = 0; y < M; ++y) std::memcpy(&padded[(size_t)(y + 1) * S + 1], maps + ((long)i * M + y) * M, sizeof(float) * M);
+    const float* pd = padded.data();
+    auto at = [&](int y, int x) { return pd[y * S + x]; };
+    const float param = params[i];
+    const float* col = colors + 3L * i;
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (int Y = cy0; Y <= cy1; ++Y) {
+      for (int X = cx0; X <= cx1; ++X) {
+        uint8_t* px = out + ((long)Y * W + X) * 3;
+        const float v = pasted_value(at, M, r.x0, r.y0, r.bw, r.bh, Y, X);
+        if (kind == kRenderFill) {
+          if (v > param)
+            for (int c = 0; c < 3; ++c) px[c] = (uint8_t)render_fill(px[c], col[c], a);
+        } else {
+          const float m = render_heat_weight(v, param);
+          if (m != 0.f)
+            for (int c = 0; c < 3; ++c) px[c] = (uint8_t)render_heat(px[c], m, col[c]);
+        }
+      }
+    }
+  }
+  return OVIS_CPU_OK;
+}
+
+extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 5 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets, input transform, prediction compositor; fp32, OpenMP)"; }

@@ -12,6 +12,7 @@
 // of 16 bytes that does not meet the integer box is zeros without any arithmetic; inside the box a pixel is
 // pasted_inside() of pasted_geom.h, the expressions of project_pasted_masks_kernel (csrc/targets.hip).
 #include "ovis_common.h"
+#define OVIS_HD __device__ __forceinline__
 #include "pasted_geom.h"
 
 namespace {

@@ -20,6 +20,7 @@
 //                  reference builds with Masker (mask_head/inference.py:100-160: pad by 1, expand the box, bilinear
 //                  resize to the integer box, > 0.5, paste) is evaluated on the fly, so the H x W canvases never exist.
 #include "ovis_common.h"
+#define OVIS_HD __device__ __forceinline__
 #include "pasted_geom.h"
 
 namespace {

@@ -61,11 +61,18 @@ class COCODataset(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.ids)
 
+    def _open(self, idx):
+        with Image.open(os.path.join(self.root, self.coco.imgs[self.ids[idx]]["file_name"])) as f:
+            return f.convert("RGB")
+
+    def original_image(self, idx):
+        """The decoded image of dataset index ``idx`` at its own size, before any transform: RGB uint8 [h, w, 3]."""
+        return np.array(self._open(idx))
+
     def _load(self, idx):
         """-> (image id, RGB uint8 [h, w, 3], the non-crowd annotations, the BoxList with labels and masks, unclipped)."""
         img_id = self.ids[idx]
-        with Image.open(os.path.join(self.root, self.coco.imgs[img_id]["file_name"])) as f:
-            img = f.convert("RGB")
+        img = self._open(idx)
         anno = [obj for obj in self.coco.anns(img_id) if obj["iscrowd"] == 0]
         boxes = torch.as_tensor([obj["bbox"] for obj in anno], dtype=torch.float32).reshape(-1, 4)  # guards against no boxes
         target = BoxList(boxes, img.size, mode="xywh")

@@ -61,6 +61,15 @@ int ovis_cpu_polygons_to_masks_u8(const float* coords, const int32_t* polygon_st
 int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch, const float* mean,
                                  const float* std, int to_bgr255, int pad_h, int pad_w, float* out, int threads);
 
+/* The prediction compositor on host tensors: twin of ovis_render_instances_u8 (include/ovis_hip.h: same arguments, same
+ * layer kinds, blends and outline rule, same bytes) -- overlay_boxes, overlay_filled_mask and overlay_uncertainty_mask
+ * (mb/engine/inference.py:519-589) over the Masker paste (mb/modeling/roi_heads/mask_head/inference.py:124-165).  `boxes`
+ * needs no alignment here; every other check answers as the device entry does. */
+int ovis_cpu_render_instances_u8(const uint8_t* image, int height, int width, const float* maps, const float* boxes,
+                                 int num_layers, int map_resolution, const int32_t* kinds, const float* params,
+                                 const float* colors, float alpha, const uint8_t* outline_colors, int outline_thickness,
+                                 uint8_t* out, int threads);
+
 const char* ovis_cpu_version(void);
 
 #ifdef __cplusplus

@@ -514,6 +514,35 @@ int ovis_project_pasted_masks_f32(const float* mask_probs, const float* gt_boxes
  * prob_resolution <= 120, num <= 65535, image_height * image_width < 2^31, else OVIS_ERANGE. */
 int ovis_paste_masks_u8(const float* mask_probs, const float* boxes, int num, int prob_resolution, int image_height,
                         int image_width, float threshold, uint8_t* out, void* stream);
+/* ovis_render_instances_u8: the prediction compositor -- overlay_boxes, overlay_filled_mask and overlay_uncertainty_mask
+ * (mb/engine/inference.py:519-540, :557-569, :571-589) over the Masker paste (mb/modeling/roi_heads/mask_head/
+ * inference.py:124-165, padding 1; thresholded for fills, un-thresholded :150-155 for heat) in ONE launch, without building
+ * a [num_layers, height, width] mask: every byte of out is written once, a pixel evaluates only the layers whose integer
+ * pasted box covers it.  image, out: uint8 [height, width, 3] (HWC); out must not overlap image (OVIS_EINVAL).
+ *
+ * Layer i = (maps[i] [M, M] f32, boxes[i] xyxy f32 (the array 16-byte aligned), kinds[i], params[i], colors[i] [3] f32 in
+ * 0..255).  The layers are applied to a pixel in INDEX order, the pixel truncated to uint8 after each (the reference
+ * assigns into a uint8 array layer by layer).  v = the pasted value at the pixel (csrc/pasted_value.h: the bilinear value
+ * of the zero-padded map resized to the integer pasted box; zero outside that box and outside the image):
+ * A layer touches ONLY the pixels of its integer pasted box clipped to the image -- a fill with a negative params[i] does
+ * not spill over the rest of the image, where v is zero.  Inside that box:
+ *   kinds[i] == 0, fill:  where v > params[i]:  p <- (uint8) trunc(p * (1 - alpha) + alpha * colors[i][c]) in DOUBLE
+ *                         (NumPy's `uint8 * 0.5 + 0.5 * c`; in float32 the sum can round across an integer)
+ *   kinds[i] == 1, heat:  m = min(max(v * params[i], 0), 1), params[i] = float32(0.2 / score);  where m != 0:
+ *                         p <- (uint8) trunc((float) p * (1 - m) + m * colors[i][c]) in FLOAT32, one rounding per operation
+ *                         (NumPy's `uint8 * float32`)
+ *   any other kind: the layer is skipped.  A box with a coordinate that is NaN or beyond +-1e6 has neither layer nor outline.
+ * Outlines (outline_colors [num_layers, 3] uint8, NULL = none) are ALL drawn before any layer, in index order.  THE RULE,
+ * ours (cv2's coverage of a thick rectangle is not reproduced): the box corners are truncated toward zero and ordered
+ * (xa <= xb, ya <= yb); with thickness t an edge at integer coordinate c covers c - floor(t/2) ... c + ceil(t/2) - 1 across
+ * its direction, and runs along its direction from the low end of the first corner's band to the high end of the second's
+ * (filled square corners); clipped to the image.
+ * num_layers == 0 copies the image.  0 <= alpha <= 1, outline_thickness >= 1 (when outlines are drawn), else OVIS_EINVAL;
+ * map_resolution <= 120, height, width <= 65535, outline_thickness <= 255, else OVIS_ERANGE.  Enqueues only. */
+int ovis_render_instances_u8(const uint8_t* image, int height, int width, const float* maps, const float* boxes,
+                             int num_layers, int map_resolution, const int32_t* kinds, const float* params,
+                             const float* colors, float alpha, const uint8_t* outline_colors, int outline_thickness,
+                             uint8_t* out, void* stream);
 /* ovis_gather_rows: out[i] = src[index[i]] for up to two [P, 4] f32 arrays and two [P] int64 arrays at once (a NULL source
  * is skipped) -- the sampled proposals' boxes, regression targets, labels and matched ground truths
  * (mb/modeling/roi_heads/box_head/loss.py:112-121 indexes every field of the BoxList separately).  One launch. */

@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, polygons, transform (``--ops paste,polygons,transform``).
+Opt-in ops outside the default list: topk, paste, polygons, transform, render (``--ops paste,polygons,transform,render``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -322,6 +322,37 @@ def main():
         res.append({"op": "transform_images (2 launches)", "shape": "2 x (480x640 -> 800x1066) uint8 -> f32", "ms": ms,
                     "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6, "frac_hbm_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS,
                     "host_twin_ms": ms_host, "host_over_device": ms_host / ms, "outputs_equal": equal})
+    if "render" in ops:  # opt-in: the prediction compositor, 100 fill layers on one 480 x 640 image, M = 14
+        k_, m_, h_, w_ = 100, 14, 480, 640
+        probs = torch.rand(k_, m_, m_, generator=g).to(dev)
+        boxes = (bench_rois(k_, 1, g, "rpn_like")[:, 1:] * (w_ / 1333.0)).contiguous().to(dev)  # the 800 x 1333 boxes at this size
+        colors = torch.randint(0, 256, (k_, 3), generator=g).float().to(dev)
+        image = torch.randint(0, 256, (h_, w_, 3), dtype=torch.uint8, generator=g).to(dev)
+
+        def over_paste_masks():  # what the library offered before: [K, H, W] masks, then K blending passes in torch
+            masks = _C.paste_masks(probs, boxes, (h_, w_))
+            img = image
+            for i in range(k_):
+                blended = (img.double() * (1.0 - 0.5) + 0.5 * colors[i].double()).to(torch.uint8)
+                img = torch.where(masks[i][:, :, None], blended, img)
+            return img
+
+        equal = torch.equal(_C.render_instances(image, probs, boxes, colors), over_paste_masks())
+        k_ms, t_ms = [], []
+        for _ in range(3):  # the two routes alternate inside this one call
+            k_ms.append(timeit(lambda: _C.render_instances(image, probs, boxes, colors), args.iters))
+            t_ms.append(timeit(over_paste_masks, max(3, args.iters // 4)))
+        ms, ms_torch = sorted(k_ms)[1], sorted(t_ms)[1]
+        px = h_ * w_
+        nbytes = 2 * 3 * px + 4 * k_ * (m_ * m_ + 4 + 3 + 2)       # image in, picture out, the layers' maps / boxes / colours / kind / param
+        # counted, not measured: the masks written once (K px); per layer and pixel-channel img.double() (1 + 8), the product
+        # (8 + 8), the sum (8 + 8), .to(uint8) (8 + 1), where() (1 + 1 + 1 out) = 53 bytes, plus the mask byte where() reads
+        nbytes_torch = k_ * px + k_ * px * (3 * 53 + 1)
+        res.append({"op": "render_instances (one launch)", "shape": "K=100 fill layers M=14 480x640 rpn_like boxes", "ms": ms,
+                    "rounds_ms": [round(v, 4) for v in k_ms], "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6,
+                    "paste_masks_plus_torch_ms": ms_torch, "paste_masks_plus_torch_rounds_ms": [round(v, 4) for v in t_ms],
+                    "paste_masks_plus_torch_bytes_MB": nbytes_torch / 1e6, "mask_bytes_MB": k_ * px / 1e6,
+                    "torch_over_kernel": ms_torch / ms, "outputs_equal": equal})
     for r_ in res:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r_.items()}))
 

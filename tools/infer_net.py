@@ -8,7 +8,10 @@ One process per GPU; the weights come from ``--ckpt`` / ``MODEL.WEIGHT`` / the l
 input path (data/build.py: loader workers decode and pack, the device makes the pixels), classified against the class
 embeddings of its own annotation file (maskrcnn_benchmark/engine/inference.py:124-131), gathered on rank 0 and saved as
 ``<OUTPUT_DIR>/inference/<name>/predictions.pth``: a list of BoxLists in dataset-index order, at the transformed image
-sizes.  ``tools/test_net.py`` stays the synthetic-stream tool; the COCO / LVIS scoring of ``evaluate`` is outside this build.
+sizes.  ``--visualize N`` (rank 0) also renders the first N images of every test set -- boxes, filled masks, class names
+(engine/visualize.py; detections scoring above ``--vis-threshold``) on the dataset's own decoded image -- to
+``<OUTPUT_DIR>/inference/<name>/vis/<file stem>.png``.  ``tools/test_net.py`` stays the synthetic-stream tool; the COCO /
+LVIS scoring of ``evaluate`` is outside this build.
 """
 import argparse
 import logging
@@ -27,12 +30,26 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  
 from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem_bn, make_batch, make_embeddings  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, inference  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, inference, visualize  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
 
-def run_datasets(cfg, model, catalog, device, logger=None):
+def save_visualizations(dataset, predictions, folder, count, threshold, device):
+    """The first ``count`` images of ``dataset`` with their detections drawn (engine/visualize.py) -> ``folder``/<stem>.png."""
+    from PIL import Image
+
+    os.makedirs(folder, exist_ok=True)
+    unseen = [dataset.json_category_id_to_contiguous_id[c] for c in dataset.class_splits.get("unseen", [])]
+    for idx in range(min(count, len(predictions), len(dataset))):
+        image = dataset.original_image(idx)  # RGB, at its own size, before any transform
+        picture = visualize.render_predictions(image, predictions[idx].to(device), dataset.class_names, threshold=threshold,
+                                               unseen_labels=unseen)
+        stem = os.path.splitext(os.path.basename(dataset.get_img_info(idx)["file_name"]))[0]
+        Image.fromarray(picture).save(os.path.join(folder, stem + ".png"))
+
+
+def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5):
     """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}."""
     transform = build_transforms(cfg, is_train=False)
     results = {}
@@ -46,6 +63,8 @@ def run_datasets(cfg, model, catalog, device, logger=None):
                                                 class_embeddings=getattr(dataset, "class_emb_mtx", None), logger=logger)
         finally:
             batches.close()
+        if visualize_count > 0 and out and results[name] is not None:  # rank 0 only: the others got None
+            save_visualizations(dataset, results[name], os.path.join(out, "vis"), visualize_count, vis_threshold, device)
     return results
 
 
@@ -57,6 +76,9 @@ def main(argv=None):
     parser.add_argument("--dataset-catalog", required=True, metavar="FILE",
                         help="JSON catalog {name: {img_dir, ann_file, ann_file_cap?, vocab_file?}} of the DATASETS.TEST names")
     parser.add_argument("--data-dir", default="", help="where the catalog's relative paths are taken from")
+    parser.add_argument("--visualize", type=int, default=0, metavar="N",
+                        help="render the first N images of every test set to OUTPUT_DIR/inference/<name>/vis/ (rank 0)")
+    parser.add_argument("--vis-threshold", type=float, default=0.5, metavar="T", help="draw detections scoring above T")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args(argv)
 
@@ -66,6 +88,8 @@ def main(argv=None):
         cfg.merge_from_file(args.config_file)
     cfg.merge_from_list(args.opts or [])
     cfg.freeze()
+    if args.visualize > 0 and not cfg.OUTPUT_DIR:
+        parser.error("--visualize writes under OUTPUT_DIR/inference/<name>/vis/: set OUTPUT_DIR")
     device = torch.device(cfg.MODEL.DEVICE, args.local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
@@ -88,7 +112,7 @@ def main(argv=None):
         calibrate_stem_bn(model, images)  # random init only: give the frozen BN usable statistics
     _, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
     model.set_class_embeddings(e_seen)  # stands until a dataset brings its own (DATASETS.DATASET_ARGS.LOAD_EMBEDDINGS)
-    for name, preds in run_datasets(cfg, model, catalog, device, logger).items():
+    for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold).items():
         if preds is not None:
             logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:
