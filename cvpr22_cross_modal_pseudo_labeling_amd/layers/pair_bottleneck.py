@@ -15,11 +15,41 @@ NHWC rows [R*H*W, C], every convolution an fp32-accurate three-term bf16 hi/lo p
   kernel (``split_gemm_pair_tn``; the 3x3 reads its input shifted per tap, so no im2col rows exist in training either).
 Saved per row: the pair forms of the input and of the two inner activations + the fp32 output.
 """
+from collections import namedtuple
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _C
+
+
+class PairWeights(namedtuple("PairWeights", "w1 w2 w3 wd w3d wts")):
+    """Pair-layout operands of one bottleneck: the forward matrices of conv1, conv2, conv3 and the projection shortcut
+    (``wd`` None = identity shortcut), ``w3d`` = [w3 | wd] side by side (the operand of the fused conv3 + shortcut product;
+    None for an identity block) and ``wts`` = the four transposed forms the data gradients read (the fourth None for an
+    identity block), or None when they were not prepared (the backward then prepares them itself)."""
+    __slots__ = ()
+
+    @classmethod
+    def prepare(cls, w1, s1, w2, s2, w3, s3, wd, sd, transposed):
+        """From RAW weights and their FrozenBN scales: fold + matrix form + split (+ transposed form), one launch per weight."""
+        p1, t1 = _C.weight_prep_pair(w1, s1, transposed)
+        p2, t2 = _C.weight_prep_pair(w2, s2, transposed)
+        p3, t3 = _C.weight_prep_pair(w3, s3, transposed)
+        pd, td = _C.weight_prep_pair(wd, sd, transposed) if wd is not None else (None, None)
+        # conv3 and the projection shortcut as ONE product (pair rows concatenate block-wise)
+        w3d = torch.cat([p3, pd], 1) if wd is not None else None
+        return cls(p1, p2, p3, pd, w3d, (t1, t2, t3, td) if transposed else None)
+
+
+# Pair-layout operands of a lone convolution (``conv_same_pair``): forward matrix and transposed form (or None).
+ConvWeights = namedtuple("ConvWeights", "w wt")
+
+# What one bottleneck hands on: ``out`` the fp32 result (a NaN placeholder when it exists in pair layout only), ``pair`` its pair
+# form or None, ``pooled`` its mean over every map ([R, C]) or None, ``selected`` = (select, the [S, h*w, C] rows of those maps)
+# or None.  ``pooled`` and ``selected`` are outputs of the block's own autograd node.
+BlockResult = namedtuple("BlockResult", "out pair pooled selected", defaults=(None, None, None))
 
 
 def pair_weight(w2d):
@@ -89,9 +119,9 @@ class WeightPrepPlan:
     [(key, [(w, scale)])] for a lone convolution (``conv_same_pair``: the RPN head's 3x3); the conv3
     and downsample forward matrices of a projection block are written side by side into ONE [N, 2 (K3 + Kd)] matrix (the
     operand of the fused conv3 + shortcut product).  ``run()`` after every optimizer step; ``lookup(key, scales)`` hands a
-    block its ``wpairs`` dict while nothing has touched its weights since (``_WEIGHTS_EPOCH`` for raw-pointer writers, the
-    tensors' version counters for everything else, identity of the FrozenBN scale tensors) -- else None, and the block
-    prepares its weights itself as before."""
+    block its ``PairWeights`` (a lone convolution its ``ConvWeights``) while nothing has touched its weights since
+    (``_WEIGHTS_EPOCH`` for raw-pointer writers, the tensors' version counters for everything else, identity of the FrozenBN
+    scale tensors) -- else None, and the block prepares its weights itself as before."""
 
     def __init__(self, blocks):
         import numpy as np
@@ -100,48 +130,40 @@ class WeightPrepPlan:
         self.entries = {}
         rows, blk = [], []
         dev = blocks[0][1][0][0].device
+
+        def item(w, sc, fbuf, fptr):
+            """Table row + tiles of one convolution (forward form at fptr inside fbuf); returns its transposed buffer."""
+            n, c, t = w.shape[0], w.shape[1], w.shape[2] * w.shape[3]
+            tb = torch.empty((c, 2 * t * n), dtype=torch.bfloat16, device=dev)
+            if sc is not None and not (sc.is_cuda and sc.dtype == torch.float32 and sc.is_contiguous() and sc.numel() == n):
+                raise RuntimeError("WeightPrepPlan: scale must be a contiguous float32 [N] HIP tensor")
+            self.max_taps = max(self.max_taps, t)
+            rows.append((w.data_ptr(), 0 if sc is None else sc.data_ptr(), fptr, tb.data_ptr(), 2 * fbuf.stride(0),
+                         2 * tb.stride(0), n | (c << 32), t))
+            blk.extend((len(rows) - 1, ti) for ti in range((n // tile) * (c // tile)))
+            return tb
+
         for key, convs in blocks:
             ws = [w for w, _ in convs]
             if not all(w.is_cuda and w.dtype == torch.float32 and w.dim() == 4 and w.is_contiguous() and w.device == dev
                        and w.shape[0] % 32 == 0 and w.shape[1] % 32 == 0 for w in ws):
                 raise RuntimeError("WeightPrepPlan: contiguous float32 HIP weights with channel counts divisible by 32 expected")
-            if len(convs) == 1:  # a lone convolution (the RPN head's 3x3): {"w": forward form, "wt": transposed form}
+            if len(convs) == 1:  # a lone convolution (the RPN head's 3x3)
                 (w, sc), = convs
-                n, c, t = w.shape[0], w.shape[1], w.shape[2] * w.shape[3]
-                f = torch.empty((n, 2 * t * c), dtype=torch.bfloat16, device=dev)
-                tb = torch.empty((c, 2 * t * n), dtype=torch.bfloat16, device=dev)
-                if sc is not None and not (sc.is_cuda and sc.dtype == torch.float32 and sc.is_contiguous() and sc.numel() == n):
-                    raise RuntimeError("WeightPrepPlan: scale must be a contiguous float32 [N] HIP tensor")
-                self.max_taps = max(self.max_taps, t)
-                rows.append((w.data_ptr(), 0 if sc is None else sc.data_ptr(), f.data_ptr(), tb.data_ptr(), 2 * f.stride(0),
-                             2 * tb.stride(0), n | (c << 32), t))
-                blk.extend((len(rows) - 1, ti) for ti in range((n // tile) * (c // tile)))
-                self.entries[key] = [{"w": f, "wt": tb}, (w,), (sc,), None]
-                continue
-            (w1, _), (w2, _), (w3, _) = convs[:3]
-            wd = convs[3][0] if len(convs) > 3 else None
-            k3 = w3.shape[1] * w3.shape[2] * w3.shape[3]
-            kd = wd.shape[1] * wd.shape[2] * wd.shape[3] if wd is not None else 0
-            f1 = torch.empty((w1.shape[0], 2 * w1[0].numel()), dtype=torch.bfloat16, device=dev)
-            f2 = torch.empty((w2.shape[0], 2 * w2[0].numel()), dtype=torch.bfloat16, device=dev)
-            f3d = torch.empty((w3.shape[0], 2 * (k3 + kd)), dtype=torch.bfloat16, device=dev)
-            fwd = [(f1, f1.data_ptr()), (f2, f2.data_ptr()), (f3d, f3d.data_ptr())] + ([(f3d, f3d.data_ptr() + 4 * k3)] if wd is not None else [])
-            bwd = []
-            for (w, sc), (fbuf, fptr) in zip(convs, fwd):
-                n, c, t = w.shape[0], w.shape[1], w.shape[2] * w.shape[3]
-                tb = torch.empty((c, 2 * t * n), dtype=torch.bfloat16, device=dev)
-                bwd.append(tb)
-                if sc is not None and not (sc.is_cuda and sc.dtype == torch.float32 and sc.is_contiguous() and sc.numel() == n):
-                    raise RuntimeError("WeightPrepPlan: scale must be a contiguous float32 [N] HIP tensor")
-                self.max_taps = max(self.max_taps, t)
-                rows.append((w.data_ptr(), 0 if sc is None else sc.data_ptr(), fptr, tb.data_ptr(), 2 * fbuf.stride(0),
-                             2 * tb.stride(0), n | (c << 32), t))
-                blk.extend((len(rows) - 1, ti) for ti in range((n // tile) * (c // tile)))
-            wp = {"w1": f1, "w2": f2, "w3": f3d[:, :2 * k3], "wd": f3d[:, 2 * k3:] if wd is not None else None,
-                  "wts": tuple(bwd) + ((None,) if wd is None else ())}
-            if wd is not None:
-                wp["w3d"] = f3d
-            self.entries[key] = [wp, tuple(w for w, _ in convs), tuple(sc for _, sc in convs), None]
+                f = torch.empty((w.shape[0], 2 * w[0].numel()), dtype=torch.bfloat16, device=dev)
+                weights = ConvWeights(f, item(w, sc, f, f.data_ptr()))
+            else:
+                w1, w2, w3, wd = (ws + [None])[:4]
+                k3, kd = w3[0].numel(), (wd[0].numel() if wd is not None else 0)
+                f1 = torch.empty((w1.shape[0], 2 * w1[0].numel()), dtype=torch.bfloat16, device=dev)
+                f2 = torch.empty((w2.shape[0], 2 * w2[0].numel()), dtype=torch.bfloat16, device=dev)
+                f3d = torch.empty((w3.shape[0], 2 * (k3 + kd)), dtype=torch.bfloat16, device=dev)
+                fwd = [(f1, f1.data_ptr()), (f2, f2.data_ptr()), (f3d, f3d.data_ptr()), (f3d, f3d.data_ptr() + 4 * k3)]
+                bwd = tuple(item(w, sc, fbuf, fptr) for (w, sc), (fbuf, fptr) in zip(convs, fwd))
+                # w3 and wd are views into the ONE [N, 2 (K3 + Kd)] buffer
+                weights = PairWeights(f1, f2, f3d[:, :2 * k3], f3d[:, 2 * k3:] if wd is not None else None,
+                                      f3d if wd is not None else None, bwd + ((None,) if wd is None else ()))
+            self.entries[key] = [weights, tuple(ws), tuple(sc for _, sc in convs), None]
         table = np.zeros((len(rows), 8), dtype=np.int64)
         for i, r in enumerate(rows):
             table[i] = r
@@ -169,7 +191,7 @@ class WeightPrepPlan:
         self.event.record(self.stream)
 
     def lookup(self, key, scales):
-        """The block's ``wpairs`` (forward forms, ``"wts"`` = transposed forms), or None: prepare them yourself."""
+        """The block's ``PairWeights`` / the lone convolution's ``ConvWeights``, or None: prepare them yourself."""
         ent = self.entries.get(key)
         if ent is None or self.epoch != _WEIGHTS_EPOCH[0]:
             return None
@@ -216,68 +238,58 @@ class GradLink:
         self.claimed = False  # a pair-only output feeds exactly ONE block (its fp32 handle is a placeholder)
 
 
+# Everything ``_BottleneckPair`` takes besides its differentiable tensors.  xp: pair form of the input rows or None; geom = (h, w)
+# of the map the rows tile; scales = (s1, s2, s3, sd), shifts = (b1, b2, b3 = the conv3 (+ shortcut) shift): the folded FrozenBN
+# affines of the RAW weights (no gradient); weights: ``PairWeights`` prepared ahead (a frozen block's cache, a ``WeightPrepPlan``)
+# or None; the flags and ``select``: see ``bottleneck_pair``; link_in / link_out: the ``GradLink`` of the input / for the output.
+PairSpec = namedtuple("PairSpec", "xp geom scales shifts weights want_pair want_f32 pool pool_only_ok select link_in link_out")
+
+
 class _BottleneckPair(Function):
     @staticmethod
-    def forward(ctx, x, xp, geom, w1, s1, b1, w2, s2, b2, w3, s3, b3, wd, sd, want_pair, wpairs, pool, want_f32=True,
-                link_in=None, link_out=None, select=None, pool_only_ok=False):
-        """x [M, Cin] f32 rows conv1 reads (may be None when wd is given and no input gradient is wanted), xp its pair
-        form or None; geom = (h, w) of the map the rows tile; w1/w2/w3/wd RAW convolution weights (wd None = identity
-        shortcut) with their folded FrozenBN scales s1/s2/s3/sd (per output channel, no gradient) and shifts b1/b2,
-        b3 = the conv3 (+ shortcut) shift; wpairs: optional cached pair weights of a frozen block.
+    def forward(ctx, x, w1, w2, w3, wd, spec):
+        """x [M, Cin] f32 rows conv1 reads (may be None when wd is given and no input gradient is wanted); w1/w2/w3/wd RAW
+        convolution weights (wd None = identity shortcut); everything else in ``spec`` (``PairSpec``).
         want_f32 False (with want_pair): the result is written in PAIR layout only -- the next block reads it as its conv1
         operand AND as its identity shortcut (hi + lo, exact in fp32; ``split_gemm_pair(residual_pair=...)``), so the 4
         bytes per element of the fp32 copy are neither written nor re-read.  The fp32 output slot then carries a
         zero-stride placeholder (never read: it carries the shape and routes the gradient between the autograd nodes of a
         chain)."""
-        h, w = geom
+        xp, (h, w), (s1, s2, s3, sd), (b1, b2, b3) = spec.xp, spec.geom, spec.scales, spec.shifts
+        want_pair, pool, select = spec.want_pair, spec.pool, spec.select
         if xp is None:
             xp = _C.split_pair(x)
         kh, kw = w2.shape[2], w2.shape[3]
         need_bwd = any(ctx.needs_input_grad)
-        wts = None
-        if wpairs is None:
-            # fold + matrix form + split (+ the transposed operands of the data gradients) in one launch per weight
-            p1, t1 = _C.weight_prep_pair(w1, s1, need_bwd)
-            p2, t2 = _C.weight_prep_pair(w2, s2, need_bwd)
-            p3, t3 = _C.weight_prep_pair(w3, s3, need_bwd)
-            pd, td = _C.weight_prep_pair(wd, sd, need_bwd) if wd is not None else (None, None)
-            wpairs = {"w1": p1, "w2": p2, "w3": p3, "wd": pd}
-            wts = (t1, t2, t3, td)
-        elif need_bwd:
-            wts = wpairs.get("wts")  # prepared behind the optimizer step together with the forward forms (WeightPrepPlan)
-        f32 = bool(want_f32 or pool or not want_pair)
+        pw = spec.weights if spec.weights is not None else PairWeights.prepare(w1, s1, w2, s2, w3, s3, wd, sd, need_bwd)
+        f32 = bool(spec.want_f32 or pool or not want_pair)
         x_real = x is not None and not is_placeholder(x)
-        _, o1p = _C.split_gemm_pair(xp, wpairs["w1"], b1, None, True, False, True)
-        _, o2p = _C.split_gemm_pair(o1p, wpairs["w2"], b2, None, True, False, True, conv=(h, w, kh, kw, False))
+        _, o1p = _C.split_gemm_pair(xp, pw.w1, b1, None, True, False, True)
+        _, o2p = _C.split_gemm_pair(o1p, pw.w2, b2, None, True, False, True, conv=(h, w, kh, kw, False))
         if wd is not None:
             # conv3 and the projection shortcut as ONE product over K = [conv2 output | block input] against
             # [w3 | wd] (pair rows concatenate block-wise): the shortcut tensor is never written or re-read
-            w3d = wpairs.get("w3d")
-            if w3d is None:
-                w3d = torch.cat([wpairs["w3"], wpairs["wd"]], 1)
-            out, outp = _C.split_gemm_pair(o2p, w3d, b3, None, True, f32, want_pair, a2_pair=xp)
+            out, outp = _C.split_gemm_pair(o2p, pw.w3d, b3, None, True, f32, want_pair, a2_pair=xp)
         elif x_real:
-            out, outp = _C.split_gemm_pair(o2p, wpairs["w3"], b3, x, True, f32, want_pair)
-        pooled_k = None
+            out, outp = _C.split_gemm_pair(o2p, pw.w3, b3, x, True, f32, want_pair)
+        pooled = None
         if wd is None and not x_real:  # the block input exists only as its pair form: shortcut = hi + lo
             fused_pool = (pool and 32 <= h * w <= 64
-                          and _C.split_gemm_pair_pool_supported(o2p.shape[0], wpairs["w3"].shape[0], o2p.shape[1] // 2, h * w))
+                          and _C.split_gemm_pair_pool_supported(o2p.shape[0], pw.w3.shape[0], o2p.shape[1] // 2, h * w))
             if fused_pool:
                 # the head's average pooling in THIS GEMM's epilogue (no second pass over the [rows, 2048] result); a pass
                 # that needs neither the backward nor the positives' maps (the no-grad teacher pass) writes the pooled rows only
-                keep = need_bwd or want_pair or select is not None or not pool_only_ok
-                out, outp, pooled_k = _C.split_gemm_pair_rp_pool(o2p, wpairs["w3"], b3, xp, True, keep, want_pair, h * w)
+                keep = need_bwd or want_pair or select is not None or not spec.pool_only_ok
+                out, outp, pooled = _C.split_gemm_pair_rp_pool(o2p, pw.w3, b3, xp, True, keep, want_pair, h * w)
                 if out is None and outp is None:
-                    out = nan_placeholder(pooled_k.device, o2p.shape[0], pooled_k.shape[1])  # never read
+                    out = nan_placeholder(pooled.device, o2p.shape[0], pooled.shape[1])  # never read
             else:
-                out, outp = _C.split_gemm_pair(o2p, wpairs["w3"], b3, None, True, f32, want_pair, residual_pair=xp)
+                out, outp = _C.split_gemm_pair(o2p, pw.w3, b3, None, True, f32, want_pair, residual_pair=xp)
         # pool: also return the mean over the h*w rows of every map (the head's average pooling) as an output of THIS
         # node, so that its gradient is broadcast inside the fused gate + split kernel of the backward instead of
         # being materialised ([rows, C] expand) and added to the dense gradient by two tensor ops
-        if pooled_k is not None:
-            pooled = pooled_k
-        else:
-            pooled = out.view(-1, h * w, out.shape[1]).mean(dim=1) if pool else None
+        if pool and pooled is None:
+            pooled = out.view(-1, h * w, out.shape[1]).mean(dim=1)
         # select [S] int64: also return the rows of the maps `select` ([S, h*w, C]; what the mask head reads: the res5
         # features of the positive RoIs) as an output of THIS node, so that their gradient reaches the backward's first
         # kernel as S dense maps -- an index backward would scatter it into a zero [rows, C] tensor (822 MB written and
@@ -287,12 +299,12 @@ class _BottleneckPair(Function):
         if out is None:  # NaN-filled: any consumer outside the one-block contract shows up in the loss instead of reading garbage
             out = nan_placeholder(outp.device, outp.shape[0], outp.shape[1] // 2)
         ctx.save_for_backward(xp, o1p, o2p, gate_src, w1, w2, w3, wd, s1, s2, s3, sd, select if out_sel is not None else None)
-        ctx.wts = wts
+        ctx.wts = pw.wts if need_bwd else None  # None: the backward prepares the transposed forms (a frozen block's cache has none)
         ctx.geom = (h, w, kh, kw)
         # link_in: this block's input exists only in pair layout and comes from a block that reads its gradient from the
         # link; link_out: this block's own output is pair-only and the block above may leave its gradient there
-        ctx.link_in = link_in if (wd is None and not x_real) else None
-        ctx.link_out = link_out if not f32 else None
+        ctx.link_in = spec.link_in if (wd is None and not x_real) else None
+        ctx.link_out = spec.link_out if not f32 else None
         ctx.set_materialize_grads(False)  # no zero tensors for absent / non-differentiable gradient slots
         if outp is not None:
             ctx.mark_non_differentiable(outp)
@@ -306,11 +318,11 @@ class _BottleneckPair(Function):
         if link_out is not None:
             link_out.grad_pair = None
         if dout is None and dpooled is None and linked is None and dsel is None:
-            return (None,) * 22
+            return (None,) * 6
         xp, o1p, o2p, out, w1, w2, w3, wd, s1, s2, s3, sd, select = ctx.saved_tensors   # out: fp32 result or its pair form (gate)
         h, w, kh, kw = ctx.geom
         need = ctx.needs_input_grad
-        need_x, need_w1, need_w2, need_w3, need_wd = need[0], need[3], need[6], need[9], need[12]
+        need_x, need_w1, need_w2, need_w3, need_wd = need[:5]
         wts = ctx.wts
         if wts is None:  # cached (frozen) weights in the forward: only the input gradient can be wanted
             wts = tuple(_C.weight_prep_pair(t, sc, True)[1] if t is not None else None
@@ -347,8 +359,7 @@ class _BottleneckPair(Function):
                                                                (w1.shape, w2.shape, w3.shape), branch_stream())
             link_in.grad_pair = gx
             dx = nan_placeholder(gx.device, xp.shape[0], xp.shape[1] // 2)
-            return (dx, None, None, dw1, None, None, dw2, None, None, dw3, None, None, None, None, None, None, None, None, None,
-                    None, None, None)
+            return dx, dw1, dw2, dw3, None, None
         dw3 = _dw(g3p, o2p, w3, s3) if need_w3 else None
         _, g2p = _C.split_gemm_pair_gated(g3p, t3, o2p)                  # (dY W3) gated by relu(o2), split: one kernel
         dw2 = _dw(g2p, o1p, w2, s2, (h, w, kh, kw)) if need_w2 else None
@@ -373,19 +384,21 @@ class _BottleneckPair(Function):
                         dx, _ = _C.split_gemm_pair(g1p, t1, None, None, False, True, False, residual_pair=g3p)
         if wd is not None and need_wd:
             dwd = _dw(g3p, xp, wd, sd)
-        return (dx, None, None, dw1, None, None, dw2, None, None, dw3, None, None, dwd, None, None, None, None, None, None,
-                None, None, None)
+        return dx, dw1, dw2, dw3, dwd, None
 
 
-def bottleneck_pair(x, xp, geom, w1, b1, w2, b2, w3, b3, wd=None, want_pair=False, wpairs=None, pool=False,
+def bottleneck_pair(x, xp, geom, w1, b1, w2, b2, w3, b3, wd=None, want_pair=False, weights=None, pool=False,
                     scales=(None, None, None, None), want_f32=True, select=None, pool_only_ok=False):
-    """(out f32 [M, Cout], out in pair layout or None[, mean of out over the h*w rows of every map when ``pool``]) of
-    one bottleneck on the rows x [M, Cin] of an (h, w) map.  w1/w2/w3/wd are the convolution weights as the model
-    stores them; ``scales`` = their folded FrozenBN scales (None = weights already folded).  ``pool_only_ok``: the caller
-    reads nothing but the pooled rows of a no-grad pass, so the [M, Cout] result itself need not be written (its handle is
-    then a NaN placeholder)."""
-    s1, s2, s3, sd = scales
+    """One bottleneck on the rows x [M, Cin] of an (h, w) map -> ``BlockResult`` (out f32 [M, Cout]; pair = out in pair
+    layout with ``want_pair``; pooled = mean of out over the h*w rows of every map with ``pool``; selected = (select, rows of
+    those maps) with ``select``).  w1/w2/w3/wd are the convolution weights as the model stores them; ``scales`` = their
+    folded FrozenBN scales (None = weights already folded); ``weights``: their ``PairWeights`` when prepared ahead.
+    ``pool_only_ok``: the caller reads nothing but the pooled rows of a no-grad pass, so the [M, Cout] result itself need
+    not be written (its handle is then a NaN placeholder)."""
     pair_only = want_pair and not want_f32 and not pool
+    # ``_ovis_grad_link`` is the ONE deliberate attribute on a tensor, set and read in this function alone: tying the link to
+    # the pair tensor itself is what makes a second consumer of a pair-only output fail loudly (``claimed``) -- a record
+    # beside the tensor could be copied or dropped without the tensor noticing
     link_in = getattr(xp, "_ovis_grad_link", None) if (xp is not None and (x is None or is_placeholder(x))) else None
     if link_in is not None and torch.is_grad_enabled():
         if link_in.claimed:
@@ -393,13 +406,11 @@ def bottleneck_pair(x, xp, geom, w1, b1, w2, b2, w3, b3, wd=None, want_pair=Fals
                                "handle is a placeholder, so the gradients of two consumers could not be summed")
         link_in.claimed = True
     link_out = GradLink() if pair_only else None
-    out, outp, pooled, out_sel = _BottleneckPair.apply(x, xp, geom, w1, s1, b1, w2, s2, b2, w3, s3, b3, wd, sd, want_pair,
-                                                       wpairs, pool, want_f32, link_in, link_out, select, pool_only_ok)
-    if out_sel is not None:
-        out._ovis_selected = (select, out_sel)  # [S, h*w, C] rows of the maps `select`, an output of the same node
+    spec = PairSpec(xp, geom, scales, (b1, b2, b3), weights, want_pair, want_f32, pool, pool_only_ok, select, link_in, link_out)
+    out, outp, pooled, out_sel = _BottleneckPair.apply(x, w1, w2, w3, wd, spec)
     if link_out is not None and outp is not None:
         outp._ovis_grad_link = link_out  # travels with the pair tensor to the block that consumes it
-    return (out, outp, pooled) if pool else (out, outp)
+    return BlockResult(out, outp, pooled, (select, out_sel) if out_sel is not None else None)
 
 
 class _ConvSamePair(Function):
@@ -412,10 +423,8 @@ class _ConvSamePair(Function):
         h, wd_ = geom
         n, c, kh, kw = w.shape
         xp = _C.split_pair(x2d)
-        if prepared is not None:  # {"w", "wt"} of a WeightPrepPlan: written behind the optimizer step
-            wp, wt = prepared["w"], prepared["wt"]
-        else:
-            wp, wt = _C.weight_prep_pair(w, None, ctx.needs_input_grad[0])
+        # prepared: the ``ConvWeights`` of a WeightPrepPlan, written behind the optimizer step
+        wp, wt = prepared if prepared is not None else _C.weight_prep_pair(w, None, ctx.needs_input_grad[0])
         y, _ = _C.split_gemm_pair(xp, wp, b, None, relu, True, False, conv=(h, wd_, kh, kw, False))
         ctx.wt = wt
         ctx.save_for_backward(xp, y if relu else None, w)
@@ -443,5 +452,5 @@ class _ConvSamePair(Function):
 
 def conv_same_pair(x2d, geom, w, b=None, relu=False, prepared=None):
     """x2d [N*H*W, C] f32 NHWC rows of (H, W) maps -> [N*H*W, Cout] f32 (C, Cout % 32 == 0).  ``prepared``: the weight's
-    pair forms from a ``WeightPrepPlan`` lookup, or None (prepared here)."""
+    ``ConvWeights`` from a ``WeightPrepPlan`` lookup, or None (prepared here)."""
     return _ConvSamePair.apply(x2d, geom, w, b, relu, prepared)

@@ -11,19 +11,29 @@ convolutions, and a bottleneck has two routes:
 
 * the pair route (``Bottleneck.pair_supported()`` on a device tensor): the whole block is one
   autograd node on the pair-layout split GEMM (layers/pair_bottleneck.py), NHWC, with the fold
-  inside its weight preparation;
+  inside its weight preparation (``PairWeights``).  A block hands on a ``BlockResult`` (out, pair,
+  pooled, selected) and the res5 head ``HeadFeatures`` (maps, pooled, selected): the node's extra
+  outputs travel as fields, nothing rides on a tensor;
 * the reference route (``Bottleneck.forward``, NCHW): each conv+FrozenBN pair is one convolution
   with the affine folded into the weights (``w * scale``) and bias (``shift``); the fold is a
   weight-sized op, differentiable w.r.t. the conv weight, and cached for frozen modules.  Host
   tensors take it, and so does a block off the pair route inside an NHWC chain (deformable,
   grouped, a strided 3x3), between two layout copies.
 """
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from ..layers import Conv2d, DFConv2d, FrozenBatchNorm2d
-from ..layers.pair_bottleneck import bottleneck_pair, is_placeholder, pair_weight
+from ..layers.pair_bottleneck import BlockResult, PairWeights, bottleneck_pair, is_placeholder, pair_weight
+
+
+# What the res5 head produces for R RoIs: ``maps`` the [R, C, h, w] view (a NaN placeholder after a ``pooled_only`` pass),
+# ``pooled`` their [R, C] means and ``selected`` = (select, the [S, h*w, C] rows of the maps ``select``) when the last block's
+# autograd node produced them itself, else None.
+HeadFeatures = namedtuple("HeadFeatures", "maps pooled selected", defaults=(None, None))
 
 
 class ConvBN(nn.Module):
@@ -162,7 +172,6 @@ class Bottleneck(nn.Module):
         return self._pair_node(None, xp, r, hs, ws, want_pair, pool, None, pair_only)
 
     def _pair_node(self, x2d, xp, r, hs, ws, want_pair, pool, select=None, pair_only=False, pool_only_ok=False):
-        from .. import _C
         # RAW weights + folded FrozenBN (scale, shift) pairs: the fold itself happens inside the node's weight-prep kernel
         w1, w2, w3 = self.conv1.weight, self.conv2.weight, self.conv3.weight
         (s1, b1), (s2, b2), (s3, b3) = self.bn1.fold(), self.bn2.fold(), self.bn3.fold()
@@ -172,47 +181,36 @@ class Bottleneck(nn.Module):
             sd, bd = self.downsample[1].fold()
         ws_all = [t for t in (w1, w2, w3, wd) if t is not None]
         bns = [self.bn1, self.bn2, self.bn3] + ([self.downsample[1]] if self.downsample is not None else [])
-        wpairs = None
+        weights = None
         if not any(t.requires_grad for t in ws_all):
             # frozen block: the pair forms of the folded weights (and the summed shift) are computed once
             key = tuple((id(t), t._version, t.device) for t in ws_all) + tuple(k for bn in bns for k in bn.fold_key())
             if self._pair_cache is None or self._pair_cache[0] != key:
-                wp = {"w1": _C.weight_prep_pair(w1, s1)[0], "w2": _C.weight_prep_pair(w2, s2)[0],
-                      "w3": _C.weight_prep_pair(w3, s3)[0],
-                      "wd": _C.weight_prep_pair(wd, sd)[0] if wd is not None else None}
-                if wd is not None:
-                    wp["w3d"] = torch.cat([wp["w3"], wp["wd"]], 1)  # conv3 + projection shortcut as one product
-                self._pair_cache = (key, wp, (b3 if bd is None else b3 + bd).contiguous())
-            wpairs, b3s = self._pair_cache[1], self._pair_cache[2]
+                self._pair_cache = (key, PairWeights.prepare(w1, s1, w2, s2, w3, s3, wd, sd, False),
+                                    (b3 if bd is None else b3 + bd).contiguous())
+            weights, b3s = self._pair_cache[1], self._pair_cache[2]
         else:
             b3s = b3 if bd is None else b3 + bd
             plan = self.__dict__.get("_prep_plan")  # trainable block: operands prepared behind the optimizer step, if still fresh
             if plan is not None:
-                wpairs = plan.lookup(id(self), (s1, s2, s3) if sd is None else (s1, s2, s3, sd))
-        res = bottleneck_pair(x2d, xp, (hs, ws), w1, b1, w2, b2, w3, b3s, wd, want_pair, wpairs, pool,
-                              scales=(s1, s2, s3, sd),
+                weights = plan.lookup(id(self), (s1, s2, s3) if sd is None else (s1, s2, s3, sd))
+        res = bottleneck_pair(x2d, xp, (hs, ws), w1, b1, w2, b2, w3, b3s, wd, want_pair, weights, pool, scales=(s1, s2, s3, sd),
                               want_f32=not (want_pair and pair_only and self.pair_only_chain), select=select,
                               pool_only_ok=pool_only_ok)
-        out = res[0].view(r, hs, ws, res[0].shape[-1])
-        if pool:
-            out._ovis_pooled = res[2]  # [R, C] mean over the map, an output of the same autograd node (see pooled())
-        sel = getattr(res[0], "_ovis_selected", None)
-        if sel is not None:
-            out._ovis_selected = sel
-        return (out, res[1]) if want_pair else out
+        return res._replace(out=res.out.view(r, hs, ws, res.out.shape[-1]))
 
     def forward_nhwc(self, x, prestrided=False, xp=None, want_pair=False, pool=False, select=None, pair_only=False,
                      pool_only_ok=False):
         """Same block on an NHWC tensor ``x`` [R, H, W, C].  On a device tensor a block that is ``pair_supported()``
         takes the pair route (``_forward_pair``).  ``prestrided``: x already holds only the positions conv1 / the
         shortcut read (the pooler applied their common stride); ``xp``: the pair-layout form of x when the producer
-        already wrote it; ``want_pair``: also return the pair form of the result for the next block; ``pair_only``: the
+        already wrote it; ``want_pair``: also write the pair form of the result for the next block; ``pair_only``: the
         consumer of the result ``takes_pair_only_input()``, so the fp32 copy may be dropped (the caller looks ahead:
         ``chain_nhwc``); ``pool`` / ``select`` / ``pool_only_ok``: see ``bottleneck_pair``.
         Otherwise (a host tensor, a block off the pair route) the reference route: ``forward`` between two layout
-        copies.  It refuses a pre-strided or pair-only input, ignores ``xp``, ``pool``, ``select`` and ``pool_only_ok``
-        (callers fall back when ``_ovis_pooled`` / ``_ovis_selected`` are absent) and hands on no pair form:
-        ``(y, None)`` with ``want_pair``."""
+        copies.  It refuses a pre-strided or pair-only input, ignores ``xp``, ``pool``, ``select`` and ``pool_only_ok`` and
+        hands on the fp32 result alone (callers fall back where ``pooled`` / ``selected`` are None).
+        Returns a ``BlockResult`` on every route."""
         if x.is_cuda and self.pair_supported():
             return self._forward_pair(x, prestrided, xp, want_pair, pool, select, pair_only, pool_only_ok)
         if is_placeholder(x):
@@ -222,8 +220,7 @@ class Bottleneck(nn.Module):
         if prestrided:
             raise RuntimeError("Bottleneck.forward_nhwc: a pre-strided input needs the pair-GEMM route (the reference "
                                "forward applies conv1's stride itself)")
-        y = self(x.permute(0, 3, 1, 2).contiguous()).permute(0, 2, 3, 1).contiguous()
-        return (y, None) if want_pair else y
+        return BlockResult(self(x.permute(0, 3, 1, 2).contiguous()).permute(0, 2, 3, 1).contiguous())
 
 
 def chain_nhwc(blocks, y, yp=None, first=None, last=None, then=None):
@@ -232,19 +229,18 @@ def chain_nhwc(blocks, y, yp=None, first=None, last=None, then=None):
     on the fp32 result alone, e.g. to a deformable block or, with STRIDE_IN_1X1 False, to a stage's first block (a strided
     3x3): those run the reference ``forward`` between two layout copies.  ``first`` / ``last``: extra keyword arguments
     of the first / last block's ``forward_nhwc``.  ``then``: the block a LATER call continues the chain with -- the last
-    block then hands on ``(y, yp)`` exactly as it would inside one chain (the frozen prefix of the trunk, run ahead on a
-    side stream: ``ResNetC4.forward_prefix``)."""
+    block then hands on ``out`` and ``pair`` exactly as it would inside one chain (the frozen prefix of the trunk, run ahead
+    on a side stream: ``ResNetC4.forward_prefix``).  Returns the last block's ``BlockResult``."""
     n = len(blocks)
     for i, b in enumerate(blocks):
         kw = dict(first or {}) if i == 0 else {}
         nxt = blocks[i + 1] if i + 1 < n else then
         if nxt is None:
             kw.update(last or {})
-        if nxt is not None and nxt.takes_pair_only_input():
-            y, yp = b.forward_nhwc(y, xp=yp, want_pair=True, pair_only=True, **kw)
-        else:
-            y, yp = b.forward_nhwc(y, xp=yp, **kw), None
-    return (y, yp) if then is not None else y
+        hand_on = nxt is not None and nxt.takes_pair_only_input()
+        res = b.forward_nhwc(y, xp=yp, want_pair=hand_on, pair_only=hand_on, **kw)
+        y, yp = res.out, res.pair
+    return res
 
 
 class Stem(nn.Module):
@@ -352,14 +348,14 @@ class ResNetC4(nn.Module):
             return None
         with torch.no_grad():
             x = self.stem.forward_gemm(x)
-            y, yp = chain_nhwc(blocks[:k], x.permute(0, 2, 3, 1).contiguous(), then=blocks[k])
-        return y, yp, k
+            res = chain_nhwc(blocks[:k], x.permute(0, 2, 3, 1).contiguous(), then=blocks[k])
+        return res.out, res.pair, k
 
     def forward(self, x, prefix=None):
         blocks = [b for name in self.stages for b in getattr(self, name)]
         if prefix is not None:  # the rest of the chain on the result of ``forward_prefix`` (same values as the whole chain)
             y, yp, k = prefix
-            return [chain_nhwc(blocks[k:], y, yp).permute(0, 3, 1, 2)]
+            return [chain_nhwc(blocks[k:], y, yp).out.permute(0, 3, 1, 2)]
         x = self.stem.forward_gemm(x) if (self.nhwc and self.stem.gemm_supported(x)) else self.stem(x)
         if self._chain_ok(x, blocks):
             # layer1-3 in NHWC with the split-GEMM bottlenecks of the res5 head (1x1 = row-major GEMM, 3x3 = implicit
@@ -368,7 +364,7 @@ class ResNetC4(nn.Module):
             # Trainable stages (teacher training): when every non-deformable block is on the pair route -- 39.4 vs 42.2 ms
             # per step against MIOpen's NCHW kernels (both with a warm MIOpen kernel cache; ``train_nhwc = False``
             # selects MIOpen).
-            y = chain_nhwc(blocks, x.permute(0, 2, 3, 1).contiguous())
+            y = chain_nhwc(blocks, x.permute(0, 2, 3, 1).contiguous()).out
             # the C4 map stays in NHWC memory (an NCHW-shaped view of it): the strided pooler reads channels-last maps in
             # place (csrc/roi_align.hip::roi_align_fwd_nhwc_in_strided_lds_kernel; it has no other form, ``_C`` copies a
             # map of the per-layer route below to this layout) and the RPN head wants NHWC rows anyway
@@ -407,7 +403,7 @@ class ResNetHead(nn.Module):
         the channels_last view of the result; ``nhwc = False`` keeps the plain per-layer convolution path."""
         if x.is_cuda and self.nhwc:
             # the first block's stride-2 slice makes this the only NCHW -> NHWC copy
-            return chain_nhwc(list(self.layer4), x.permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+            return chain_nhwc(list(self.layer4), x.permute(0, 2, 3, 1)).out.permute(0, 3, 1, 2)
         return self.layer4(x)
 
     def pooler_stride(self):
@@ -426,24 +422,19 @@ class ResNetHead(nn.Module):
         return bool(self.pooler_stride()) and b0.pair_supported() and b0._fd is not None
 
     def forward_pooled_nhwc(self, y, yp=None, shape=None, select=None, pooled_only=False):
-        """y [R, 7, 7, C]: the pooled bins conv1 reads, NHWC (from ``forward_strided_nhwc``) -> [R, 2048, 7, 7] view;
-        or y None and yp the same bins in pair layout with shape = (R, 7, 7) (from ``roi_align_forward_strided_pair``).
-        ``pooled_only``: the caller reads nothing but the pooled [R, 2048] rows (``_ovis_pooled``) of a no-grad pass -- the
-        last block may then skip writing its [R*49, 2048] result (the returned view is a NaN placeholder)."""
+        """y [R, 7, 7, C]: the pooled bins conv1 reads, NHWC (from ``forward_strided_nhwc``) -> ``HeadFeatures`` with the
+        [R, 2048, 7, 7] view as ``maps``; or y None and yp the same bins in pair layout with shape = (R, 7, 7) (from
+        ``roi_align_forward_strided_pair``).  ``pooled_only``: the caller reads nothing but the ``pooled`` [R, 2048] rows of a
+        no-grad pass -- the last block may then skip writing its [R*49, 2048] result (``maps`` is a NaN placeholder)."""
         blocks = list(self.layer4)
+        last = {"pool": True, "select": select, "pool_only_ok": pooled_only}
         if y is None:  # bins in pair layout only: the first block runs on them directly
-            y, yp = blocks[0].forward_pair_rows(yp, shape[0], shape[1], shape[2], want_pair=True,
-                                                pair_only=blocks[1].takes_pair_only_input())
-            y = chain_nhwc(blocks[1:], y, yp, last={"pool": True, "select": select, "pool_only_ok": pooled_only})
+            res = blocks[0].forward_pair_rows(yp, shape[0], shape[1], shape[2], want_pair=True,
+                                              pair_only=blocks[1].takes_pair_only_input())
+            res = chain_nhwc(blocks[1:], res.out, res.pair, last=last)
         else:
-            y = chain_nhwc(blocks, y, yp, first={"prestrided": True},
-                           last={"pool": True, "select": select, "pool_only_ok": pooled_only})
-        out = y.permute(0, 3, 1, 2)
-        for attr in ("_ovis_pooled", "_ovis_selected"):  # outputs of the last block's autograd node, carried on its result
-            v = getattr(y, attr, None)
-            if v is not None:
-                setattr(out, attr, v)
-        return out
+            res = chain_nhwc(blocks, y, yp, first={"prestrided": True}, last=last)
+        return HeadFeatures(res.out.permute(0, 3, 1, 2), res.pooled, res.selected)
 
 
 def _trainable_pair_blocks(model):

@@ -25,7 +25,7 @@ from torch import nn
 from .. import _C
 from ..layers import (Conv2d, ConvTranspose2d, ROIAlign, linear_mfma, smooth_l1_loss, smooth_l1_picked, stochastic_mask_bce,
                       text_logits, weighted_cross_entropy)
-from .backbone import ResNetHead
+from .backbone import HeadFeatures, ResNetHead
 from .box_coder import BoxCoder
 from .matcher import BalancedPositiveNegativeSampler, Matcher
 from .structures import BoxList, PastedMasks, PolygonMasks, box_iou, boxlist_nms, cat_boxlist
@@ -73,7 +73,8 @@ class ResNet50Conv5ROIFeatureExtractor(nn.Module):
 
     def forward_rois(self, x, rois, select=None, pooled_only=False):
         """``rois`` [R, 5] = (image index into x[0], x1, y1, x2, y2): the same pass on an explicit RoI tensor (lets a
-        caller pool RoIs of several proposal lists / image subsets in one go)."""
+        caller pool RoIs of several proposal lists / image subsets in one go).  Returns ``HeadFeatures`` on every route;
+        the un-fused device route and the host route leave ``pooled`` and ``selected`` None."""
         p = self.pooler.pooler
         s = self.head.pooler_stride() if x[0].is_cuda else 0
         if s:  # the head's first 1x1 has stride s: pool only the bins it reads, straight into NHWC
@@ -84,7 +85,7 @@ class ResNet50Conv5ROIFeatureExtractor(nn.Module):
                 yp, (oh, ow) = _C.roi_align_forward_strided_pair(x[0], rois, p.spatial_scale, ph, pw, p.sampling_ratio, s)
                 return self.head.forward_pooled_nhwc(None, yp, (rois.shape[0], oh, ow), select=select, pooled_only=pooled_only)
             return self.head.forward_pooled_nhwc(p.forward_strided_nhwc(x[0], rois, s), select=select, pooled_only=pooled_only)
-        return self.head(p(x[0], rois))
+        return HeadFeatures(self.head(p(x[0], rois)))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -122,11 +123,9 @@ class FastRCNNPredictor(nn.Module):
         nn.init.constant_(self.bbox_pred.bias, 0)
 
     def pooled(self, x):
+        """[R, C, h, w] maps -> their [R, C] means; [R, C] rows (``HeadFeatures.pooled``, where the head produced them) as is."""
         if x.dim() != 4:
             return x
-        p = getattr(x, "_ovis_pooled", None)
-        if p is not None and p.shape == (x.shape[0], x.shape[1]):
-            return p  # the res5 head's last autograd node already produced the pooled map (backbone.py::_forward_pair)
         xl = x.permute(0, 2, 3, 1)
         if xl.is_contiguous():
             # the res5 head hands over an NCHW view of NHWC memory: reduce over the contiguous [R, H*W, C] form, so
@@ -417,15 +416,13 @@ class ROIBoxHead(nn.Module):
                 proposals = self.loss_evaluator.subsample(proposals, targets)
         # evaluation / no-grad passes read nothing but the pooled rows of the box features (the predictor here, the teacher's
         # ``predictor.embed`` in generate_pseudo_label; the mask head pools its own features then): the res5 head's last
-        # block may leave its [R*49, 2048] result unwritten
+        # block may leave its [R*49, 2048] result unwritten (``maps`` is then a NaN placeholder).  Such a pass hands the
+        # [R, 2048] rows themselves on as the box features -- ``predictor.pooled`` / ``embed`` take 2-D input -- so that no
+        # consumer of ``package_x['bbox']`` can read the placeholder
         pooled_only = not self.training and not torch.is_grad_enabled()
-        x = self.feature_extractor(features, proposals, pooled_only=pooled_only)
-        if pooled_only and getattr(x, "_ovis_pooled", None) is not None:
-            # the pass may have produced NOTHING but the pooled rows (the [R, 2048, 7, 7] view is then a NaN placeholder):
-            # hand the [R, 2048] rows themselves on as the box features -- ``predictor.pooled`` / ``embed`` take 2-D input --
-            # so that no consumer of ``package_x['bbox']`` can read the placeholder
-            x = x._ovis_pooled
-        class_logits, box_regression = self.predictor(x)
+        feats = self.feature_extractor(features, proposals, pooled_only=pooled_only)
+        x = feats.pooled if (pooled_only and feats.pooled is not None) else feats.maps
+        class_logits, box_regression = self.predictor(feats.pooled if feats.pooled is not None else x)
         if not self.training:
             return x, self.post_processor((class_logits, box_regression), proposals), {}
         loss_classifier, loss_box_reg = self.loss_evaluator(class_logits, box_regression)
@@ -761,7 +758,7 @@ class ROIMaskHead(nn.Module):
             else:
                 x = features[sel]
         else:
-            x = self.feature_extractor(features, proposals)
+            x = self.feature_extractor(features, proposals).maps
         if self.training:
             return x, proposals, dict(loss_mask=self.fused_training_loss(x, proposals, targets, compute_uncertain, eps))
         if compute_uncertain:
@@ -837,8 +834,8 @@ class CombinedROIHeads(nn.ModuleDict):
         # so the last res5 block hands those maps out itself (their gradient then enters its backward as dense maps
         # instead of being scattered into a zero tensor of all RoIs first)
         sel_pos = positives_index([p for props in sampled for p in props]) if self.mask_on else None
-        x = box.feature_extractor.forward_rois([feat], rois, select=sel_pos)
-        pooled = box.predictor.pooled(x)
+        x, pooled, handed = box.feature_extractor.forward_rois([feat], rois, select=sel_pos)
+        pooled = box.predictor.pooled(pooled if pooled is not None else x)
         counts = [sum(len(p) for p in props) for props in sampled]
         out, off = [], 0
         for br, props, cnt in zip(branches, sampled, counts):
@@ -857,7 +854,6 @@ class CombinedROIHeads(nn.ModuleDict):
                 pos_masks = [[p.get_field("labels") > 0 for p in props] for props in sampled]
                 sel = _cat([m for ms in pos_masks for m in ms], 0)
                 pos_all = [[p[m] for p, m in zip(props, ms)] for props, ms in zip(sampled, pos_masks)]
-            handed = getattr(x, "_ovis_selected", None)
             fl = x.permute(0, 2, 3, 1)
             if handed is not None and handed[0] is sel:
                 xs = handed[1].view(sel.numel(), x.shape[2], x.shape[3], x.shape[1]).permute(0, 3, 1, 2)

@@ -40,7 +40,7 @@ def record_gates(sites):
     def bneck(x, xp, geom, *a, **k):
         mask_site[0] = None
         res = orig_b(x, xp, geom, *a, **k)
-        node = res[0].grad_fn
+        node = res.out.grad_fn
         if node is not None:  # (a frozen block records nothing: no gradient crosses its ReLUs)
             h, w = geom
             for t in node.saved_tensors[1:4]:  # o1 (pair), o2 (pair), the block output (fp32 or pair)

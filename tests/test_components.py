@@ -629,3 +629,46 @@ def test_branch_run_ahead_joins_precomputed_gradients_to_the_graph():
     gf, gp = run(1.0, 1.0, [None] + pre[1:])   # a frozen trunk: only the head trains
     assert torch.equal(gf, torch.full_like(feature, 2.0)) and torch.equal(gp[0], pre[1])
 
+
+
+def test_roi_feature_extractor_hands_out_the_head_record_on_host_tensors():
+    """``ResNet50Conv5ROIFeatureExtractor`` returns ``HeadFeatures`` on the host route too, with nothing but the maps in it
+    (``pooled`` / ``selected`` are outputs of the device route's last autograd node); ``FastRCNNPredictor`` on those maps
+    gives the logits of the pass without the record -- pooler bins -> ``ResNetHead`` -> predictor, bit for bit -- which are
+    avgpool -> Linear -> product with the class matrix (fp64; bound: the two fp32 dot products of 2048 and 768 terms at
+    2^-24 per term, worst case)."""
+    from tests.oracle_backend import oracle_ops
+    from tests.tiny_model import build_tiny
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.backbone import HeadFeatures
+
+    model, _, e_seen, _, _ = build_tiny("zeroshot_mask")
+    box = model.roi_heads["box"].eval()
+    box.predictor.set_class_embeddings(e_seen)
+    fe, pred = box.feature_extractor, box.predictor
+    g = torch.Generator().manual_seed(2)
+    feat = torch.randn(2, fe.head.layer4[0].conv1.in_channels, 10, 12, generator=g)
+    props = []
+    for n in (5, 3):
+        xy = torch.rand(n, 2, generator=g) * torch.tensor([120.0, 100.0])
+        props.append(BoxList(torch.cat([xy, xy + 16 + torch.rand(n, 2, generator=g) * 50], 1), (192, 160)))
+    with oracle_ops(), torch.no_grad():
+        feats = fe([feat], props)
+        assert isinstance(feats, HeadFeatures) and feats.pooled is None and feats.selected is None
+        assert feats.maps.shape == (8, fe.out_channels, 7, 7)
+        by_rois = fe.forward_rois([feat], fe.pooler.convert_to_roi_format(props))
+        assert isinstance(by_rois, HeadFeatures) and by_rois[1:] == (None, None) and torch.equal(by_rois.maps, feats.maps)
+        logits, deltas = pred(feats.maps)
+        plain = fe.head(fe.pooler([feat], props))
+        assert torch.equal(plain, feats.maps)
+        want_logits, want_deltas = pred(plain)
+        assert torch.equal(logits, want_logits) and torch.equal(deltas, want_deltas)
+        assert torch.equal(pred.pooled(feats.maps), feats.maps.mean(dim=(2, 3))) and pred.pooled(deltas) is deltas
+        x_box, _, _ = box([feat], [p.copy_with_fields([]) for p in props])
+        assert torch.equal(x_box, feats.maps)  # the box features of a host pass stay the maps
+    pooled = feats.maps.double().mean(dim=(2, 3))
+    emb = F.linear(pooled, pred.emb_pred.weight.double(), pred.emb_pred.bias.double())
+    ref_logits = emb @ pred.cls_score.double().t()
+    ref_deltas = F.linear(pooled, pred.bbox_pred.weight.double(), pred.bbox_pred.bias.double())
+    tol = (2048 + 768) * 2.0 ** -24
+    assert logits.shape == ref_logits.shape and (logits.double() - ref_logits).abs().max().item() <= tol * ref_logits.abs().max().item()
+    assert (deltas.double() - ref_deltas).abs().max().item() <= tol * ref_deltas.abs().max().item()

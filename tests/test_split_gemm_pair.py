@@ -211,7 +211,9 @@ def test_bottleneck_pair_node_vs_fp64_autograd(proj):
     w3 = (torch.randn(cout, cb, 1, 1, device=dev) / cb ** 0.5).requires_grad_(True)
     wd = (torch.randn(cout, cin, 1, 1, device=dev) / cin ** 0.5).requires_grad_(True) if proj else None
     b1, b2, b3 = (torch.randn(n, device=dev) * 0.1 for n in (cb, cb, cout))
-    out, outp = bottleneck_pair(x, None, (h, w), w1, b1, w2, b2, w3, b3, wd, True)
+    res = bottleneck_pair(x, None, (h, w), w1, b1, w2, b2, w3, b3, wd, True)
+    out, outp = res.out, res.pair
+    assert res.pooled is None and res.selected is None
     from cvpr22_cross_modal_pseudo_labeling_amd import _C as C
     assert torch.equal(outp, C.split_pair(out.detach()))
     gout = torch.randn_like(out)
@@ -346,7 +348,7 @@ def test_bottleneck_chain_pair_only_vs_fp32_chain(train):
             b.pair_only_chain = pair_only
         xx = x.clone().requires_grad_(train)
         with torch.set_grad_enabled(train):
-            y = head.forward_pooled_nhwc(xx)
+            y = head.forward_pooled_nhwc(xx).maps
             if train:
                 head.zero_grad()
                 y.backward(gy)
@@ -356,8 +358,8 @@ def test_bottleneck_chain_pair_only_vs_fp32_chain(train):
     b0 = head.layer4[0]
     b0.pair_only_chain = True
     with torch.no_grad():
-        mid, midp = b0.forward_nhwc(x, prestrided=True, want_pair=True, pair_only=True)
-        both, bothp = b0.forward_nhwc(x, prestrided=True, want_pair=True)  # no look-ahead given: both forms are written
+        mid, midp = b0.forward_nhwc(x, prestrided=True, want_pair=True, pair_only=True)[:2]
+        both, bothp = b0.forward_nhwc(x, prestrided=True, want_pair=True)[:2]  # no look-ahead given: both forms are written
     assert is_placeholder(mid) and midp.shape == (20 * 49, 2 * 2048)
     assert bool(torch.isnan(mid).all())  # a misuse of the placeholder shows up as NaN, not as plausible garbage
     assert not is_placeholder(both) and torch.equal(bothp, midp)
@@ -428,7 +430,8 @@ def test_pair_only_output_feeds_exactly_one_block():
     head = ResNetHead(cfg).cuda()
     b0, b1 = head.layer4[0], head.layer4[1]
     x = torch.randn(4, 7, 7, 1024, device="cuda", requires_grad=True)
-    mid, midp = b0.forward_nhwc(x, prestrided=True, want_pair=True, pair_only=True)
+    res = b0.forward_nhwc(x, prestrided=True, want_pair=True, pair_only=True)
+    mid, midp = res.out, res.pair
     b1.forward_nhwc(mid, xp=midp)
     with pytest.raises(RuntimeError, match="can feed one block"):
         b1.forward_nhwc(mid, xp=midp)
@@ -464,11 +467,11 @@ def test_frozen_trunk_with_stride_in_3x3_keeps_fp32_between_routes():
         body.nhwc = True
         # the hand-over in front of the strided block carries real fp32 values; inside a stage it is pair-only
         y = body.stem.forward_gemm(x).permute(0, 2, 3, 1).contiguous()
-        mid, midp = body.layer1[0].forward_nhwc(y, want_pair=True, pair_only=body.layer1[1].takes_pair_only_input())
+        mid, midp = body.layer1[0].forward_nhwc(y, want_pair=True, pair_only=body.layer1[1].takes_pair_only_input())[:2]
         assert is_placeholder(mid) and midp is not None
-        last1 = chain_nhwc(list(body.layer1), y)
-        m2, m2p = body.layer1[1].forward_nhwc(mid, xp=midp, want_pair=True, pair_only=body.layer1[2].takes_pair_only_input())
-        out, outp = body.layer1[2].forward_nhwc(m2, xp=m2p, want_pair=True, pair_only=body.layer2[0].takes_pair_only_input())
+        last1 = chain_nhwc(list(body.layer1), y).out
+        m2, m2p = body.layer1[1].forward_nhwc(mid, xp=midp, want_pair=True, pair_only=body.layer1[2].takes_pair_only_input())[:2]
+        out, outp = body.layer1[2].forward_nhwc(m2, xp=m2p, want_pair=True, pair_only=body.layer2[0].takes_pair_only_input())[:2]
         assert not is_placeholder(out) and torch.equal(out, last1)
         with pytest.raises(RuntimeError, match="pair layout only"):
             body.layer2[0].forward_nhwc(mid.expand(1, 32, 40, 256), xp=None)
@@ -539,8 +542,9 @@ def test_bottleneck_pair_pooled_output_and_fused_pool_gradient():
         x = torch.randn(r * h * w, cin, device=dev, generator=torch.Generator(device=dev).manual_seed(1)).requires_grad_(True)
         wl = [t.clone().requires_grad_(True) for t in ws]
         res = bottleneck_pair(x, None, (h, w), wl[0], bs[0], wl[1], bs[1], wl[2], bs[2], None, False, None, pool)
-        out = res[0]
-        pooled = res[2] if pool else out.view(r, h * w, cout).mean(1)
+        out = res.out
+        assert (res.pooled is not None) == pool
+        pooled = res.pooled if pool else out.view(r, h * w, cout).mean(1)
         loss = (pooled * gp).sum() + ((out * gd).sum() if dense else 0.0)
         grads = torch.autograd.grad(loss, [x] + wl)
         return pooled.detach(), grads
@@ -560,6 +564,77 @@ def test_bottleneck_pair_pooled_output_and_fused_pool_gradient():
     assert torch.equal(g32, want) and torch.equal(g_pair, C.split_pair(want))
     g_pair, g32 = C.gate_split_pair(None, y, want_f32=True, pooled=pl, pool_rows=7)
     assert torch.equal(g32, (pl * (1.0 / 7)).repeat_interleave(7, 0) * (y > 0))
+
+
+def _record_case(cb, seed):
+    """Host tensors of an identity block 128 -> cb -> 128 on R = 3 maps of 7 x 7 (147 rows: one full 128-row tile + a partial
+    one), its fp64 result and the smallest |pre-activation| of its three ReLUs.  The shifts centre the pre-activations at +1.5
+    (about a tenth of the gates stay closed)."""
+    g = torch.Generator().manual_seed(seed)
+    r, h, w, c = 3, 7, 7, 128
+    x = torch.randn(r * h * w, c, generator=g)
+    hi = x.to(torch.bfloat16)
+    x = hi.float() + (x - hi.float()).to(torch.bfloat16).float()  # exactly what its pair form holds (hi + lo)
+    ws = [torch.randn(cb, c, 1, 1, generator=g) / c ** 0.5, torch.randn(cb, cb, 3, 3, generator=g) / (9 * cb) ** 0.5,
+          torch.randn(c, cb, 1, 1, generator=g) / cb ** 0.5]
+    bs = [torch.randn(n, generator=g) * 0.1 + 1.5 for n in (cb, cb, c)]
+    gp, gs = torch.randn(r, c, generator=g), torch.randn(2, h * w, c, generator=g)
+
+    def ref(wl):
+        xd = x.double().view(r, h, w, c).permute(0, 3, 1, 2)
+        p1 = F.conv2d(xd, wl[0], bs[0].double())
+        p2 = F.conv2d(F.relu(p1), wl[1], bs[1].double(), padding=1)
+        p3 = F.conv2d(F.relu(p2), wl[2], bs[2].double()) + xd
+        margin = min(p.detach().abs().min().item() for p in (p1, p2, p3))
+        return F.relu(p3).permute(0, 2, 3, 1).reshape(r, h * w, c), margin
+
+    return x, ws, bs, gp, gs, ref
+
+
+# seeds at which no ReLU of the fp64 reference has a pre-activation within 1e-4 of zero (found on the host; asserted below): the
+# node's three-term bf16 products sit ~4e-6 relative from fp64, and ONE gate that falls on the other side of zero moves a
+# weight gradient by ~1 / sqrt(rows * channels) = 4e-3 of its norm -- with the gates equal what is compared is arithmetic
+_RECORD_SEEDS = {32: 3, 512: 9}
+
+
+@pytest.mark.parametrize("cb,fused", [(32, True), (512, False)])
+def test_block_record_carries_pooled_and_selected_outputs(cb, fused):
+    """``bottleneck_pair(pool=True, select=...)`` hands ``pooled`` and ``selected`` out as FIELDS of its ``BlockResult`` --
+    nothing rides on the ``out`` tensor, so a view / copy of it loses nothing.  K = 32: un-split launch plan, the fused-pool
+    epilogue runs; K = 512: the plan splits K, ``split_gemm_pair_pool_supported`` is false and the unfused mean runs.  Both:
+    pooled = mean of out over every map (1e-5 of its norm, the tolerance of
+    ``test_bottleneck_pair_pooled_output_and_fused_pool_gradient``), the selected rows bit-equal to out's, the weight gradients
+    through both outputs within 1e-5 (L2) of fp64 autograd."""
+    from cvpr22_cross_modal_pseudo_labeling_amd.layers.pair_bottleneck import BlockResult, bottleneck_pair
+    C = _C()
+    r, h, w, c = 3, 7, 7, 128
+    x, ws, bs, gp, gs, ref = _record_case(cb, _RECORD_SEEDS[cb])
+    assert C.split_gemm_pair_pool_supported(r * h * w, c, cb, h * w) == fused
+    calls, rp_pool = [], C.split_gemm_pair_rp_pool
+    C.split_gemm_pair_rp_pool = lambda *a, **k: calls.append(1) or rp_pool(*a, **k)
+    wl = [t.cuda().requires_grad_(True) for t in ws]
+    sel = torch.tensor([0, 2], device="cuda")
+    try:  # the block input exists in pair layout only (x None): the route of the res5 head's last block
+        res = bottleneck_pair(None, C.split_pair(x.cuda()), (h, w), wl[0], bs[0].cuda(), wl[1], bs[1].cuda(), wl[2], bs[2].cuda(),
+                              None, False, None, True, select=sel)
+    finally:
+        C.split_gemm_pair_rp_pool = rp_pool
+    assert isinstance(res, BlockResult) and res.pair is None and len(calls) == int(fused)
+    maps = res.out.view(r, h * w, c)
+    want = maps.detach().mean(1)
+    assert res.pooled.shape == (r, c) and (res.pooled.detach() - want).norm().item() <= 1e-5 * want.norm().item()
+    assert res.selected[0] is sel and torch.equal(res.selected[1], maps[sel])
+    grads = torch.autograd.grad((res.pooled * gp.cuda()).sum() + (res.selected[1] * gs.cuda()).sum(), wl)
+
+    wd = [t.double().requires_grad_(True) for t in ws]
+    o, margin = ref(wd)
+    assert margin > 1e-4, margin
+    assert (maps.detach().cpu().double() - o).abs().max().item() <= 1e-5 * o.abs().max().item()
+    rgrads = torch.autograd.grad((o.mean(1) * gp.double()).sum() + (o[[0, 2]] * gs.double()).sum(), wd)
+    for name, a, b in zip(("dw1", "dw2", "dw3"), grads, rgrads):
+        err = (a.cpu().double() - b).norm().item() / b.norm().item()
+        print(f"cb={cb} {name}: relative L2 error vs fp64 = {err:.3e}")
+        assert err <= 1e-5, (name, err)
 
 
 def test_strided_pooler_pair_output_is_split_of_fp32_output():
@@ -763,14 +838,14 @@ def test_weight_prep_plan_equals_per_weight_preparation():
         assert wp is not None
         want = [_C.weight_prep_pair(w, s, True) for w, s in convs]
         for name, (f, _) in zip(("w1", "w2", "w3", "wd"), want):
-            assert torch.equal(wp[name].contiguous().view(torch.int16), f.view(torch.int16)), (key, name)
+            assert torch.equal(getattr(wp, name).contiguous().view(torch.int16), f.view(torch.int16)), (key, name)
         for i, (_, t) in enumerate(want):
-            assert torch.equal(wp["wts"][i].view(torch.int16), t.view(torch.int16)), (key, i)
+            assert torch.equal(wp.wts[i].view(torch.int16), t.view(torch.int16)), (key, i)
         if len(convs) == 4:
-            assert torch.equal(wp["w3d"].view(torch.int16), torch.cat([want[2][0], want[3][0]], 1).view(torch.int16))
-            assert wp["w3"].data_ptr() == wp["w3d"].data_ptr()
+            assert torch.equal(wp.w3d.view(torch.int16), torch.cat([want[2][0], want[3][0]], 1).view(torch.int16))
+            assert wp.w3.data_ptr() == wp.w3d.data_ptr()
         else:
-            assert wp["wd"] is None and wp["wts"][3] is None and "w3d" not in wp
+            assert wp.wd is None and wp.wts[3] is None and wp.w3d is None
     scales_a = tuple(s for _, s in proj)
     # (1) a raw-pointer writer announced itself, (2) an in-place update moved a version counter, (3) other scale tensors
     note_weights_written()
@@ -782,9 +857,52 @@ def test_weight_prep_plan_equals_per_weight_preparation():
     assert plan.lookup("a", scales_a) is None and plan.lookup("b", tuple(s for _, s in plain)) is not None
     plan.run()
     wp = plan.lookup("a", scales_a)
-    assert torch.equal(wp["w2"].view(torch.int16), _C.weight_prep_pair(proj[1][0], proj[1][1], True)[0].view(torch.int16))
+    assert torch.equal(wp.w2.view(torch.int16), _C.weight_prep_pair(proj[1][0], proj[1][1], True)[0].view(torch.int16))
     assert plan.describes()
     assert plan.lookup("a", (scales_a[0].clone(),) + scales_a[1:]) is None and not plan.describes()
+
+
+def test_pair_weights_prepare_equals_the_plan():
+    """``PairWeights.prepare`` (one launch per weight + the [w3 | wd] concatenation: what the autograd node and the frozen
+    block cache build) holds, field by field, the bytes ``WeightPrepPlan.run()`` writes in one launch -- a projection block, an
+    identity block with mixed scales, and the ``ConvWeights`` of a lone 3x3 against its per-weight preparation."""
+    from cvpr22_cross_modal_pseudo_labeling_amd import _C
+    from cvpr22_cross_modal_pseudo_labeling_amd.layers.pair_bottleneck import ConvWeights, PairWeights, WeightPrepPlan
+
+    g = torch.Generator().manual_seed(6)
+
+    def conv(n, c, k, scaled=True):
+        w = (torch.randn(n, c, k, k, generator=g) * 0.1).cuda().requires_grad_()
+        return w, ((torch.rand(n, generator=g) + 0.5).cuda() if scaled else None)
+
+    def bits(t):
+        return t.contiguous().view(torch.int16)
+
+    proj = [conv(64, 256, 1), conv(64, 64, 3), conv(256, 64, 1), conv(256, 256, 1)]
+    plain = [conv(128, 512, 1, False), conv(128, 128, 3), conv(512, 128, 1, False)]
+    lone = [conv(128, 128, 3, False)]
+    plan = WeightPrepPlan([("a", proj), ("b", plain), ("c", lone)])
+    plan.run()
+    for key, convs in (("a", proj), ("b", plain)):
+        got = plan.lookup(key, tuple(s for _, s in convs))
+        flat = [t for ws in convs for t in ws] + [None, None] * (4 - len(convs))
+        for transposed in (True, False):
+            want = PairWeights.prepare(*flat, transposed)
+            assert isinstance(got, PairWeights) and isinstance(want, PairWeights)
+            for name in PairWeights._fields[:5]:  # w1, w2, w3, and wd + the [w3 | wd] matrix (None for an identity block)
+                a, b = getattr(got, name), getattr(want, name)
+                assert (a is None) == (b is None) == (len(convs) == 3 and name in PairWeights._fields[3:5]), (key, name)
+                assert a is None or torch.equal(bits(a), bits(b)), (key, name)
+            if not transposed:
+                assert want.wts is None
+                continue
+            assert len(got.wts) == len(want.wts) == 4
+            for i, (a, b) in enumerate(zip(got.wts, want.wts)):
+                assert (a is None) == (b is None) == (len(convs) == 3 and i == 3), (key, i)
+                assert a is None or torch.equal(bits(a), bits(b)), (key, i)
+    got = plan.lookup("c", (None,))
+    want = ConvWeights(*_C.weight_prep_pair(lone[0][0], None, True))
+    assert isinstance(got, ConvWeights) and torch.equal(bits(got.w), bits(want.w)) and torch.equal(bits(got.wt), bits(want.wt))
 
 
 @pytest.mark.parametrize("m_hw,cin,mid", [((3, 20, 24), 256, 128), ((2, 50, 84), 1024, 256), ((1, 7, 9), 128, 128)])

@@ -278,8 +278,9 @@ def run_student_staged(device, img, tol_feat, tol_grad, prop_frac):
         #   = the aligned regions' boxes after the teacher's own class-agnostic regression, unfiltered (is_teacher
         #   PostProcessor, box_head/inference.py:49-100); the argmax itself, from the scores the product computes:
         with torch.no_grad():
+            feats = model.roi_heads["box"].feature_extractor([fz["feat"]], [props])
             raw = model.roi_heads["box"].predictor.embed(
-                model.roi_heads["box"].feature_extractor([fz["feat"]], [props])) @ model._noun_embs(target).t()
+                feats.pooled if feats.pooled is not None else feats.maps) @ model._noun_embs(target).t()
         assert torch.equal(raw.argmax(0).cpu(), idx)
         s_want = torch.from_numpy(d[key + "region_noun_scores"])
         assert float((raw.float().cpu() - s_want).abs().max()) <= 1e-3 * float(s_want.abs().max())

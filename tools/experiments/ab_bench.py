@@ -28,7 +28,7 @@ PATCHES = {
                             "def _init(self, *a, **k):\n    _i(self, *a, **k); self.heads_as_one_branch = False\n"
                             "_d.GeneralizedRCNN.__init__ = _init"),
     "drop_trunk_dw": ("from cvpr22_cross_modal_pseudo_labeling_amd.layers import pair_bottleneck as _p; _b = _p._BottleneckPair.backward\n"
-                      "def _bw(ctx, *g):\n    out = list(_b(ctx, *g))\n    for i in (3, 6, 9, 12):\n        out[i] = None\n    return tuple(out)\n"
+                      "def _bw(ctx, *g):\n    out = list(_b(ctx, *g))\n    for i in (1, 2, 3, 4):\n        out[i] = None\n    return tuple(out)\n"
                       "_p._BottleneckPair.backward = staticmethod(_bw)"),
     # (needs tools/experiments/python_patches/trunk_dw_beside.patch applied)
     "dw_beside": "from cvpr22_cross_modal_pseudo_labeling_amd.layers import pair_bottleneck as _p; _p.DW_BESIDE_ROWS = 40000",
