@@ -107,18 +107,8 @@ def _record_stream(obj, stream):
     elif isinstance(obj, (list, tuple)):
         for v in obj:
             _record_stream(v, stream)
-    elif hasattr(obj, "bbox") and hasattr(obj, "extra_fields"):  # BoxList
-        _record_stream(obj.bbox, stream)
-        _record_stream(obj.extra_fields, stream)
-        _record_stream(getattr(obj, "pos_index", None), stream)  # sampled lists: where their positives sit
-    elif hasattr(obj, "polygon_start"):  # PolygonMasks
-        for t in (obj.coords, obj.polygon_start, obj.instance_start):
-            _record_stream(t, stream)
-    elif hasattr(obj, "probs") and hasattr(obj, "boxes"):  # PastedMasks
-        _record_stream(obj.probs, stream)
-        _record_stream(obj.boxes, stream)
-    elif hasattr(obj, "tensors") and hasattr(obj, "image_sizes"):  # ImageList: the padded batch to_image_list allocates
-        _record_stream(obj.tensors, stream)
+    elif hasattr(obj, "device_tensors"):  # BoxList, PolygonMasks, PastedMasks, ImageList (modeling/structures.py)
+        _record_stream(obj.device_tensors(), stream)
 
 
 _SIDE_STREAMS = {}

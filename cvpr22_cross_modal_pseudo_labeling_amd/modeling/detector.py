@@ -144,10 +144,7 @@ class STGeneralizedRCNN(nn.Module):
 
     def set_class_embeddings(self, embs):
         """Seen-class matrix with the all-zero background row 0 (engine/trainer.py:85-90)."""
-        self.roi_heads["box"].predictor.set_class_embeddings(embs)
-        # own reference: generate_pseudo_label swaps the teacher predictor's matrix for a dummy while it runs, and the
-        # frozen half may be running on another thread (engine/trainer.py::PipelinedTrainer)
-        self._seen_cls = self.roi_heads["box"].predictor.cls_score
+        self.roi_heads["box"].predictor.set_class_embeddings(embs)  # the only writer: every pass takes its matrix as an argument
 
     def _noun_embs(self, target):
         """[W, D] embeddings of an image's caption nouns: given (``cap_embs`` field), extracted from the strings
@@ -178,12 +175,6 @@ class STGeneralizedRCNN(nn.Module):
 
     def prepare_model(self):
         self.prepare_text()
-        student = self.roi_heads_student["box"].predictor
-        seen = getattr(self, "_seen_cls", None)
-        if seen is None:
-            seen = self.roi_heads["box"].predictor.cls_score
-        if student.cls_score is None:  # every pass sets the matrix it needs; this only covers first use
-            student.cls_score = seen
         if self.iter == 0 and not self.resume:
             self.roi_heads_student.load_state_dict(copy.deepcopy(self.roi_heads.state_dict()), strict=False)
             self.iter += 1
@@ -198,10 +189,9 @@ class STGeneralizedRCNN(nn.Module):
     @torch.no_grad()
     def generate_pseudo_label(self, features, proposals, noun_embs, targets):
         teacher = self.roi_heads
-        class_embs = teacher["box"].predictor.cls_score
-        teacher["box"].predictor.set_class_embeddings(features[0].new_zeros((1, teacher["box"].predictor.emb_dim)))
+        no_classes = features[0].new_zeros((1, teacher["box"].predictor.emb_dim))  # the passes' class scores are not read
         teacher.eval()
-        package_x, results, _ = teacher(features, proposals, None, bbox_only=True)
+        package_x, results, _ = teacher(features, proposals, None, bbox_only=True, cls_embs=no_classes)
         cls_embs = teacher["box"].predictor.embed(package_x["bbox"]).split([len(p) for p in proposals])
         pseudo_labels = []
         for emb_img, w_cap, result_img, target_img in zip(cls_embs, noun_embs, results, targets):
@@ -217,7 +207,7 @@ class STGeneralizedRCNN(nn.Module):
             pl.add_field("embs", emb_img[idx])
             pseudo_labels.append(pl)
         if self.mask_on:
-            _, results, _ = teacher(features, pseudo_labels, None, bbox_only=False)
+            _, results, _ = teacher(features, pseudo_labels, None, bbox_only=False, cls_embs=no_classes)
             for res, pl in zip(results, pseudo_labels):
                 if pl.bbox.is_cuda:
                     # the pasted image-size masks (Masker, mask_head/inference.py:124-205) are only ever cropped and
@@ -228,7 +218,6 @@ class STGeneralizedRCNN(nn.Module):
                                                       self.masker.threshold, self.masker.padding))
                 else:
                     pl.add_field("masks", self.masker(res.get_field("mask"), pl)[:, 0])  # [W,H,W] bool
-        teacher["box"].predictor.set_class_embeddings(class_embs)
         return pseudo_labels
 
     # -- step ----------------------------------------------------------------------------------------------
@@ -241,8 +230,8 @@ class STGeneralizedRCNN(nn.Module):
         if not self.training:
             self.rpn.eval()
             proposals, _ = self.rpn(images, features, None)
-            student["box"].predictor.set_class_embeddings(self.combine_embs(self.roi_heads["box"].predictor.cls_score))
-            _, result, _ = student(features, proposals, targets, is_eval_func=True)
+            _, result, _ = student(features, proposals, targets, is_eval_func=True,
+                                   cls_embs=self.combine_embs(self.roi_heads["box"].predictor.cls_score))
             return result
 
         frozen = self.forward_frozen(images, targets, features=features)
@@ -293,6 +282,7 @@ class STGeneralizedRCNN(nn.Module):
         """The trainable half of the step: both student passes and their losses on the outputs of ``forward_frozen``."""
         student = self.roi_heads_student
         self.prepare_model()
+        seen_embs = self.roi_heads["box"].predictor.cls_score
         # the all-parameter zero loss (st_generalized_rcnn.py:277-282) only enters the graph when a branch has no
         # images; it is ~3 launches per parameter, so it is built on first use
         dummy = []
@@ -311,13 +301,13 @@ class STGeneralizedRCNN(nn.Module):
                 dict(image_ids=frozen["idxs_cap"], proposals=frozen["cap_proposals"], targets=frozen["pseudo_targets"],
                      cls_embs=self.combine_embs(self.cap_embs), compute_uncertain=self.uncertainty, eps=eps),
                 dict(image_ids=frozen["idxs_gt"], proposals=frozen["gt_proposals"], targets=gt_targets,
-                     cls_embs=self.combine_embs(self._seen_cls), compute_uncertain=False, eps=None)])
+                     cls_embs=self.combine_embs(seen_embs), compute_uncertain=False, eps=None)])
         # ---- pseudo branch: images that come with caption nouns ------------------------------------------
         if frozen["idxs_cap"]:
             if not batched:
-                student["box"].predictor.set_class_embeddings(self.combine_embs(self.cap_embs))
                 _, _, loss_pseudo = student(frozen["cap_features"], frozen["cap_proposals"], frozen["pseudo_targets"],
-                                            compute_uncertain=self.uncertainty, eps=eps)
+                                            compute_uncertain=self.uncertainty, eps=eps,
+                                            cls_embs=self.combine_embs(self.cap_embs))
             for k in loss_pseudo:
                 if self.uncertainty and self.reweight:
                     if "mask" not in k:
@@ -335,8 +325,8 @@ class STGeneralizedRCNN(nn.Module):
         # ---- seen-class branch: images with box / mask ground truth -----------------------------------------
         if frozen["idxs_gt"] and not batched:
             gt_targets = [targets[i] for i in frozen["idxs_gt"]]
-            student["box"].predictor.set_class_embeddings(self.combine_embs(self._seen_cls))
-            _, _, loss_gt = student(frozen["gt_features"], frozen["gt_proposals"], gt_targets, compute_uncertain=False)
+            _, _, loss_gt = student(frozen["gt_features"], frozen["gt_proposals"], gt_targets, compute_uncertain=False,
+                                    cls_embs=self.combine_embs(seen_embs))
         for k in self.LOSS_NAMES:
             losses[k] = loss_gt[k] if k in loss_gt else dummy_loss()
 

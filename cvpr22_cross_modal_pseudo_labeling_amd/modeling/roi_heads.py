@@ -28,7 +28,7 @@ from ..layers import (Conv2d, ConvTranspose2d, ROIAlign, linear_mfma, smooth_l1_
 from .backbone import HeadFeatures, ResNetHead
 from .box_coder import BoxCoder
 from .matcher import BalancedPositiveNegativeSampler, Matcher
-from .structures import BoxList, PastedMasks, PolygonMasks, box_iou, boxlist_nms, cat_boxlist
+from .structures import BoxList, PastedMasks, PolygonMasks, SampledBoxList, box_iou, boxlist_nms, cat_boxlist
 
 
 def _cat(tensors, dim=0):
@@ -134,7 +134,8 @@ class FastRCNNPredictor(nn.Module):
             return xl.reshape(x.shape[0], -1, x.shape[1]).mean(dim=1)
         return x.mean(dim=(2, 3))
 
-    def forward(self, x):
+    def forward(self, x, cls_embs=None):
+        """``cls_embs`` [C, emb_dim]: the class-embedding matrix of this pass (None: the stored ``cls_score``)."""
         x = self.pooled(x)
         # both Linear layers share the pooled operand: one GEMM over the concatenated [768 + 8, 2048] weight, built
         # already padded with zero rows to the split GEMM's 128-column tiles (one cat, no separate pad)
@@ -149,7 +150,7 @@ class FastRCNNPredictor(nn.Module):
         head, bbox = y[:, :n1], y[:, n1:n]
         if not self.embedding_based:
             return head, bbox  # cls_score(x), bbox_pred(x): roi_box_predictors.py:70-72
-        cls_logit = text_logits(head, self.cls_score)  # einsum('pe,ce->pc')
+        cls_logit = text_logits(head, self.cls_score if cls_embs is None else cls_embs.to(head.device))  # einsum('pe,ce->pc')
         return cls_logit, bbox
 
     def _zero_rows(self, pad, x):
@@ -192,8 +193,8 @@ class FastRCNNLossComputation:
         """``subsample`` for several (proposals, targets) groups -- the student's pseudo-label and ground-truth branches --
         at once.  On the device every image costs two launches (IoU match + labels + delta targets, csrc/targets.hip
         ``match_encode``; fg / bg sampling, ``sample_fg_bg``) and the host reads the survivor counts of ALL images back in
-        ONE copy; the sampled lists carry ``pos_index`` (where the positives sit), so neither the box loss nor the mask
-        head runs a ``nonzero``.  The reference's sequence (box_head/loss.py:89-123: IoU matrix, Matcher, randperm
+        ONE copy; the sampled lists (``SampledBoxList``) carry ``pos_index`` (where the positives sit), so neither the box
+        loss nor the mask head runs a ``nonzero``.  The reference's sequence (box_head/loss.py:89-123: IoU matrix, Matcher, randperm
         sampler, boolean indexing: ~60 launches and 3 host syncs per image) serves CPU tensors."""
         if not all(p.bbox.is_cuda for props, _ in groups for p in props) or self.matcher.allow_low_quality_matches \
                 or not self.device_sampler:
@@ -218,8 +219,7 @@ class FastRCNNLossComputation:
                 b.add_field("labels", labels_s)
                 b.add_field("regression_targets", reg_s)
                 b.add_field("matched_gt", idx_s)
-                b.pos_index = slots[:npos]
-                group.append(b)
+                group.append(SampledBoxList(b, slots[:npos]))
             out.append(group)
         self._proposals = out[-1]
         return out
@@ -246,12 +246,15 @@ class FastRCNNLossComputation:
             labels_all.append(labels)
         pos, neg = self.sampler(labels_all, generator=self.generator)
         for prop, p, n in zip(proposals, pos, neg):
-            out.append(prop[torch.nonzero(p | n).squeeze(1)])
+            out.append(SampledBoxList(prop[torch.nonzero(p | n).squeeze(1)]))
         self._proposals = out
         return out
 
-    def __call__(self, class_logits, box_regression):
-        proposals = self._proposals
+    def __call__(self, class_logits, box_regression, proposals=None):
+        """``proposals``: the sampled lists the rows belong to (None: the ones the last ``subsample`` call stored, the
+        reference's protocol, box_head/loss.py:125-137)."""
+        if proposals is None:
+            proposals = self._proposals
         labels = _cat([p.get_field("labels") for p in proposals], 0)
         reg_targets = _cat([p.get_field("regression_targets") for p in proposals], 0)
         pos = positives_index(proposals)
@@ -273,20 +276,19 @@ class FastRCNNLossComputation:
 
 
 def positives_index(proposals):
-    """Row indices of the positives in the concatenation of sampled proposal lists, from the ``pos_index`` the device
-    sampler attached to every list (None when a list has none: the caller falls back to ``nonzero``)."""
+    """Row indices of the positives in the concatenation of sampled proposal lists, from the ``pos_index`` of every
+    ``SampledBoxList`` (None when a list has none: the caller falls back to ``nonzero``)."""
     parts, off = [], 0
     for p in proposals:
-        pi = getattr(p, "pos_index", None)
-        if pi is None:
+        if not isinstance(p, SampledBoxList) or p.pos_index is None:
             return None
-        parts.append(pi + off if off else pi)
+        parts.append(p.pos_index + off if off else p.pos_index)
         off += len(p)
     return _cat(parts, 0) if parts else None
 
 
 def positive_proposals(p):
-    """The positives of a sampled list as a light BoxList (boxes, labels, matched ground-truth index), flagged
+    """The positives of a sampled list as a light list (boxes, labels, matched ground-truth index), declared
     ``all_positive`` so that the mask loss neither re-matches them nor searches them again."""
     pi = p.pos_index
     if p.bbox.is_cuda:
@@ -296,8 +298,11 @@ def positive_proposals(p):
     out = BoxList(bbox, p.size)
     out.add_field("labels", labels)
     out.add_field("matched_gt", matched)
-    out.all_positive = True
-    return out
+    return SampledBoxList(out, all_positive=True)
+
+
+def _all_positive(p):
+    return isinstance(p, SampledBoxList) and p.all_positive
 
 
 class PostProcessor(nn.Module):
@@ -410,7 +415,7 @@ class ROIBoxHead(nn.Module):
                 p.requires_grad = False
         self.is_teacher = is_teacher
 
-    def forward(self, features, proposals, targets=None):
+    def forward(self, features, proposals, targets=None, cls_embs=None):
         if self.training:
             with torch.no_grad():
                 proposals = self.loss_evaluator.subsample(proposals, targets)
@@ -422,10 +427,10 @@ class ROIBoxHead(nn.Module):
         pooled_only = not self.training and not torch.is_grad_enabled()
         feats = self.feature_extractor(features, proposals, pooled_only=pooled_only)
         x = feats.pooled if (pooled_only and feats.pooled is not None) else feats.maps
-        class_logits, box_regression = self.predictor(feats.pooled if feats.pooled is not None else x)
+        class_logits, box_regression = self.predictor(feats.pooled if feats.pooled is not None else x, cls_embs)
         if not self.training:
             return x, self.post_processor((class_logits, box_regression), proposals), {}
-        loss_classifier, loss_box_reg = self.loss_evaluator(class_logits, box_regression)
+        loss_classifier, loss_box_reg = self.loss_evaluator(class_logits, box_regression, proposals)
         return x, proposals, dict(loss_classifier=loss_classifier, loss_box_reg=loss_box_reg)
 
 
@@ -478,16 +483,20 @@ class MaskRCNNC4Predictor(nn.Module):
         y = linear_mfma(rows, conv.weight.view(conv.out_channels, -1), conv.bias)
         return y.view(p, h, w, conv.out_channels).permute(0, 3, 1, 2)
 
-    def forward_parts(self, x):
-        """-> (mask logits mu [P,C,M,M], predicted std-dev sigma [P,1,M,M]) for the fused stochastic BCE."""
+    def _upsampled(self, x):
+        """-> (u, conv1x1): u = relu(conv5_mask(x)) in the form of the route taken -- NHWC rows of the split GEMM, or the
+        plain convolution's maps -- and conv1x1(conv, u) = the 1x1 convolution ``conv`` of u (or of ``u.detach()``) as
+        [P, C, 2H, 2W] maps."""
         if self._gemm_ok(x):
             rows, shape = self._upsampled_rows(x)
-            mu = self._rows_conv1x1(rows, shape, self.mask_fcn_logits)
-            sigma = torch.exp(0.5 * self._rows_conv1x1(rows.detach(), shape, self.uncertain_pred)) if self.uncertainty else None
-            return mu, sigma
-        x_ = F.relu(self.conv5_mask(x))
-        mu = self.mask_fcn_logits(x_)
-        sigma = torch.exp(0.5 * self.uncertain_pred(x_.detach())) if self.uncertainty else None
+            return rows, lambda conv, r: self._rows_conv1x1(r, shape, conv)
+        return F.relu(self.conv5_mask(x)), lambda conv, u: conv(u)
+
+    def forward_parts(self, x, with_sigma=True):
+        """-> (mask logits mu [P,C,M,M], predicted std-dev sigma [P,1,M,M] or None) for the fused stochastic BCE."""
+        u, conv1x1 = self._upsampled(x)
+        mu = conv1x1(self.mask_fcn_logits, u)
+        sigma = torch.exp(0.5 * conv1x1(self.uncertain_pred, u.detach())) if (self.uncertainty and with_sigma) else None
         return mu, sigma
 
     def forward(self, x, compute_uncertain=False, eps=None):
@@ -495,23 +504,15 @@ class MaskRCNNC4Predictor(nn.Module):
         ``mask_logits*0+scale``, i.e. independently per logit channel, roi_mask_predictors.py:47-53,62)
         can be injected for reproducible tests; by default it is drawn on the device (the reference
         draws on the host and copies)."""
-        if self._gemm_ok(x):
-            rows, shape = self._upsampled_rows(x)
-            mask_logits = self._rows_conv1x1(rows, shape, self.mask_fcn_logits)
-            unc = (lambda: self._rows_conv1x1(rows.detach(), shape, self.uncertain_pred))
-        else:
-            x_ = F.relu(self.conv5_mask(x))
-            mask_logits = self.mask_fcn_logits(x_)
-            unc = (lambda: self.uncertain_pred(x_.detach()))
-        if self.uncertainty and compute_uncertain:
-            scale = torch.exp(0.5 * unc())  # [P,1,M,M] std-dev
-            if self.training:
-                std = mask_logits * 0.0 + scale  # [P,C,M,M]
-                if eps is None:
-                    eps = torch.randn((1, *std.shape), device=std.device, dtype=std.dtype)
-                mask_logits = mask_logits[None] + eps * std[None]  # [1,P,C,M,M]
-            return mask_logits, scale
-        return mask_logits
+        mask_logits, scale = self.forward_parts(x, compute_uncertain)  # scale [P,1,M,M] std-dev
+        if scale is None:
+            return mask_logits
+        if self.training:
+            std = mask_logits * 0.0 + scale  # [P,C,M,M]
+            if eps is None:
+                eps = torch.randn((1, *std.shape), device=std.device, dtype=std.dtype)
+            mask_logits = mask_logits[None] + eps * std[None]  # [1,P,C,M,M]
+        return mask_logits, scale
 
 
 def project_masks_on_boxes(masks, gt_index, boxes, M):
@@ -575,7 +576,7 @@ class MaskRCNNLossComputation:
                 masks.append(torch.empty(0, dtype=torch.float32, device=prop.bbox.device))
                 continue
             gt_masks = tgt.get_field("masks")
-            if getattr(prop, "all_positive", False) and prop.has_field("matched_gt") and prop.bbox.is_cuda:
+            if _all_positive(prop) and prop.has_field("matched_gt") and prop.bbox.is_cuda:
                 # sampled positives of the box head: same thresholds, so the match is the one already made
                 labels.append(prop.get_field("labels"))
                 masks.append(self._project(gt_masks, prop.get_field("matched_gt"), prop.bbox))
@@ -623,13 +624,12 @@ class MaskRCNNLossComputation:
         labels, mask_targets = self.prepare_targets(list(proposals), list(targets))
         labels = _cat(labels, 0)
         mask_targets = _cat([m for m in mask_targets if m.numel() > 0] or mask_targets[:1], 0)
-        if all(getattr(p, "all_positive", False) for p in proposals):
+        if all(_all_positive(p) for p in proposals):
             pos = torch.arange(labels.numel(), device=labels.device)
         else:
             pos = torch.nonzero(labels > 0).squeeze(1)
         if mask_targets.numel() == 0:
             return mu.sum() * 0
-        self.mask_targets, self.positive_inds = mask_targets, pos
         e = None if eps is None else eps.reshape(mu.shape)
         # class-agnostic: every positive reads logit channel 1 (labels_pos * 0 + 1); class-specific: the channel of its
         # label (mask_logits[positive_inds, labels_pos], mask_head/loss.py:131-141) -- an index into the same kernel
@@ -650,7 +650,6 @@ class MaskRCNNLossComputation:
             labels_pos = labels_pos * 0 + 1
         if mask_targets.numel() == 0:
             return mask_logits.sum() * 0
-        self.mask_targets, self.positive_inds = mask_targets, pos
         return F.binary_cross_entropy_with_logits(mask_logits[pos, labels_pos], mask_targets, reduction="none").mean()
 
 
@@ -766,38 +765,31 @@ class ROIMaskHead(nn.Module):
             self.log, self.avg_uncertain = scale.max(), scale.mean()
         else:
             mask_logits = self.predictor(x)
-        if not self.training:
-            prob = mask_logits.sigmoid()
-            if self.cls_agnostic_mask:
-                prob = prob[:, 1][:, None]
-            else:
-                labels = _cat([b.get_field("labels") for b in proposals], 0)
-                prob = prob[torch.arange(prob.shape[0], device=prob.device), labels][:, None]
-            results = []
-            for p, b in zip(prob.split([len(b) for b in proposals], 0), proposals):
-                out = b.copy_with_fields(b.fields())
-                out.add_field("mask", p if self.masker is None else self.masker(p, b))
-                results.append(out)
-            return x, results, {}
-        loss_mask = self.loss_evaluator(proposals, mask_logits, targets)
-        return x, proposals, dict(loss_mask=loss_mask)
+        prob = mask_logits.sigmoid()
+        if self.cls_agnostic_mask:
+            prob = prob[:, 1][:, None]
+        else:
+            labels = _cat([b.get_field("labels") for b in proposals], 0)
+            prob = prob[torch.arange(prob.shape[0], device=prob.device), labels][:, None]
+        results = []
+        for p, b in zip(prob.split([len(b) for b in proposals], 0), proposals):
+            out = b.copy_with_fields(b.fields())
+            out.add_field("mask", p if self.masker is None else self.masker(p, b))
+            results.append(out)
+        return x, results, {}
 
-
-def _mask_fused_training_loss(self, x, proposals, targets, compute_uncertain=False, eps=None):
-    """Training loss of the mask head (class-agnostic or class-specific logits) on the positives' features x (fused
-    stochastic BCE; noise drawn on the device unless injected)."""
-    mu, sigma = self.predictor.forward_parts(x)
-    if compute_uncertain and sigma is not None:
-        self.log, self.avg_uncertain = sigma.max(), sigma.mean()
-        if eps is None:
-            eps = torch.randn((1, *mu.shape), device=mu.device, dtype=mu.dtype)
-        else:  # injected noise (tests): a pool at least as large as the positives
-            eps = eps[:, : mu.shape[0]].to(mu.device)
-        return self.loss_evaluator.fused(proposals, mu, sigma, eps, targets)
-    return self.loss_evaluator.fused(proposals, mu, None, None, targets)
-
-
-ROIMaskHead.fused_training_loss = _mask_fused_training_loss
+    def fused_training_loss(self, x, proposals, targets, compute_uncertain=False, eps=None):
+        """Training loss of the mask head (class-agnostic or class-specific logits) on the positives' features x (fused
+        stochastic BCE; noise drawn on the device unless injected)."""
+        mu, sigma = self.predictor.forward_parts(x)
+        if compute_uncertain and sigma is not None:
+            self.log, self.avg_uncertain = sigma.max(), sigma.mean()
+            if eps is None:
+                eps = torch.randn((1, *mu.shape), device=mu.device, dtype=mu.dtype)
+            else:  # injected noise (tests): a pool at least as large as the positives
+                eps = eps[:, : mu.shape[0]].to(mu.device)
+            return self.loss_evaluator.fused(proposals, mu, sigma, eps, targets)
+        return self.loss_evaluator.fused(proposals, mu, None, None, targets)
 
 
 class CombinedROIHeads(nn.ModuleDict):
@@ -839,10 +831,8 @@ class CombinedROIHeads(nn.ModuleDict):
         counts = [sum(len(p) for p in props) for props in sampled]
         out, off = [], 0
         for br, props, cnt in zip(branches, sampled, counts):
-            box.predictor.set_class_embeddings(br["cls_embs"])
-            class_logits, box_regression = box.predictor(pooled[off:off + cnt])
-            box.loss_evaluator._proposals = props
-            lc, lb = box.loss_evaluator(class_logits, box_regression)
+            class_logits, box_regression = box.predictor(pooled[off:off + cnt], br["cls_embs"])
+            lc, lb = box.loss_evaluator(class_logits, box_regression, props)
             out.append(dict(loss_classifier=lc, loss_box_reg=lb))
             off += cnt
         if self.mask_on:
@@ -868,7 +858,7 @@ class CombinedROIHeads(nn.ModuleDict):
         return out
 
     def forward(self, features, proposals, targets=None, bbox_only=False, compute_uncertain=False, eps=None,
-                is_eval_func=False):
+                is_eval_func=False, cls_embs=None):
         losses, package_x = {}, {}
         # MODEL.GT_BOX_EVAL (roi_heads.py:31-49): the evaluation pass of a detector -- not the teacher's passes inside
         # generate_pseudo_label, which leave ``is_eval_func`` False -- classifies and segments the ground-truth boxes
@@ -880,7 +870,7 @@ class CombinedROIHeads(nn.ModuleDict):
                 det = t.copy_with_fields(["labels"])
                 det.add_field("objectness", t.get_field("labels") * 0.0 + 1.0)
                 proposals.append(det.to(device))
-        x, detections, loss_box = self.box(features, proposals, targets)
+        x, detections, loss_box = self.box(features, proposals, targets, cls_embs)
         if gt_boxes:
             for det, tar in zip(detections, targets):
                 assert len(det) == len(tar), "GT_BOX_EVAL keeps one detection per ground-truth box"

@@ -75,6 +75,10 @@ class BoxList:
             out.add_field(k, v.to(device) if hasattr(v, "to") else v)
         return out
 
+    def device_tensors(self):
+        """What a stream has to be told about (engine/trainer.py::_record_stream): tensors, or holders of tensors."""
+        return [self.bbox, *self.extra_fields.values()]
+
     def area(self):
         b = self.bbox
         return (b[:, 2] - b[:, 0] + TO_REMOVE) * (b[:, 3] - b[:, 1] + TO_REMOVE)
@@ -134,6 +138,26 @@ class BoxList:
         return f"BoxList(num_boxes={len(self)}, image_width={self.size[0]}, image_height={self.size[1]})"
 
 
+class SampledBoxList(BoxList):
+    """A proposal list as the box head's sampler hands it out (roi_heads.py::FastRCNNLossComputation.subsample_many), with
+    what the sampler knows about its positives: ``pos_index`` int64 [npos], the rows whose label is > 0 (None: the
+    tensor-op sampler made the list, ask ``nonzero``), ``all_positive``: every row is a positive, matched to the ground-truth
+    box in its ``matched_gt`` field.  Takes bbox, size and fields from ``boxlist``.  Only ``to`` keeps the type: indexing,
+    ``copy_with_fields`` and ``cat_boxlist`` change the rows, so they yield a plain ``BoxList``."""
+
+    def __init__(self, boxlist, pos_index=None, all_positive=False):
+        super().__init__(boxlist.bbox, boxlist.size)
+        self.extra_fields = dict(boxlist.extra_fields)
+        self.pos_index, self.all_positive = pos_index, all_positive
+
+    def to(self, device):
+        return SampledBoxList(super().to(device), None if self.pos_index is None else self.pos_index.to(device),
+                              self.all_positive)
+
+    def device_tensors(self):
+        return [*super().device_tensors(), self.pos_index]
+
+
 class PastedMasks:
     """Binary instance masks of one image that are DEFINED by per-instance probability maps and boxes through the
     Masker paste (mask_head/inference.py:100-160) -- the pseudo labels' masks (st_generalized_rcnn.py:266-271) -- kept in
@@ -150,6 +174,9 @@ class PastedMasks:
 
     def to(self, device):
         return PastedMasks(self.probs.to(device), self.boxes.to(device), self.image_size, self.threshold, self.padding)
+
+    def device_tensors(self):
+        return [self.probs, self.boxes]
 
     def materialize(self):
         """bool [G, H, W]: what Masker(threshold, padding) pastes."""
@@ -191,6 +218,9 @@ class PolygonMasks:
     def to(self, device):
         return PolygonMasks(None, self.size, (self.coords.to(device), self.polygon_start.to(device),
                                               self.instance_start.to(device)))
+
+    def device_tensors(self):
+        return [self.coords, self.polygon_start, self.instance_start]
 
     def instances(self):
         """Back to the nested-list form: per instance a list of flat float32 polygons (host tensors)."""
@@ -292,6 +322,9 @@ class ImageList:
 
     def to(self, *args, **kwargs):
         return ImageList(self.tensors.to(*args, **kwargs), self.image_sizes)
+
+    def device_tensors(self):
+        return [self.tensors]  # the padded batch to_image_list allocates
 
 
 def to_image_list(tensors, size_divisible=0):
