@@ -1667,3 +1667,143 @@ def sgd_momentum_multi(items, blocks, lr, weight_decay, momentum, apply_weight_d
         rc = _L.ovis_sgd_momentum_multi_f32(items.data_ptr(), blocks.data_ptr(), blocks.size(0), lr, weight_decay, momentum,
                                             int(bool(apply_weight_decay)), _stream())
     _lib.check(rc, "sgd_momentum_multi")
+
+
+# ---- COCO scoring (evaluation/coco/coco_eval.py:315-333 -> pycocotools' COCOeval; csrc/coco_eval.hip) -------------------
+class CocoProblems:
+    """The (image, category) problems of a chunk of images, the table of include/ovis_hip.h: ``table`` HOST int64 [P, 8] =
+    (det_start, det_count, gt_start, gt_count, iou_offset, det_word_start, gt_word_start, words_per_mask).  Kept on the
+    host (the ops check every row against their buffers there: the kernels trust the table) and uploaded once."""
+
+    def __init__(self, table, device):
+        table = torch.as_tensor(table, dtype=torch.int64).reshape(-1, 8).contiguous()
+        if table.is_cuda or bool((table < 0).any()):
+            raise RuntimeError("CocoProblems: a host table of non-negative int64 [P, 8] expected")
+        self.host = table
+        self.pairs = table[:, 1] * table[:, 3]
+        self.max_pairs = int(self.pairs.max()) if len(table) else 0
+        self.max_gts = int(table[:, 3].max()) if len(table) else 0
+        self.iou_numel = int((table[:, 4] + self.pairs).max()) if len(table) else 0
+        self.dev = table.to(device)
+
+    def __len__(self):
+        return self.host.shape[0]
+
+    @classmethod
+    def dense(cls, num_dets, num_gts, device, words=0):
+        """One problem over all rows: its IoU block is the whole [num_dets, num_gts] matrix."""
+        return cls([[0, num_dets, 0, num_gts, 0, 0, 0, words]], device)
+
+    def check(self, what, num_dets, num_gts, iou_numel=None, det_words=None, gt_words=None):
+        t = self.host
+        bad = (t[:, 0] + t[:, 1] > num_dets) | (t[:, 2] + t[:, 3] > num_gts)
+        if iou_numel is not None:
+            bad |= t[:, 4] + self.pairs > iou_numel
+        if det_words is not None:
+            bad |= (t[:, 5] + t[:, 1] * t[:, 7] > det_words) | (t[:, 6] + t[:, 3] * t[:, 7] > gt_words)
+        if bool(bad.any()):
+            raise RuntimeError(f"{what}: problem {int(torch.nonzero(bad)[0])} of the table points outside its buffers")
+
+
+def coco_box_iou(dets, gts, gt_crowd, problems=None):
+    """fp64 IoU of xywh boxes, COCOeval.computeIoU for bbox (``ovis_coco_box_iou_f64``): dets [D, 4], gts [G, 4] fp64,
+    gt_crowd [G] uint8 (a crowd's union is the detection's area).  Without ``problems``: the dense [D, G] matrix; with a
+    ``CocoProblems``: the flat buffer that holds every problem's block.  Bit-identical to the formula in
+    include/ovis_hip.h."""
+    dets, gts = _dev(dets, "dets", torch.float64), _dev(gts, "gts", torch.float64)
+    gt_crowd = _dev(gt_crowd, "gt_crowd", torch.uint8)
+    if dets.dim() != 2 or dets.shape[1] != 4 or gts.dim() != 2 or gts.shape[1] != 4 or gt_crowd.shape != (gts.shape[0],):
+        raise RuntimeError("coco_box_iou: expected dets [D,4], gts [G,4] and gt_crowd [G]")
+    d, g = dets.shape[0], gts.shape[0]
+    dense = problems is None
+    if dense and (d == 0 or g == 0):
+        return torch.empty((d, g), dtype=torch.float64, device=dets.device)
+    if dense:
+        problems = CocoProblems.dense(d, g, dets.device)
+    problems.check("coco_box_iou", d, g)
+    out = torch.zeros((problems.iou_numel,), dtype=torch.float64, device=dets.device)
+    if problems.max_pairs:
+        with _on(dets.device):
+            rc = _L.ovis_coco_box_iou_f64(dets.data_ptr(), gts.data_ptr(), gt_crowd.data_ptr(), problems.dev.data_ptr(),
+                                          len(problems), problems.max_pairs, out.data_ptr(), _stream())
+        _lib.check(rc, "coco_box_iou")
+    return out.view(d, g) if dense else out
+
+
+def coco_pack_masks(masks):
+    """(words int64 [P, ceil(H * W / 64)], areas int64 [P]): bool / uint8 masks [P, H, W] -- what ``paste_masks`` and
+    ``polygons_to_masks`` return -- as bit words (pixel p of the row-major mask = bit p % 64 of word p / 64, the tail
+    zero-filled) and their pixel counts (``ovis_coco_pack_masks_u64``).  The words are stored in int64 tensors."""
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    masks = _dev(masks, "masks", torch.uint8)
+    if masks.dim() != 3:
+        raise RuntimeError("coco_pack_masks: expected masks [P,H,W]")
+    p, pixels = masks.shape[0], masks.shape[1] * masks.shape[2]
+    words = torch.empty((p, (pixels + 63) // 64), dtype=torch.int64, device=masks.device)
+    areas = torch.empty((p,), dtype=torch.int64, device=masks.device)
+    if p == 0 or pixels == 0:
+        return words, areas.zero_()
+    with _on(masks.device):
+        rc = _L.ovis_coco_pack_masks_u64(masks.data_ptr(), p, pixels, words.data_ptr(), areas.data_ptr(), _stream())
+    _lib.check(rc, "coco_pack_masks")
+    return words, areas
+
+
+def coco_mask_iou(det_words, det_areas, gt_words, gt_areas, gt_crowd, problems=None):
+    """fp64 IoU of packed masks, COCOeval.computeIoU for segm (``ovis_coco_mask_iou_f64``): the intersection is the
+    popcount of the ANDed words, the result the ratio of two integers -- exact.  Without ``problems``: det_words [D, Wn],
+    gt_words [G, Wn] -> [D, G]; with a ``CocoProblems``: flat word buffers addressed by the table -> the flat IoU buffer."""
+    det_words, gt_words = _dev(det_words, "det_words", torch.int64), _dev(gt_words, "gt_words", torch.int64)
+    det_areas, gt_areas = _dev(det_areas, "det_areas", torch.int64), _dev(gt_areas, "gt_areas", torch.int64)
+    gt_crowd = _dev(gt_crowd, "gt_crowd", torch.uint8)
+    d, g = det_areas.numel(), gt_areas.numel()
+    if gt_crowd.shape != (g,):
+        raise RuntimeError("coco_mask_iou: expected gt_crowd [G]")
+    dense = problems is None
+    if dense:
+        if det_words.dim() != 2 or gt_words.dim() != 2 or det_words.shape[0] != d or gt_words.shape[0] != g \
+                or det_words.shape[1] != gt_words.shape[1]:
+            raise RuntimeError("coco_mask_iou: expected det_words [D,Wn] and gt_words [G,Wn]")
+        if d == 0 or g == 0:
+            return torch.empty((d, g), dtype=torch.float64, device=det_words.device)
+        problems = CocoProblems.dense(d, g, det_words.device, det_words.shape[1])
+    problems.check("coco_mask_iou", d, g, det_words=det_words.numel(), gt_words=gt_words.numel())
+    out = torch.zeros((problems.iou_numel,), dtype=torch.float64, device=det_words.device)
+    if problems.max_pairs:
+        with _on(det_words.device):
+            rc = _L.ovis_coco_mask_iou_f64(det_words.data_ptr(), det_areas.data_ptr(), gt_words.data_ptr(), gt_areas.data_ptr(),
+                                           gt_crowd.data_ptr(), problems.dev.data_ptr(), len(problems), problems.max_pairs,
+                                           out.data_ptr(), _stream())
+        _lib.check(rc, "coco_mask_iou")
+    return out.view(d, g) if dense else out
+
+
+def coco_match(iou, problems, det_areas, gt_areas, gt_crowd, area_ranges, thresholds):
+    """COCOeval.evaluateImg for every problem, area range and IoU threshold in one launch (``ovis_coco_match``).  iou:
+    the flat fp64 buffer of ``coco_box_iou`` / ``coco_mask_iou`` for the same ``problems``; det_areas [D], gt_areas [G]
+    fp64, gt_crowd [G] uint8, area_ranges [A, 2] and thresholds [T] fp64, all on the device.  -> (dt_match int32
+    [A, T, D]: the matched ground truth's index inside its problem or -1, dt_ignore bool [A, T, D], gt_ignore bool
+    [A, G]).  Rows no problem covers come back as -1 / False."""
+    iou, det_areas, gt_areas = _dev(iou, "iou", torch.float64), _dev(det_areas, "det_areas", torch.float64), \
+        _dev(gt_areas, "gt_areas", torch.float64)
+    gt_crowd = _dev(gt_crowd, "gt_crowd", torch.uint8)
+    area_ranges, thresholds = _dev(area_ranges, "area_ranges", torch.float64), _dev(thresholds, "thresholds", torch.float64)
+    if area_ranges.dim() != 2 or area_ranges.shape[1] != 2 or thresholds.dim() != 1 or gt_crowd.shape != gt_areas.shape \
+            or det_areas.dim() != 1 or gt_areas.dim() != 1 or not area_ranges.numel() or not thresholds.numel():
+        raise RuntimeError("coco_match: expected det_areas [D], gt_areas / gt_crowd [G], area_ranges [A,2], thresholds [T]")
+    d, g, a, t = det_areas.numel(), gt_areas.numel(), area_ranges.shape[0], thresholds.numel()
+    problems.check("coco_match", d, g, iou_numel=iou.numel())
+    dt_match = torch.full((a, t, d), -1, dtype=torch.int32, device=iou.device)
+    dt_ignore = torch.zeros((a, t, d), dtype=torch.bool, device=iou.device)
+    gt_ignore = torch.zeros((a, g), dtype=torch.bool, device=iou.device)
+    if len(problems) == 0:
+        return dt_match, dt_ignore, gt_ignore
+    with _on(iou.device):
+        rc = _L.ovis_coco_match(iou.data_ptr() if iou.numel() else 0, problems.dev.data_ptr(), len(problems), problems.max_gts,
+                                det_areas.data_ptr() if d else 0, gt_areas.data_ptr() if g else 0,
+                                gt_crowd.data_ptr() if g else 0, area_ranges.data_ptr(), a, thresholds.data_ptr(), t, d, g,
+                                dt_match.data_ptr() if d else 0, dt_ignore.data_ptr() if d else 0,
+                                gt_ignore.data_ptr() if g else 0, _stream())
+    _lib.check(rc, "coco_match")
+    return dt_match, dt_ignore, gt_ignore

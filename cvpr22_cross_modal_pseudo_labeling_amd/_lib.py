@@ -100,6 +100,10 @@ SIGNATURES = {
     "ovis_weighted_ce_fwd_bwd_f32": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp]),
     "ovis_mask_bce_stochastic_fwd_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ovis_mask_bce_stochastic_classes_fwd_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ovis_coco_box_iou_f64": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp]),
+    "ovis_coco_pack_masks_u64": (_i, [_vp, _i, _l, _vp, _vp, _vp]),
+    "ovis_coco_mask_iou_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _vp, _vp]),
+    "ovis_coco_match": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _l, _l, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,407 @@
+"""COCO box / mask AP and the seen / unseen AP50 of a prediction list -- the dataset-specific ``evaluate`` the reference
+runs after ``inference`` (maskrcnn_benchmark/data/datasets/evaluation/coco/coco_eval.py: ``prepare_for_coco_detection``
+:71-105, ``prepare_for_coco_segmentation`` :108-162, ``evaluate_predictions_on_coco`` :315-333, ``COCOResults`` :336-414).
+
+The reference hands JSON results to pycocotools' ``COCOeval``; pycocotools is not a dependency here, its rules are restated:
+
+* on the DEVICE (csrc/coco_eval.hip through ``_C``), a chunk of images at a time: the detections' masks are pasted at
+  image size (``_C.paste_masks``) and the polygon ground truth rasterised (``_C.polygons_to_masks``) per image size,
+  packed to bit words, and then three launches cover the whole chunk -- box IoU or mask IoU of every (image, category)
+  problem, and ``COCOeval.evaluateImg``'s matching for every problem, area range and IoU threshold.  Only the match tables
+  come back: 4 x 10 x (an int32 and a flag) per detection.
+* on the HOST, in NumPy fp64: ``COCOeval.accumulate`` and ``summarize`` (``accumulate`` / ``summarize`` below), term by
+  term -- O(detections), not hot.
+
+Chunks are sized by device memory: an image costs (detections + ground truths) x height x width x 9 / 8 bytes (the pasted
+byte masks and their packed words; box scoring costs nothing worth counting), and a chunk takes images in id order until
+a quarter of the memory free at the start is used, or ``MAX_CHUNK_IMAGES``, or until its detections, its ground truths or
+its polygons would exceed ``MAX_CALL_MASKS`` -- the most one ``paste_masks`` / ``polygons_to_masks`` call takes, so the
+per-size calls of a chunk stay inside their callees' limits even when every image has the same size.
+
+Semantics beyond pycocotools' own: images and categories are all those of the annotation file, sorted by id; an image
+without a prediction counts with zero detections; every annotation is ground truth, crowds included (``ignore =
+iscrowd``); a ground truth's ``area`` is the annotation's ``area`` when present, else its box's w * h; an IoU whose union
+is 0 is 0 (pycocotools yields NaN for two zero-area boxes; clipped detections have w, h >= 1).  AR summaries, keypoints
+and ``box_proposal`` recall are not computed.
+"""
+import contextlib
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from .. import _C
+from ..modeling.structures import BoxList, PolygonMasks
+
+IOU_THRESHOLDS = np.linspace(.5, .95, 10)
+RECALL_THRESHOLDS = np.linspace(0, 1, 101)
+MAX_DETS = (1, 10, 100)
+AREA_RANGES = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e10]], dtype=np.float64)  # all, s, m, l
+METRICS = ("AP", "AP50", "AP75", "APs", "APm", "APl")
+MAX_CHUNK_IMAGES = 4096
+MAX_CALL_MASKS = 65535  # what one paste_masks / polygons_to_masks call takes: masks, instances or polygons
+
+
+# ---- host: COCOeval.accumulate / summarize --------------------------------------------------------------------------------
+def accumulate(tables, num_categories):
+    """``COCOeval.accumulate`` -> precision fp64 [T, R, K, A, M] (-1: no image entry or no non-ignored ground truth).
+
+    ``tables``: the match tables of every problem -- (image, category) with a detection or a ground truth -- in image-id
+    order, as plain NumPy arrays: ``category`` int [P] (index into the sorted category ids), ``det_start`` int [P + 1] and
+    ``gt_start`` int [P + 1] (row ranges), ``scores`` f64 [D] (descending and at most 100 inside a problem), ``dt_match``
+    int [A, T, D] (>= 0: matched), ``dt_ignore`` bool [A, T, D], ``gt_ignore`` bool [A, G]."""
+    cat = np.asarray(tables["category"], dtype=np.int64)
+    det_start, gt_start = np.asarray(tables["det_start"], dtype=np.int64), np.asarray(tables["gt_start"], dtype=np.int64)
+    scores_all = np.asarray(tables["scores"], dtype=np.float64)
+    matched_all, dt_ignore_all = np.asarray(tables["dt_match"]) >= 0, np.asarray(tables["dt_ignore"], dtype=bool)
+    gt_ignore_all = np.asarray(tables["gt_ignore"], dtype=bool)
+    det_problem = np.repeat(np.arange(len(cat)), np.diff(det_start))
+    det_rank = np.arange(len(det_problem)) - det_start[:-1][det_problem]
+    det_cat, gt_cat = cat[det_problem], np.repeat(cat, np.diff(gt_start))
+    num_t, num_r, num_a, num_m = len(IOU_THRESHOLDS), len(RECALL_THRESHOLDS), len(AREA_RANGES), len(MAX_DETS)
+    precision = -np.ones((num_t, num_r, num_categories, num_a, num_m))
+    for k in range(num_categories):
+        if not np.any(cat == k):
+            continue
+        dets_k, gts_k = np.nonzero(det_cat == k)[0], gt_cat == k
+        for a in range(num_a):
+            npig = np.count_nonzero(~gt_ignore_all[a][gts_k])
+            if npig == 0:
+                continue
+            for m, max_det in enumerate(MAX_DETS):
+                sel = dets_k[det_rank[dets_k] < max_det]
+                # a stable sort: equal scores stay in image order
+                sel = sel[np.argsort(-scores_all[sel], kind="mergesort")]
+                dtm, dt_ig = matched_all[a][:, sel], dt_ignore_all[a][:, sel]
+                tp_sum = np.cumsum(np.logical_and(dtm, np.logical_not(dt_ig)), axis=1).astype(dtype=np.float64)
+                fp_sum = np.cumsum(np.logical_and(np.logical_not(dtm), np.logical_not(dt_ig)), axis=1).astype(dtype=np.float64)
+                for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+                    nd = len(tp)
+                    rc = tp / npig
+                    pr = tp / (fp + tp + np.spacing(1))
+                    q = np.zeros((num_r,))
+                    if nd:  # the right-to-left envelope: pr[i - 1] = max(pr[i - 1], pr[i])
+                        pr = np.maximum.accumulate(pr[::-1])[::-1]
+                    inds = np.searchsorted(rc, RECALL_THRESHOLDS, side="left")
+                    ok = inds < nd  # a recall point past the last detection keeps precision 0
+                    q[ok] = pr[inds[ok]]
+                    precision[t, :, k, a, m] = q
+    return precision
+
+
+def _mean(s):
+    s = s[s > -1]
+    return float(np.mean(s)) if s.size else -1.0
+
+
+def summarize(precision, category_names, class_splits, class_order=None):
+    """``COCOeval.summarize``'s six AP numbers and ``COCOResults.update``'s per-class / per-split AP50 (coco_eval.py:364-404)
+    -> OrderedDict.  category_names: the name of every category index; class_splits: {split: [category indices]};
+    class_order: the category indices in the order their ``AP50_class_`` keys appear (None: index order)."""
+    m100 = MAX_DETS.index(100)
+    t50, t75 = np.where(.5 == IOU_THRESHOLDS)[0], np.where(.75 == IOU_THRESHOLDS)[0]
+    res = OrderedDict()
+    res["AP"] = _mean(precision[:, :, :, 0, m100])
+    res["AP50"] = _mean(precision[t50][:, :, :, 0, m100])
+    res["AP75"] = _mean(precision[t75][:, :, :, 0, m100])
+    for name, a in (("APs", 1), ("APm", 2), ("APl", 3)):
+        res[name] = _mean(precision[:, :, :, a, m100])
+    s = precision[t50][:, :, :, 0, m100]  # [1, R, K]
+    for k in range(len(category_names)) if class_order is None else class_order:
+        res[f"AP50_class_{category_names[k]}"] = _mean(s[:, :, [k]])
+    for split, cats in class_splits.items():
+        res[f"AP50_split_{split}"] = _mean(s[:, :, list(cats)])
+    return res
+
+
+def format_results(results):
+    """The reference's ``Task: ... / names / values`` table (``COCOResults.__repr__``, coco_eval.py:406-414)."""
+    out = "\n"
+    for task, metrics in results.items():
+        out += "Task: {}\n".format(task)
+        out += ", ".join(metrics.keys()) + "\n"
+        out += ", ".join("{:.4f}".format(v) for v in metrics.values()) + "\n"
+    return out
+
+
+# ---- host: ground truth and detections as rows ----------------------------------------------------------------------------
+def rle_decode(rle, height, width):
+    """uint8 [height, width] of a COCO RLE ``{"counts", "size"}``: column-major runs, zeros first; ``counts`` an
+    uncompressed list or pycocotools' compressed string (``rleFrString``)."""
+    counts = rle["counts"]
+    if list(rle.get("size", [height, width])) != [height, width]:
+        raise ValueError(f"RLE of size {rle.get('size')} on an image of {height} x {width}")
+    if isinstance(counts, (str, bytes)):
+        s = counts.encode("ascii") if isinstance(counts, str) else counts
+        runs, p = [], 0
+        while p < len(s):
+            x, k, more = 0, 0, True
+            while more:
+                c = s[p] - 48
+                x |= (c & 0x1f) << (5 * k)
+                more = bool(c & 0x20)
+                p += 1
+                k += 1
+                if not more and (c & 0x10):
+                    x |= -1 << (5 * k)
+            if len(runs) > 2:
+                x += runs[-2]
+            runs.append(x)
+        counts = runs
+    counts = np.asarray(counts, dtype=np.int64)
+    if counts.ndim != 1 or (counts < 0).any() or int(counts.sum()) != height * width:
+        raise ValueError(f"RLE runs do not add up to {height} x {width} pixels")
+    flat = np.repeat(np.arange(len(counts)) % 2, counts).astype(np.uint8)
+    return np.ascontiguousarray(flat.reshape(width, height).T)
+
+
+def _ground_truth(dataset):
+    """-> (category ids sorted, per image of the file in id order a record of its annotations sorted by category index,
+    stably: annotation order inside a category)."""
+    coco = dataset.coco
+    cat_ids = coco.cat_ids()
+    cat_index = {c: i for i, c in enumerate(cat_ids)}
+    images = []
+    for img_id in sorted(coco.imgs):
+        info = coco.imgs[img_id]
+        anns = [a for a in coco.anns(img_id) if a["category_id"] in cat_index]
+        anns = sorted(anns, key=lambda a: cat_index[a["category_id"]])  # stable
+        boxes = np.asarray([a["bbox"] for a in anns], dtype=np.float64).reshape(-1, 4)
+        images.append({
+            "id": img_id, "width": int(info["width"]), "height": int(info["height"]), "anns": anns, "boxes": boxes,
+            "cats": np.asarray([cat_index[a["category_id"]] for a in anns], dtype=np.int64),
+            "areas": np.asarray([a["area"] if "area" in a else a["bbox"][2] * a["bbox"][3] for a in anns], dtype=np.float64),
+            "crowd": np.asarray([1 if a.get("iscrowd", 0) else 0 for a in anns], dtype=np.uint8),
+            "polygons": sum(len(a["segmentation"]) for a in anns if isinstance(a.get("segmentation"), list))})
+    return cat_ids, images
+
+
+def _detections(pred, image, label_to_cat, with_masks):
+    """One image's prediction as rows sorted by (category index, descending score), stably, at most 100 per category
+    (coco_eval.py:71-105 / :108-162 and the ``dt[0:maxDets[-1]]`` of COCOeval.computeIoU)."""
+    empty = {"cats": np.zeros(0, np.int64), "scores": np.zeros(0), "xywh": np.zeros((0, 4)), "xyxy": None, "maps": None}
+    if pred is None or len(pred) == 0:
+        return empty
+    xyxy = BoxList(pred.bbox.detach().cpu(), pred.size).resize((image["width"], image["height"])).bbox
+    x1, y1, x2, y2 = xyxy.unbind(1)
+    xywh = torch.stack((x1, y1, x2 - x1 + 1, y2 - y1 + 1), 1)  # float32, as BoxList.convert("xywh") of the reference
+    scores = pred.get_field("scores").detach().cpu().double().numpy()
+    cats = np.asarray([label_to_cat[int(l)] for l in pred.get_field("labels").tolist()], dtype=np.int64)
+    order = np.lexsort((-scores, cats))  # stable: ties keep prediction order
+    rank = np.arange(len(order)) - np.searchsorted(cats[order], cats[order], side="left")
+    order = order[rank < MAX_DETS[-1]]
+    out = {"cats": cats[order], "scores": scores[order], "xywh": xywh.double().numpy()[order], "xyxy": None, "maps": None}
+    if with_masks:
+        if not pred.has_field("mask"):
+            raise ValueError("evaluate_coco: segm scoring needs the predictions' 'mask' field (MODEL.MASK_ON)")
+        maps = pred.get_field("mask")
+        if not torch.is_tensor(maps) or not maps.is_floating_point() or maps.dim() != 4 or maps.shape[1] != 1 \
+                or maps.shape[2] != maps.shape[3] or maps.shape[0] != len(pred):
+            raise ValueError(
+                f"evaluate_coco: field 'mask' must hold the mask head's [K, 1, M, M] probability maps, got "
+                f"{getattr(maps, 'dtype', type(maps).__name__)} {tuple(getattr(maps, 'shape', ()))}; masks that are already "
+                "pasted into the image (MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS True) cannot be scored -- run inference with "
+                "MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS False")
+        index = torch.from_numpy(order)
+        out["maps"], out["xyxy"] = maps.detach().cpu()[index, 0].float(), xyxy[index]
+    return out
+
+
+def _chunks(images, dets, with_masks, budget, max_images=None):
+    """Lists of consecutive image indices: a chunk closes before the image that would take it over ``budget`` bytes of
+    masks, over ``max_images`` (None: MAX_CHUNK_IMAGES) or -- for segm -- over MAX_CALL_MASKS detections, ground truths or
+    polygons.  An image that breaks a limit alone still gets its own chunk."""
+    max_images = MAX_CHUNK_IMAGES if max_images is None else max_images
+    chunk, used = [], np.zeros(4, dtype=np.int64)
+    limits = np.asarray([budget, MAX_CALL_MASKS, MAX_CALL_MASKS, MAX_CALL_MASKS], dtype=np.float64)
+    for i, (image, det) in enumerate(zip(images, dets)):
+        n_det, n_gt = len(det["cats"]), len(image["cats"])
+        cost = np.asarray([(n_det + n_gt) * image["height"] * image["width"] * 9 // 8, n_det, n_gt, image["polygons"]],
+                          dtype=np.int64) * (1 if with_masks else 0)
+        if chunk and (np.any(used + cost > limits) or len(chunk) >= max_images):
+            yield chunk
+            chunk, used = [], np.zeros(4, dtype=np.int64)
+        chunk.append(i)
+        used = used + cost
+    if chunk:
+        yield chunk
+
+
+@contextlib.contextmanager
+def _stage(timer, name):
+    """Device events around a stage when ``timer`` (a dict name -> list of (start, end)) is given."""
+    if timer is None:
+        yield
+        return
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    yield
+    end.record()
+    timer.setdefault(name, []).append((start, end))
+
+
+def _pack_group(group_rows, masks, words_parts, areas_out, base):
+    """Packs one image-size group's masks; -> the word offset behind it."""
+    words, areas = _C.coco_pack_masks(masks)
+    words_parts.append(words.reshape(-1))
+    areas_out[group_rows] = areas
+    return base + words.numel()
+
+
+def score_chunk(images, dets, iou_type, device, timer=None):
+    """The match tables of one chunk of images (the NumPy form ``accumulate`` takes): a constant number of launches --
+    box or mask IoU and the matching -- plus, for segm, the paste, rasterise and pack calls of every image size."""
+    with_masks = iou_type == "segm"
+    rows, det_base, gt_base, iou_off = [], 0, 0, 0
+    det_image_base, gt_image_base = [], []
+    for i, (image, det) in enumerate(zip(images, dets)):
+        det_image_base.append(det_base)
+        gt_image_base.append(gt_base)
+        for c in np.union1d(det["cats"], image["cats"]).tolist():
+            d0, d1 = np.searchsorted(det["cats"], [c, c + 1])
+            g0, g1 = np.searchsorted(image["cats"], [c, c + 1])
+            rows.append([det_base + d0, d1 - d0, gt_base + g0, g1 - g0, iou_off, 0, 0, 0, c, i])
+            iou_off += (d1 - d0) * (g1 - g0)
+        det_base += len(det["cats"])
+        gt_base += len(image["cats"])
+    table = np.asarray(rows, dtype=np.int64).reshape(-1, 10)
+    num_dets, num_gts = det_base, gt_base
+    crowd = torch.from_numpy(np.concatenate([im["crowd"] for im in images] + [np.zeros(0, np.uint8)])).to(device)
+    gt_areas = torch.from_numpy(np.concatenate([im["areas"] for im in images] + [np.zeros(0)])).to(device)
+    scores = np.concatenate([d["scores"] for d in dets] + [np.zeros(0)])
+    if not with_masks:
+        det_xywh = torch.from_numpy(np.concatenate([d["xywh"] for d in dets] + [np.zeros((0, 4))])).to(device)
+        gt_xywh = torch.from_numpy(np.concatenate([im["boxes"] for im in images] + [np.zeros((0, 4))])).to(device)
+        problems = _C.CocoProblems(table[:, :8], device)
+        with _stage(timer, "iou"):
+            iou = _C.coco_box_iou(det_xywh, gt_xywh, crowd, problems)
+            det_areas = det_xywh[:, 2] * det_xywh[:, 3]
+    else:
+        groups = {}
+        for i, image in enumerate(images):
+            groups.setdefault((image["height"], image["width"]), []).append(i)
+        det_words, gt_words, det_word_base, gt_word_base = [], [], 0, 0
+        det_areas_i = torch.zeros(num_dets, dtype=torch.int64, device=device)
+        gt_areas_i = torch.zeros(num_gts, dtype=torch.int64, device=device)
+        image_words = {}  # image -> (first det word, first gt word, words per mask)
+        for (height, width), members in groups.items():
+            nwords = (height * width + 63) // 64
+            det_rows = np.concatenate([np.arange(len(dets[i]["cats"])) + det_image_base[i] for i in members])
+            gt_rows = np.concatenate([np.arange(len(images[i]["cats"])) + gt_image_base[i] for i in members])
+            d_off, g_off = det_word_base, gt_word_base
+            for i in members:
+                image_words[i] = (d_off, g_off, nwords)
+                d_off += len(dets[i]["cats"]) * nwords
+                g_off += len(images[i]["cats"]) * nwords
+            if len(det_rows):
+                maps = torch.cat([dets[i]["maps"] for i in members if len(dets[i]["cats"])]).to(device)
+                boxes = torch.cat([dets[i]["xyxy"] for i in members if len(dets[i]["cats"])]).to(device)
+                with _stage(timer, "paste"):
+                    pasted = _C.paste_masks(maps, boxes, (height, width))
+                with _stage(timer, "pack"):
+                    det_word_base = _pack_group(torch.from_numpy(det_rows).to(device), pasted, det_words,
+                                                det_areas_i, det_word_base)
+                del pasted
+            if len(gt_rows):
+                anns = [a for i in members for a in images[i]["anns"]]
+                for a in anns:
+                    if "segmentation" not in a:
+                        raise ValueError(f"evaluate_coco: annotation {a.get('id')} has no 'segmentation' (segm scoring)")
+                polygons = PolygonMasks([[] if isinstance(a["segmentation"], dict) else a["segmentation"] for a in anns],
+                                        (width, height)).to(device)
+                with _stage(timer, "rasterise"):
+                    masks = polygons.convert_to_binarymask()
+                rle_rows = [r for r, a in enumerate(anns) if isinstance(a["segmentation"], dict)]
+                if rle_rows:  # decoded on the host and uploaded
+                    decoded = np.stack([rle_decode(anns[r]["segmentation"], height, width) for r in rle_rows])
+                    masks[torch.tensor(rle_rows, device=device)] = torch.from_numpy(decoded).to(device)
+                with _stage(timer, "pack"):
+                    gt_word_base = _pack_group(torch.from_numpy(gt_rows).to(device), masks, gt_words, gt_areas_i,
+                                               gt_word_base)
+                del masks
+        if len(table):  # the word columns of every problem, from its image's share of the word buffers
+            img = table[:, 9]
+            first = np.asarray([image_words[i] for i in range(len(images))], dtype=np.int64).reshape(-1, 3)
+            table[:, 7] = first[img, 2]
+            table[:, 5] = first[img, 0] + (table[:, 0] - np.asarray(det_image_base)[img]) * table[:, 7]
+            table[:, 6] = first[img, 1] + (table[:, 2] - np.asarray(gt_image_base)[img]) * table[:, 7]
+        problems = _C.CocoProblems(table[:, :8], device)
+        empty = torch.zeros(0, dtype=torch.int64, device=device)
+        with _stage(timer, "iou"):
+            iou = _C.coco_mask_iou(torch.cat(det_words) if det_words else empty, det_areas_i,
+                                   torch.cat(gt_words) if gt_words else empty, gt_areas_i, crowd, problems)
+        det_areas = det_areas_i.double()
+    thresholds = torch.from_numpy(IOU_THRESHOLDS).to(device)
+    area_ranges = torch.from_numpy(AREA_RANGES).to(device)
+    with _stage(timer, "match"):
+        dt_match, dt_ignore, gt_ignore = _C.coco_match(iou, problems, det_areas, gt_areas, crowd, area_ranges, thresholds)
+    return {"category": table[:, 8].copy(),
+            "det_start": np.concatenate([table[:, 0], [num_dets]]), "gt_start": np.concatenate([table[:, 2], [num_gts]]),
+            "scores": scores, "dt_match": dt_match.cpu().numpy(), "dt_ignore": dt_ignore.cpu().numpy(),
+            "gt_ignore": gt_ignore.cpu().numpy()}
+
+
+def concatenate_tables(parts):
+    """The match tables of consecutive chunks as one."""
+    det_off, gt_off, det_start, gt_start = 0, 0, [], []
+    for p in parts:
+        det_start.append(p["det_start"][:-1] + det_off)
+        gt_start.append(p["gt_start"][:-1] + gt_off)
+        det_off += p["det_start"][-1]
+        gt_off += p["gt_start"][-1]
+    num_a, num_t = len(AREA_RANGES), len(IOU_THRESHOLDS)
+    return {"category": np.concatenate([p["category"] for p in parts] + [np.zeros(0, np.int64)]),
+            "det_start": np.concatenate(det_start + [np.asarray([det_off], dtype=np.int64)]),
+            "gt_start": np.concatenate(gt_start + [np.asarray([gt_off], dtype=np.int64)]),
+            "scores": np.concatenate([p["scores"] for p in parts] + [np.zeros(0)]),
+            "dt_match": np.concatenate([p["dt_match"] for p in parts] + [np.zeros((num_a, num_t, 0), np.int32)], axis=2),
+            "dt_ignore": np.concatenate([p["dt_ignore"] for p in parts] + [np.zeros((num_a, num_t, 0), bool)], axis=2),
+            "gt_ignore": np.concatenate([p["gt_ignore"] for p in parts] + [np.zeros((num_a, 0), bool)], axis=1)}
+
+
+def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None):
+    """-> (the match tables of every (image, category) problem of the annotation file, in image-id order; the sorted
+    category ids).  ``budget``: the bytes of device memory a chunk may plan with (None: a quarter of what is free);
+    ``max_images``: the most images of a chunk (None: MAX_CHUNK_IMAGES); ``ground_truth``: ``_ground_truth(dataset)`` when
+    the caller already has it."""
+    if iou_type not in ("bbox", "segm"):
+        raise ValueError(f"evaluate_coco: iou_type '{iou_type}' is not supported (bbox, segm)")
+    if len(predictions) > len(dataset):
+        raise ValueError(f"evaluate_coco: {len(predictions)} predictions for a dataset of {len(dataset)} images")
+    device = torch.device(device)
+    cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset)
+    cat_index = {c: i for i, c in enumerate(cat_ids)}
+    label_to_cat = {label: cat_index[json_id] for label, json_id in dataset.contiguous_category_id_to_json_id.items()}
+    by_image = {dataset.id_to_img_map[idx]: pred for idx, pred in enumerate(predictions)}
+    with_masks = iou_type == "segm"
+    dets = [_detections(by_image.get(image["id"]), image, label_to_cat, with_masks) for image in images]
+    if budget is None:
+        budget = torch.cuda.mem_get_info(device)[0] // 4
+    parts = [score_chunk([images[i] for i in chunk], [dets[i] for i in chunk], iou_type, device, timer)
+             for chunk in _chunks(images, dets, with_masks, budget, max_images)]
+    return concatenate_tables(parts), cat_ids
+
+
+def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda"):
+    """{iou_type: OrderedDict of AP, AP50, AP75, APs, APm, APl, AP50_class_<name> per category (in the order of
+    ``dataset.categories``, as ``COCOResults.update`` iterates) and AP50_split_<split> per key of ``dataset.class_splits``}
+    for ``predictions``: the list ``inference()`` returns or ``torch.load`` gives from ``predictions.pth`` (BoxLists in
+    dataset-index order, fields ``scores``, ``labels`` and -- for segm -- ``mask`` [K, 1, M, M]).  ``device``: the HIP
+    device that scores; there is no host-only scoring."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError("evaluate_coco: scoring runs on the HIP device (IoU and matching have no host implementation)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    results = OrderedDict()
+    ground_truth = _ground_truth(dataset)
+    cat_ids = ground_truth[0]
+    cat_index = {c: i for i, c in enumerate(cat_ids)}
+    splits = OrderedDict((split, [cat_index[c] for c in ids]) for split, ids in dataset.class_splits.items())
+    class_order = [cat_index[c] for c in dataset.categories if c in cat_index]
+    with torch.cuda.device(device):
+        for iou_type in iou_types:
+            tables, _ = match_tables(dataset, predictions, iou_type, device, ground_truth=ground_truth)
+            results[iou_type] = summarize(accumulate(tables, len(cat_ids)), [dataset.categories[c] for c in cat_ids], splits,
+                                          class_order)
+    return results

@@ -6,9 +6,10 @@ Counterpart of maskrcnn_benchmark/engine/inference.py:25-47 (``compute_on_datase
 detections are packed into a handful of flat tensors per rank and exchanged with padded tensor all-gathers over the
 process group's own backend (RCCL on the GPUs, gloo on CPU): the payload is never pickled and stays on the device for
 the NCCL backend (only the field names / trailing shapes -- configuration, the same on every rank -- travel as a small
-object, so that a rank without images knows the layout).  Dataset-specific scoring (COCO / LVIS ``evaluate``) needs the
-annotation files and ``pycocotools``, neither of which exists in this build: ``inference`` returns / saves the ordered
-prediction list the reference hands to ``evaluate`` (``predictions.pth``, inference.py:163-164).
+object, so that a rank without images knows the layout).  ``inference`` returns / saves the ordered prediction list the
+reference hands to ``evaluate`` (``predictions.pth``, inference.py:163-164); the dataset-specific scoring of that list is
+``engine/coco_eval.py::evaluate_coco`` (COCO box / mask AP on the device, without ``pycocotools``), which
+``tools/infer_net.py --evaluate`` calls on rank 0.  LVIS scoring is outside this build.
 """
 import logging
 import os

@@ -786,6 +786,48 @@ int ovis_bottleneck_identity_backward(
 int ovis_weight_prep_pair_multi_f32(const void* items, const void* blocks, int num_blocks, int max_taps, void* stream);
 int ovis_weight_prep_tile(void);
 
+/* COCO box / mask AP scoring (csrc/coco_eval.hip): the device half of pycocotools' COCOeval, which the reference calls in
+ * mb/data/datasets/evaluation/coco/coco_eval.py:315-333 on the results of :71-162.  A chunk of images is scored at once.
+ * A PROBLEM is one (image, category) pair with a detection or a ground truth; `problems` is a device table
+ *   int64 [num_problems, 8] = (det_start, det_count, gt_start, gt_count, iou_offset, det_word_start, gt_word_start,
+ *                              words_per_mask)
+ * over the chunk's detection rows (inside a problem: descending score, stable, at most 100 -- COCOeval.evaluateImg's
+ * order), its ground-truth rows (annotation order) and one flat fp64 IoU buffer that holds every problem's
+ * [det_count, gt_count] block at iou_offset.  The last three columns are read by the mask IoU only: offsets in 64-bit
+ * words into det_words / gt_words and the words of one mask of that image.  The kernels do not check the table; the
+ * caller checks it against the buffer sizes on the host.  max_pairs / max_gts: the largest det_count * gt_count /
+ * gt_count of the table (they size the grid; max_gts > 4096: OVIS_ERANGE).  Empty inputs return before any launch.
+ *
+ * ovis_coco_box_iou_f64 (COCOeval.computeIoU, iouType bbox; coco_eval.py:71-105 makes the xywh boxes): dets / gts fp64
+ *   xywh rows;  iw = min(dx+dw, gx+gw) - max(dx, gx) clamped at 0, ih likewise, i = iw*ih,
+ *   u = crowd ? dw*dh : dw*dh + gw*gh - i, iou = i / u in exactly this fp64 operation order (no contraction);
+ *   u == 0 gives 0 (stated deviation: pycocotools yields NaN).
+ * ovis_coco_pack_masks_u64: masks [num, pixels] bytes (the outputs of ovis_paste_masks_u8 / ovis_polygons_to_masks_u8:
+ *   coco_eval.py:108-162 pastes with Masker(0.5, padding=1)) -> words [num, ceil(pixels / 64)], pixel p = bit p % 64 of
+ *   word p / 64, the tail zero-filled, and areas [num] = the number of set pixels (the `area` of a segm result).
+ * ovis_coco_mask_iou_f64 (computeIoU, iouType segm): i = popcount(D & G) as an integer,
+ *   u = crowd ? |D| : |D| + |G| - i, iou = double(i) / double(u), u == 0 gives 0: exact.
+ * ovis_coco_match (COCOeval.evaluateImg): for every problem, each of num_areas area ranges [lo, hi] (area_ranges
+ *   [num_areas, 2] fp64) and each of num_thresholds IoU thresholds (fp64): a ground truth is ignored if it is a crowd or
+ *   its area is < lo or > hi; the detections, in row order, each take -- among the ground truths not yet matched at this
+ *   threshold and not ignored, with iou >= min(t, 1 - 1e-10) -- the one of largest IoU, ties to the later one; when there
+ *   is none, the same among the ignored ones that are unmatched or crowd.  Writes dt_match [num_areas, num_thresholds,
+ *   num_dets] int32 = the matched ground truth's index INSIDE its problem (annotation order) or -1, dt_ignore (same
+ *   shape, u8) = the matched ground truth's ignore flag, or for an unmatched detection whether its own area is outside
+ *   [lo, hi], and gt_ignore [num_areas, num_gts] u8.  Every row that belongs to a problem is written; deterministic, no
+ *   atomics.  det_areas / gt_areas fp64, gt_crowd u8.  iou may be NULL when no problem of the table has both a detection
+ *   and a ground truth (the IoU buffer is empty then and is not read). */
+int ovis_coco_box_iou_f64(const double* dets, const double* gts, const uint8_t* gt_crowd, const int64_t* problems,
+                          int num_problems, long max_pairs, double* iou, void* stream);
+int ovis_coco_pack_masks_u64(const uint8_t* masks, int num, long pixels, uint64_t* words, int64_t* areas, void* stream);
+int ovis_coco_mask_iou_f64(const uint64_t* det_words, const int64_t* det_areas, const uint64_t* gt_words,
+                           const int64_t* gt_areas, const uint8_t* gt_crowd, const int64_t* problems, int num_problems,
+                           long max_pairs, double* iou, void* stream);
+int ovis_coco_match(const double* iou, const int64_t* problems, int num_problems, int max_gts, const double* det_areas,
+                    const double* gt_areas, const uint8_t* gt_crowd, const double* area_ranges, int num_areas,
+                    const double* thresholds, int num_thresholds, long num_dets, long num_gts, int32_t* dt_match,
+                    uint8_t* dt_ignore, uint8_t* gt_ignore, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,10 +10,14 @@ embeddings of its own annotation file (maskrcnn_benchmark/engine/inference.py:12
 ``<OUTPUT_DIR>/inference/<name>/predictions.pth``: a list of BoxLists in dataset-index order, at the transformed image
 sizes.  ``--visualize N`` (rank 0) also renders the first N images of every test set -- boxes, filled masks, class names
 (engine/visualize.py; detections scoring above ``--vis-threshold``) on the dataset's own decoded image -- to
-``<OUTPUT_DIR>/inference/<name>/vis/<file stem>.png``.  ``tools/test_net.py`` stays the synthetic-stream tool; the COCO /
-LVIS scoring of ``evaluate`` is outside this build.
+``<OUTPUT_DIR>/inference/<name>/vis/<file stem>.png``.  ``--evaluate`` (rank 0, after the gather) scores every test set
+against its own annotation file on the device (engine/coco_eval.py: COCO box AP, and mask AP when MODEL.MASK_ON, plus AP50
+per class and per seen / unseen split), logs the reference's ``Task: ... / names / values`` table and writes
+``<OUTPUT_DIR>/inference/<name>/coco_results.json``; it needs OUTPUT_DIR and MODEL.DEVICE cuda -- there is no host-only
+scoring.  ``tools/test_net.py`` stays the synthetic-stream tool; LVIS scoring is outside this build.
 """
 import argparse
+import json
 import logging
 import os
 import sys
@@ -30,7 +34,7 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  
 from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem_bn, make_batch, make_embeddings  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, inference, visualize  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, comm, inference, visualize  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
@@ -49,7 +53,17 @@ def save_visualizations(dataset, predictions, folder, count, threshold, device):
         Image.fromarray(picture).save(os.path.join(folder, stem + ".png"))
 
 
-def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5):
+def save_evaluation(dataset, predictions, folder, iou_types, device, logger):
+    """COCO scoring of one test set (engine/coco_eval.py): the table goes to the log, the numbers to
+    ``folder``/coco_results.json as {iou_type: {metric: value}}."""
+    results = coco_eval.evaluate_coco(dataset, predictions, iou_types, device)
+    logger.info(coco_eval.format_results(results))
+    with open(os.path.join(folder, "coco_results.json"), "w") as f:
+        json.dump(results, f, indent=1)
+    return results
+
+
+def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False):
     """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}."""
     transform = build_transforms(cfg, is_train=False)
     results = {}
@@ -65,6 +79,11 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
             batches.close()
         if visualize_count > 0 and out and results[name] is not None:  # rank 0 only: the others got None
             save_visualizations(dataset, results[name], os.path.join(out, "vis"), visualize_count, vis_threshold, device)
+        if evaluate and not out:
+            raise ValueError("run_datasets: evaluate=True writes OUTPUT_DIR/inference/<name>/coco_results.json: set OUTPUT_DIR")
+        if evaluate and results[name] is not None:
+            save_evaluation(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",), device,
+                            logger or logging.getLogger("ovis.inference"))
     return results
 
 
@@ -79,6 +98,9 @@ def main(argv=None):
     parser.add_argument("--visualize", type=int, default=0, metavar="N",
                         help="render the first N images of every test set to OUTPUT_DIR/inference/<name>/vis/ (rank 0)")
     parser.add_argument("--vis-threshold", type=float, default=0.5, metavar="T", help="draw detections scoring above T")
+    parser.add_argument("--evaluate", action="store_true",
+                        help="score every test set on the device (COCO box / mask AP, AP50 per class and split) and write "
+                             "OUTPUT_DIR/inference/<name>/coco_results.json (rank 0)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args(argv)
 
@@ -90,6 +112,11 @@ def main(argv=None):
     cfg.freeze()
     if args.visualize > 0 and not cfg.OUTPUT_DIR:
         parser.error("--visualize writes under OUTPUT_DIR/inference/<name>/vis/: set OUTPUT_DIR")
+    if args.evaluate and not cfg.OUTPUT_DIR:
+        parser.error("--evaluate writes OUTPUT_DIR/inference/<name>/coco_results.json: set OUTPUT_DIR")
+    if args.evaluate and cfg.MODEL.DEVICE != "cuda":
+        parser.error("--evaluate scores on the HIP device (mask IoU and matching have no host implementation): "
+                     "set MODEL.DEVICE cuda")
     device = torch.device(cfg.MODEL.DEVICE, args.local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
@@ -112,7 +139,8 @@ def main(argv=None):
         calibrate_stem_bn(model, images)  # random init only: give the frozen BN usable statistics
     _, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
     model.set_class_embeddings(e_seen)  # stands until a dataset brings its own (DATASETS.DATASET_ARGS.LOAD_EMBEDDINGS)
-    for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold).items():
+    for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
+                                    args.evaluate).items():
         if preds is not None:
             logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:
