@@ -32,8 +32,8 @@ def synchronize():
 
 def broadcast_parameters(model, src=0):
     """Initial parameter + buffer broadcast (the DDP constructor's job in the reference).  The tensors themselves are
-    written (not ``t.data``, which carries its own version counter), so every cache keyed on ``_version`` -- folded
-    FrozenBN weights, pair-layout weight forms -- sees the new values."""
+    written (not ``t.data``, which carries its own version counter), so every value derived from them -- folded
+    FrozenBN weights, pair-layout weight forms: layers/derived.py -- is rebuilt from the new values."""
     if get_world_size() == 1:
         return
     with torch.no_grad():

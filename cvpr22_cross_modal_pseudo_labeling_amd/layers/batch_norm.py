@@ -7,6 +7,8 @@ memory-bound pass."""
 import torch
 from torch import nn
 
+from .derived import derived
+
 
 class FrozenBatchNorm2d(nn.Module):
     def __init__(self, n):
@@ -16,21 +18,17 @@ class FrozenBatchNorm2d(nn.Module):
         self.register_buffer("running_mean", torch.zeros(n))
         self.register_buffer("running_var", torch.ones(n))
 
-    def fold_key(self):
-        """Identity + version of the four buffers: what any cache of a value derived from ``fold()`` must be keyed on."""
-        return tuple((id(b), b._version) for b in (self.weight, self.bias, self.running_mean, self.running_var))
+    def sources(self):
+        """The four buffers: the sources of ``fold()`` and of every value derived from it (layers/derived.py)."""
+        return tuple(self._buffers.values())  # weight, bias, running_mean, running_var
 
     def fold(self):
-        # the four buffers are constants of the step: the pair is computed once per buffer state (in-place updates such
-        # as load_state_dict bump the version counters, .to() replaces the tensors)
-        key = self.fold_key()
-        cached = getattr(self, "_fold_cache", None)
-        if cached is not None and cached[0] == key:
-            return cached[1], cached[2]
+        # computed once per state of the buffers: the SAME two tensors until then (``WeightPrepPlan.lookup`` compares by identity)
+        return derived(self.sources(), "fold", self._fold)
+
+    def _fold(self):
         scale = self.weight * self.running_var.rsqrt()
-        shift = self.bias - self.running_mean * scale
-        self._fold_cache = (key, scale, shift)
-        return scale, shift
+        return scale, self.bias - self.running_mean * scale
 
     def forward(self, x):
         scale, shift = self.fold()

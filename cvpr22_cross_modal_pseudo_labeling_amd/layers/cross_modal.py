@@ -12,6 +12,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _C
+from .derived import derived
 
 
 class _LinearMFMA(Function):
@@ -32,35 +33,20 @@ class _LinearMFMA(Function):
         return dx, dw, db
 
 
-_PAIR_WEIGHT_CACHE = {}
-
-
 def _pair_weight_padded(weight, n_pad, transposed=False):
     """[N, K] f32 -> pair layout [n_pad, 2K] (zero rows behind N), or of its transpose [K, 2 * n_pad] (the data-gradient
-    operand); cached for tensors that do not require grad (the class / vocabulary matrices, frozen emb_pred), keyed on
-    identity + version."""
-    import torch.nn.functional as F
-    frozen = not weight.requires_grad
-    slot = (id(weight), transposed)
-    key = (id(weight), weight._version, weight.device, n_pad, transposed)
-    if frozen:
-        hit = _PAIR_WEIGHT_CACHE.get(slot)
-        if hit is not None and hit[0] == key and hit[1]() is weight:
-            return hit[2]
-    w = weight.detach()
-    if transposed:
-        w = w.t()
-        if w.shape[1] != n_pad:
-            w = F.pad(w, (0, n_pad - w.shape[1]))
-    elif w.shape[0] != n_pad:
-        w = F.pad(w, (0, 0, 0, n_pad - w.shape[0]))
-    wp = _C.split_pair(w.contiguous())
-    if frozen:
-        import weakref
-        if len(_PAIR_WEIGHT_CACHE) > 64:
-            _PAIR_WEIGHT_CACHE.clear()
-        _PAIR_WEIGHT_CACHE[slot] = (key, weakref.ref(weight), wp)
-    return wp
+    operand); computed once for a tensor that does not require grad (the class / vocabulary matrices, frozen emb_pred)."""
+    def build():
+        import torch.nn.functional as F
+        w = weight.detach()
+        if transposed:
+            w = w.t()
+            if w.shape[1] != n_pad:
+                w = F.pad(w, (0, n_pad - w.shape[1]))
+        elif w.shape[0] != n_pad:
+            w = F.pad(w, (0, 0, 0, n_pad - w.shape[0]))
+        return _C.split_pair(w.contiguous())
+    return derived((weight,), ("pair", n_pad, transposed), build)
 
 
 class _LinearPair(Function):

@@ -27,6 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..layers import Conv2d, DFConv2d, FrozenBatchNorm2d
+from ..layers.derived import derived
 from ..layers.pair_bottleneck import BlockResult, PairWeights, bottleneck_pair, is_placeholder, pair_weight
 
 
@@ -43,19 +44,15 @@ class ConvBN(nn.Module):
         super().__init__()
         self.conv = conv
         self.bn = bn
-        self._cache = None
 
     def folded(self):
         w = self.conv.weight
-        frozen = not w.requires_grad
-        key = (id(w), w._version, w.device) + self.bn.fold_key()  # the FrozenBN buffers are part of the folded weight
-        if frozen and self._cache is not None and self._cache[0] == key:
-            return self._cache[1], self._cache[2]
-        scale, shift = self.bn.fold()
-        fw = w * scale.reshape(-1, 1, 1, 1)
-        if frozen:
-            self._cache = (key, fw.detach(), shift.detach())
-        return fw, shift
+
+        def fold():
+            scale, shift = self.bn.fold()
+            fw = w * scale.reshape(-1, 1, 1, 1)
+            return (fw, shift) if w.requires_grad else (fw.detach(), shift.detach())
+        return derived((w,) + self.bn.sources(), "folded", fold)  # the FrozenBN buffers are part of the folded weight
 
     def forward(self, x):
         w, b = self.folded()
@@ -107,7 +104,6 @@ class Bottleneck(nn.Module):
         # a block that hands its result on in pair layout (want_pair) does not also write it as fp32: the next block
         # takes its identity shortcut from the pair form (hi + lo).  False = fp32 + pair (cross-check in the tests)
         self.pair_only_chain = True
-        self._pair_cache = None
 
     def forward(self, x):
         out = F.relu_(self._f1[0](x))
@@ -174,22 +170,19 @@ class Bottleneck(nn.Module):
     def _pair_node(self, x2d, xp, r, hs, ws, want_pair, pool, select=None, pair_only=False, pool_only_ok=False):
         # RAW weights + folded FrozenBN (scale, shift) pairs: the fold itself happens inside the node's weight-prep kernel
         w1, w2, w3 = self.conv1.weight, self.conv2.weight, self.conv3.weight
-        (s1, b1), (s2, b2), (s3, b3) = self.bn1.fold(), self.bn2.fold(), self.bn3.fold()
-        wd = sd = bd = None
-        if self.downsample is not None:
-            wd = self.downsample[0].weight
-            sd, bd = self.downsample[1].fold()
-        ws_all = [t for t in (w1, w2, w3, wd) if t is not None]
-        bns = [self.bn1, self.bn2, self.bn3] + ([self.downsample[1]] if self.downsample is not None else [])
-        weights = None
-        if not any(t.requires_grad for t in ws_all):
-            # frozen block: the pair forms of the folded weights (and the summed shift) are computed once
-            key = tuple((id(t), t._version, t.device) for t in ws_all) + tuple(k for bn in bns for k in bn.fold_key())
-            if self._pair_cache is None or self._pair_cache[0] != key:
-                self._pair_cache = (key, PairWeights.prepare(w1, s1, w2, s2, w3, s3, wd, sd, False),
-                                    (b3 if bd is None else b3 + bd).contiguous())
-            weights, b3s = self._pair_cache[1], self._pair_cache[2]
+        wd = self.downsample[0].weight if self.downsample is not None else None
+        convs = [w1, w2, w3] + ([wd] if wd is not None else [])
+        bns = [self.bn1, self.bn2, self.bn3] + ([self.downsample[1]] if wd is not None else [])
+        if not any(t.requires_grad for t in convs):
+            def operands():  # frozen block: the folds, the pair forms of the folded weights and the summed shift, computed once
+                folds = ([bn.fold() for bn in bns] + [(None, None)])[:4]
+                (s1, _), (s2, _), (s3, b3), (sd, bd) = folds
+                return folds, PairWeights.prepare(w1, s1, w2, s2, w3, s3, wd, sd, False), (b3 if bd is None else b3 + bd).contiguous()
+            folds, weights, b3s = derived(convs + [b for bn in bns for b in bn.sources()], "pair", operands)
         else:
+            folds, weights = ([bn.fold() for bn in bns] + [(None, None)])[:4], None  # (an identity block has no shortcut FrozenBN)
+        (s1, b1), (s2, b2), (s3, b3), (sd, bd) = folds
+        if weights is None:
             b3s = b3 if bd is None else b3 + bd
             plan = self.__dict__.get("_prep_plan")  # trainable block: operands prepared behind the optimizer step, if still fresh
             if plan is not None:
@@ -260,19 +253,19 @@ class Stem(nn.Module):
         split GEMM with the FrozenBN shift and the ReLU in its epilogue, max-pool on the NHWC result.  Returns the
         channels_last view [N, 64, H/4, W/4] (MIOpen's fp32 kernel for this 3-channel convolution runs at 6 TFLOP/s)."""
         from .. import _C
-        w, b = self._f[0].folded()
         c = self.conv1
-        key = (id(w), w._version) + self.bn1.fold_key()
-        if getattr(self, "_wp", None) is None or self._wp[0] != key:
-            k = w.shape[1] * w.shape[2] * w.shape[3]
-            kp = -(-k // 32) * 32
-            wm = w.new_zeros((w.shape[0], kp))
-            wm[:, :k] = w.permute(0, 2, 3, 1).reshape(w.shape[0], k)   # k = (ky*KW + kx)*C + c
-            self._wp = (key, pair_weight(wm))
+        wp, b = derived((c.weight,) + self.bn1.sources(), "stem_gemm", self._gemm_operands)
         rows, (ho, wo) = _C.im2col_nchw_pair(x.contiguous(), c.kernel_size[0], c.kernel_size[1], c.stride[0], c.padding[0])
-        y, _ = _C.split_gemm_pair(rows, self._wp[1], b, None, True)
+        y, _ = _C.split_gemm_pair(rows, wp, b, None, True)
         y = y.view(x.shape[0], ho, wo, -1).permute(0, 3, 1, 2)          # NCHW view of NHWC memory (channels_last)
         return F.max_pool2d(y, kernel_size=3, stride=2, padding=1)
+
+    def _gemm_operands(self):
+        w, b = self._f[0].folded()
+        k = w.shape[1] * w.shape[2] * w.shape[3]
+        wm = w.new_zeros((w.shape[0], -(-k // 32) * 32))
+        wm[:, :k] = w.permute(0, 2, 3, 1).reshape(w.shape[0], k)   # k = (ky*KW + kx)*C + c
+        return pair_weight(wm), b
 
     def gemm_supported(self, x):
         c = self.conv1

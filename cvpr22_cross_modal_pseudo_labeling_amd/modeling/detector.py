@@ -25,6 +25,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import _C
+from ..layers.derived import derived
 from .backbone import Backbone
 from .roi_heads import CombinedROIHeads, Masker
 from .rpn import RPNModule
@@ -157,17 +158,8 @@ class STGeneralizedRCNN(nn.Module):
         return self.cap_embs[target.get_field("ids_cap")]
 
     def combine_embs(self, embs):
-        # exemplar bank is empty (see module docstring) -> st_generalized_rcnn.py:165-166.  The matrices are constants of
-        # the run: the normalised form is computed once per (tensor, version), so the predictor's operand caches hit
-        key = (id(embs), embs._version, embs.device)
-        cache = self.__dict__.setdefault("_combined", {})
-        hit = cache.get(id(embs))
-        if hit is None or hit[0] != key or hit[1] is not embs:
-            if len(cache) > 8:
-                cache.clear()
-            hit = (key, embs, F.normalize(embs, dim=-1))
-            cache[id(embs)] = hit
-        return hit[2]
+        # exemplar bank is empty (see module docstring) -> st_generalized_rcnn.py:165-166; once per matrix, so its pair form is too
+        return derived((embs,), "normalized", lambda: F.normalize(embs, dim=-1))
 
     def prepare_text(self):
         if self.cap_vocab is not None:

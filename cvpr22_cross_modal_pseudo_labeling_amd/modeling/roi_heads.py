@@ -25,6 +25,7 @@ from torch import nn
 from .. import _C
 from ..layers import (Conv2d, ConvTranspose2d, ROIAlign, linear_mfma, smooth_l1_loss, smooth_l1_picked, stochastic_mask_bce,
                       text_logits, weighted_cross_entropy)
+from ..layers.derived import derived
 from .backbone import HeadFeatures, ResNetHead
 from .box_coder import BoxCoder
 from .matcher import BalancedPositiveNegativeSampler, Matcher
@@ -143,9 +144,12 @@ class FastRCNNPredictor(nn.Module):
         n1 = first.out_features
         n = n1 + self.bbox_pred.out_features
         pad = (-n) % 128 if x.is_cuda else 0
-        zw, zb = self._zero_rows(pad, x)
-        w = torch.cat([first.weight, self.bbox_pred.weight] + ([zw] if pad else []), 0)
-        b = torch.cat([first.bias, self.bbox_pred.bias] + ([zb] if pad else []), 0)
+
+        def concatenated():  # a frozen predictor's is built once, so the pair form of that stable tensor is too (layers/derived.py)
+            zw, zb = self._zero_rows(pad, x)
+            return (torch.cat([first.weight, self.bbox_pred.weight] + ([zw] if pad else []), 0),
+                    torch.cat([first.bias, self.bbox_pred.bias] + ([zb] if pad else []), 0))
+        w, b = derived((first.weight, first.bias, self.bbox_pred.weight, self.bbox_pred.bias), ("predictor", pad), concatenated)
         y = linear_mfma(x, w, b)
         head, bbox = y[:, :n1], y[:, n1:n]
         if not self.embedding_based:

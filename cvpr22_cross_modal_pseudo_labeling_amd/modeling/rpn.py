@@ -10,6 +10,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..layers import smooth_l1_loss
+from ..layers.derived import derived
 from .box_coder import BoxCoder
 from .matcher import BalancedPositiveNegativeSampler, Matcher
 from .structures import BoxList, box_iou, boxlist_nms, cat_boxlist, remove_small_boxes
@@ -109,8 +110,7 @@ class RPNHead(nn.Module):  # rpn.py:74-106
         if self._gemm_ok(feature):
             return self._forward_gemm(feature)
         c = self.conv
-        if (feature.is_cuda and c.in_channels % 128 == 0 and c.out_channels % 128 == 0 and c.kernel_size == (3, 3)
-                and c.padding == (1, 1) and c.stride == (1, 1) and self.split_gemm):
+        if feature.is_cuda and self._split_gemm_shape(128):
             # trainable head (teacher configuration): the 3x3 through the split-GEMM autograd node, the two small 1x1
             # predictors as linear maps of its NHWC rows (layers/cross_modal.py::linear_mfma: the 60-channel box
             # predictor on the split GEMM, the 15-channel objectness on the exact-fp32 MFMA GEMM) -- no library
@@ -131,46 +131,46 @@ class RPNHead(nn.Module):  # rpn.py:74-106
     def prep_plan_convs(self):
         """[(weight, scale)] for ``modeling/backbone.py::prepare_weights_ahead``: the trainable 3x3 on the split GEMM."""
         c = self.conv
-        if (self.split_gemm and c.weight.requires_grad and c.weight.is_cuda and c.in_channels % 128 == 0
-                and c.out_channels % 128 == 0 and c.kernel_size == (3, 3) and c.padding == (1, 1) and c.stride == (1, 1)):
+        if c.weight.requires_grad and c.weight.is_cuda and self._split_gemm_shape(128):
             return [(c.weight, None)]
         return None
 
-    def _gemm_ok(self, feature):
+    def _split_gemm_shape(self, multiple):
+        """A "same" stride-1 3x3 with channel counts divisible by ``multiple`` (the no-grad product: 32, the autograd node: 128)."""
         c = self.conv
+        return (self.split_gemm and c.in_channels % multiple == 0 and c.out_channels % multiple == 0
+                and c.kernel_size == (3, 3) and c.padding == (1, 1) and c.stride == (1, 1))
+
+    def _gemm_ok(self, feature):
         no_grad = not torch.is_grad_enabled() or not (feature.requires_grad or any(p.requires_grad for p in self.parameters()))
-        return (feature.is_cuda and no_grad and c.in_channels % 32 == 0 and c.out_channels % 32 == 0
-                and c.kernel_size == (3, 3) and c.padding == (1, 1) and c.stride == (1, 1) and self.split_gemm)
+        return feature.is_cuda and no_grad and self._split_gemm_shape(32)
 
     def _forward_gemm(self, feature):
-        """Frozen head on the split GEMM (csrc/split_gemm.hip): the 3x3 as an implicit GEMM with bias + ReLU in the
-        epilogue and its result only in pair layout, the two 1x1 predictors as ONE GEMM over the concatenated (zero-
+        """Head outside a graph on the split GEMM (csrc/split_gemm.hip): the 3x3 as an implicit GEMM with bias + ReLU in
+        the epilogue and its result only in pair layout, the two 1x1 predictors as ONE GEMM over the concatenated (zero-
         padded) weight; returns NCHW views of the NHWC result.  MIOpen's fp32 Winograd kernel for the 3x3
-        (1024 -> 1024 on 50x84) takes 1.6 ms per batch."""
+        (1024 -> 1024 on 50x84) takes 1.6 ms per batch.  Only a frozen head keeps its operands (layers/derived.py)."""
         from .. import _C
-        from ..layers.pair_bottleneck import conv_weight_matrix, pair_weight
         n, c, h, w = feature.shape
-        ws = (self.conv.weight, self.conv.bias, self.cls_logits.weight, self.cls_logits.bias, self.bbox_pred.weight,
-              self.bbox_pred.bias)
-        key = tuple((id(t), t._version) for t in ws)
-        if getattr(self, "_gemm_cache", None) is None or self._gemm_cache[0] != key:
-            a = self.cls_logits.out_channels
-            n11 = -(-(5 * a) // 4) * 4
-            w11 = feature.new_zeros((n11, c))
-            b11 = feature.new_zeros((n11,))
-            w11[:a] = self.cls_logits.weight.detach().view(a, c)
-            w11[a:5 * a] = self.bbox_pred.weight.detach().view(4 * a, c)
-            b11[:a] = self.cls_logits.bias.detach()
-            b11[a:5 * a] = self.bbox_pred.bias.detach()
-            self._gemm_cache = (key, pair_weight(conv_weight_matrix(self.conv.weight.detach())),
-                                self.conv.bias.detach().contiguous(), pair_weight(w11), b11)
-        _, w3p, b3, w11p, b11 = self._gemm_cache
+        w3p, b3, w11p, b11 = derived(tuple(self.parameters()), "rpn_gemm", self._gemm_operands)  # the six tensors
         a = self.cls_logits.out_channels
         xp = _C.split_pair(feature.detach().permute(0, 2, 3, 1).contiguous().view(-1, c))
         _, tp = _C.split_gemm_pair(xp, w3p, b3, None, True, False, True, conv=(h, w, 3, 3, False))
         y, _ = _C.split_gemm_pair(tp, w11p, b11)
         y = y.view(n, h, w, -1)
         return y[..., :a].permute(0, 3, 1, 2), y[..., a:5 * a].permute(0, 3, 1, 2)
+
+    def _gemm_operands(self):
+        from ..layers.pair_bottleneck import conv_weight_matrix, pair_weight
+        a, c = self.cls_logits.out_channels, self.conv.out_channels
+        n11 = -(-(5 * a) // 4) * 4
+        w11 = self.conv.weight.new_zeros((n11, c))
+        b11 = self.conv.weight.new_zeros((n11,))
+        w11[:a] = self.cls_logits.weight.detach().view(a, c)
+        w11[a:5 * a] = self.bbox_pred.weight.detach().view(4 * a, c)
+        b11[:a] = self.cls_logits.bias.detach()
+        b11[a:5 * a] = self.bbox_pred.bias.detach()
+        return pair_weight(conv_weight_matrix(self.conv.weight.detach())), self.conv.bias.detach().contiguous(), pair_weight(w11), b11
 
 
 def permute_and_flatten(layer, n, a, c, h, w):  # rpn/utils.py
