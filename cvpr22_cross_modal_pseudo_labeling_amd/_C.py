@@ -919,6 +919,11 @@ def _tn_slices(m, n, ch, taps):
 
 
 @functools.lru_cache(maxsize=None)
+def _tn_map_slices(m, n, ch, kh, kw, h, w):
+    return int(_L.ovis_split_gemm_tn_map_slices(m, n, ch, kh, kw, h, w))
+
+
+@functools.lru_cache(maxsize=None)
 def _gemm_f32_ws_bytes(m, n, k):
     return int(_L.ovis_gemm_f32_workspace_bytes(m, n, k))
 
@@ -1153,7 +1158,7 @@ def split_gemm_pair_tn(g_pair, x_pair, conv=None, scale=None, weight_shape=None)
     if m == 0:
         z = torch.zeros((n, kh * kw * ch), dtype=torch.float32, device=dev)
         return z if weight_shape is None else z.new_zeros(weight_shape)
-    slices = _tn_slices(m, n, ch, kh * kw)
+    slices = _tn_slices(m, n, ch, 1) if conv is None else _tn_map_slices(m, n, ch, kh, kw, h, w)
     slabs = torch.empty((slices, n, kh * kw * ch), dtype=torch.float32, device=dev)
     with _on(dev):
         rc = _L.ovis_split_gemm_pair_tn(g_pair.data_ptr(), 2 * g_pair.stride(0), x_pair.data_ptr(), 2 * x_pair.stride(0),

@@ -24,13 +24,23 @@ struct BbPlan {
   int s1, s2, s3;       // K slices of dW1, dW2, dW3
 };
 
-BbPlan bb_plan(long m, int cin, int mid, int kh, int kw, int width, int config) {
+// height <= 0: not known (the workspace query) -- the slabs of dW2 are then sized for the largest slice count any map
+// height could give (only maps of at most 64 pixels have a count of their own: ovis_split_gemm_tn_map_slices).
+BbPlan bb_plan(long m, int cin, int mid, int kh, int kw, int height, int width, int config) {
   BbPlan p;
   const size_t a = ovis_split_gemm_pair_workspace_bytes_ex(m, mid, cin, 0, 1, 1, 0, config);        // g2: N = mid, K = cin
   const size_t b = ovis_split_gemm_pair_workspace_bytes_ex(m, mid, mid, 0, kh, kw, width, config);  // g1: 3x3
   p.chain_bytes = bb_align(a > b ? a : b);
   p.s3 = ovis_split_gemm_tn_slices(m, cin, mid, 1);        // dW3 [cin, mid]
-  p.s2 = ovis_split_gemm_tn_slices(m, mid, mid, kh * kw);  // dW2 [mid, mid, kh, kw]
+  if (height > 0) {
+    p.s2 = ovis_split_gemm_tn_map_slices(m, mid, mid, kh, kw, height, width);  // dW2 [mid, mid, kh, kw]
+  } else {
+    p.s2 = ovis_split_gemm_tn_slices(m, mid, mid, kh * kw);
+    for (int h = 1; width > 0 && (long)h * width <= 64; ++h) {
+      const int s = ovis_split_gemm_tn_map_slices(m, mid, mid, kh, kw, h, width);
+      if (s > p.s2) p.s2 = s;
+    }
+  }
   p.s1 = ovis_split_gemm_tn_slices(m, mid, cin, 1);        // dW1 [mid, cin]
   const size_t w3 = (size_t)p.s3 * cin * mid * 4, w2 = (size_t)p.s2 * mid * mid * kh * kw * 4, w1 = (size_t)p.s1 * mid * cin * 4;
   size_t mx = w3 > w2 ? w3 : w2;
@@ -55,7 +65,7 @@ hipEvent_t* bb_events() {
 extern "C" size_t ovis_bottleneck_identity_backward_workspace_bytes(long m, int channels, int mid_channels, int taps_h,
                                                                     int taps_w, int width, int config) {
   if (m <= 0 || channels <= 0 || mid_channels <= 0 || taps_h <= 0 || taps_w <= 0) return 0;
-  const BbPlan p = bb_plan(m, channels, mid_channels, taps_h, taps_w, width, config);
+  const BbPlan p = bb_plan(m, channels, mid_channels, taps_h, taps_w, 0, width, config);
   return p.chain_bytes + p.slab_bytes;
 }
 
@@ -70,7 +80,7 @@ extern "C" int ovis_bottleneck_identity_backward(
       !dw1 || !dw2 || !dw3 || !workspace)
     return OVIS_EINVAL;
   if (channels % 128 || mid_channels % 128 || !(taps_h & 1) || !(taps_w & 1)) return OVIS_ERANGE;
-  const BbPlan p = bb_plan(m, channels, mid_channels, taps_h, taps_w, width, config);
+  const BbPlan p = bb_plan(m, channels, mid_channels, taps_h, taps_w, height, width, config);
   if (workspace_bytes < p.chain_bytes + p.slab_bytes) return OVIS_ENOSPC;
   hipStream_t s = (hipStream_t)stream;
   hipStream_t side = side_stream ? (hipStream_t)side_stream : s;

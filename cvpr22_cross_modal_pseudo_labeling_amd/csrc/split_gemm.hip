@@ -42,6 +42,11 @@
 // co-resident on one L2: the A rows are fetched from HBM once).
 #include <stdlib.h>
 
+#include <functional>
+#include <mutex>
+#include <queue>
+#include <vector>
+
 #include "ovis_common.h"
 constexpr int kGroupWidth = 4;   // column tiles per group of the tile order (16 measured slower, profiles/r4_column_group_ab.txt)
 
@@ -647,8 +652,12 @@ __global__ __launch_bounds__(256) void split_gemm_finish_kernel(SplitGemmArgs p)
 // f(row) = ((row >> 3) & 1) << 2 | (row & 3) (on the DMA source address) so that the 8 rows a 32-lane half reads sit
 // on 8 different bank octets.  The contraction is long (M = R*49 rows) and the output small, so the rows are cut
 // into `slices` and every (tile, slice) workgroup writes its own fp32 slab; the caller sums the slabs
-// (deterministic, no atomics).  For a 3x3 the X rows are read shifted by the tap (zero line outside the map, from a
-// per-position tap mask table in LDS): no im2col rows are materialised for the weight gradient either.
+// (deterministic, no atomics).  For a 3x3 the X rows are read shifted by the tap: no im2col rows are materialised for
+// the weight gradient either.  On large maps (general form) a row whose shifted pixel falls outside the map reads a zero
+// line.  On maps of at most 64 pixels (SMALL form, the 7x7 maps of the res5 head) the rows ARE the contraction
+// dimension, so a tap contracts over its in-map rows only: a k-step is built from 32 consecutive in-map rows of the
+// tap (9 % to 27 % fewer k-steps than rows / 32 on 7x7), every tap is cut into the same number of slices, and the
+// workgroups of the taps with the most in-map rows are dispatched first so that the resident slots end together.
 // ---------------------------------------------------------------------------------------------------
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 
@@ -658,6 +667,18 @@ struct SplitGemmTnArgs {
   float* C;                   // [slices][N][T*ch]
   long M; int N; int ch; int T; int H; int W; int KH; int KW; int slices; int steps_per_slice;
   int g_major;                // tile order inside a row slice: G column tile major (else X column tile major), see the launcher
+};
+
+// SMALL form only: the taps sorted by their number of in-map rows (most first), grouped into classes of equal count.
+// Block ids are class-major, so the long workgroups start first; inside a class they are slice-major as in the other
+// forms.  Filled on the host by the launcher (ovis_split_gemm_pair_tn) from tn_tap_classes() and passed by value.
+constexpr int kTnMaxTaps = 25, kTnMaxClasses = 9;
+struct TnMapPlan {
+  int R;                                 // maps: M / (H * W)
+  int ncls;
+  int cls_end[kTnMaxClasses];            // block ids [cls_end[k-1], cls_end[k]) belong to class k
+  int cls_tap0[kTnMaxClasses + 1];       // class k owns tap_of[cls_tap0[k] .. cls_tap0[k+1])
+  unsigned char tap_of[kTnMaxTaps + 7];
 };
 
 // The transpose reads are inline asm: hipcc treats the ds_read_tr builtin as possibly aliasing the in-flight LDS-DMA
@@ -672,13 +693,17 @@ struct SplitGemmTnArgs {
                : "n"(N)                                                                                            \
                : "memory")
 
-// SMALL (with CONV): maps of at most 64 pixels (the 7x7 maps of the res5 head).  Which rows of a map a tap reads inside the
-// map is then one 64-bit mask (built by a ballot at kernel start) and a DMA row only tracks its pixel index -- ~10 vector
-// instructions per row and step instead of ~45 for the (y, x) bookkeeping of the general form, which at 181 VALU + 73
-// SALU per 48 MFMAs had the 3x3 weight gradient issue-bound (1000 TFLOP/s against 1260-1360 for the 1x1 forms).
+// SMALL (with CONV): maps of at most 64 pixels (the 7x7 maps of the res5 head).  The in-map OUTPUT pixels of a tap
+// (tdy, tdx) form the rectangle y in [max(0,-tdy), H-1-max(0,tdy)], x likewise: hv x wv = cnt pixels per map.
+// Contraction index c in [0, R*cnt) is map r = c / cnt, pixel i = c % cnt of the rectangle, i.e. row
+// m = r*HW + (y0 + i / wv)*W + x0 + i % wv of G and row m + tdy*W + tdx of X (always inside the map: only the rows past
+// R*cnt in the last k-step read the zero line).  A DMA row keeps (r*HW, i) and advances by 32 / cnt maps and 32 % cnt
+// pixels per step with one carry; i / wv is a multiply-shift (i < 64) -- ~16 vector instructions per row and step,
+// against ~45 for the (y, x) bookkeeping of the general form, which at 181 VALU + 73 SALU per 48 MFMAs had the 3x3
+// weight gradient issue-bound (1000 TFLOP/s against 1260-1360 for the 1x1 forms).
 template <bool CONV, bool SMALL = false>
-__global__ __launch_bounds__(256, 2) void split_gemm_tn_kernel(SplitGemmTnArgs p, int tiles_i, int tiles_j,
-                                                              int nblocks) {
+__global__ __launch_bounds__(256, 2) void split_gemm_tn_kernel(SplitGemmTnArgs p, TnMapPlan plan, int tiles_i,
+                                                              int tiles_j, int nblocks) {
   constexpr int TILE_BYTES = 32 * 512, STAGE = 2 * TILE_BYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -688,80 +713,140 @@ __global__ __launch_bounds__(256, 2) void split_gemm_tn_kernel(SplitGemmTnArgs p
   // their G / X working set (~200 MB on the res5 shapes) stays inside the 256 MB Infinity Cache.  Renumbering the whole
   // grid at once spread the resident set over ALL slices (410 MB) and the kernel fetched 2.3x its algorithmic bytes
   // from HBM (profiles/r1_pmc_step_hbm_traffic_student.json).
-  int id;
-  {
+  // SMALL: the same inside each class of taps; a class need not start at a multiple of 8, so the ids of XCD x
+  // (block index % 8) are counted from the chunk's bounds.
+  int id, slice, tile_i, tile_j;
+  if (CONV && SMALL) {
+    constexpr int kChunk = 2 * OVIS_NUM_CU;
+    const int b = blockIdx.x;
+    int k = 0;
+    while (k + 1 < plan.ncls && b >= plan.cls_end[k]) ++k;
+    const int cs = k ? plan.cls_end[k - 1] : 0, ce = plan.cls_end[k];
+    const int lo = cs + (b - cs) / kChunk * kChunk, hi = min(ce, lo + kChunk), xcd = b & 7;
+    int run = 0;
+    for (int x = 0; x < xcd; ++x) run += ((hi - x + 7) >> 3) - ((lo - x + 7) >> 3);
+    id = lo - cs + run + ((b - lo - ((xcd - lo) & 7)) >> 3);
+    const int ct = p.ch >> 7;                                     // column tiles per tap
+    const int tiles_jc = (plan.cls_tap0[k + 1] - plan.cls_tap0[k]) * ct;
+    const int per_slice = tiles_i * tiles_jc;
+    slice = id / per_slice;
+    const int rem = id - slice * per_slice;
+    const int tjc = p.g_major ? rem % tiles_jc : rem / tiles_i;
+    tile_i = p.g_major ? rem / tiles_jc : rem - tjc * tiles_i;
+    const int ti = tjc / ct;
+    tile_j = plan.tap_of[plan.cls_tap0[k] + ti] * ct + (tjc - ti * ct);
+  } else {
     constexpr int kChunk = 2 * OVIS_NUM_CU;
     const int b = blockIdx.x, base = b / kChunk * kChunk;
     const int nb = min(nblocks - base, kChunk), bl = b - base;
     const int q = nb >> 3, r = nb & 7, xcd = bl & 7, loc = bl >> 3;
     id = base + (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    const int per_slice = tiles_i * tiles_j;
+    slice = id / per_slice;
+    const int rem = id - slice * per_slice;
+    tile_j = p.g_major ? rem % tiles_j : rem / tiles_i;
+    tile_i = p.g_major ? rem / tiles_j : rem - tile_j * tiles_i;
   }
-  const int per_slice = tiles_i * tiles_j;
-  const int slice = id / per_slice;
-  const int rem = id - slice * per_slice;
-  const int tile_j = p.g_major ? rem % tiles_j : rem / tiles_i;
-  const int tile_i = p.g_major ? rem / tiles_j : rem - tile_j * tiles_i;
   const int i0 = tile_i * 128, j0 = tile_j * 128;
   const int tap = CONV ? j0 / p.ch : 0, c0 = CONV ? j0 - tap * p.ch : j0;
-  // tap of this workgroup's column tile: X rows are read shifted by (tdy, tdx); a row whose shifted pixel lies outside
-  // the map reads the zero line.  The (y, x) position of every DMA row is tracked incrementally (rows advance by 32
-  // per step: x += 32 % W with carry into y), so maps of any size work and no table is needed.
+  // tap of this workgroup's column tile: X rows are read shifted by (tdy, tdx).  General form: a row whose shifted pixel
+  // lies outside the map reads the zero line, and the (y, x) position of every DMA row is tracked incrementally (rows
+  // advance by 32 per step: x += 32 % W with carry into y), so maps of any size work and no table is needed.  SMALL form:
+  // only rows whose shifted pixel is inside the map are enumerated (below).
   int off_rows = 0, tdy = 0, tdx = 0;
   if (CONV) {
     tdy = tap / p.KW - p.KH / 2;
     tdx = tap % p.KW - p.KW / 2;
     off_rows = tdy * p.W + tdx;
   }
-  const long step0 = (long)slice * p.steps_per_slice;
-  const long steps_total = (p.M + 31) >> 5;
-  long step1 = step0 + p.steps_per_slice;
+  // SMALL: the in-map rectangle of this tap and its own k-step count, cut into the same number of slices as every tap
+  const int HW = CONV ? p.H * p.W : 1;
+  int cnt = 0, wv = 1, pix0 = 0;
+  if (CONV && SMALL) {
+    const int hv = max(p.H - abs(tdy), 0);
+    wv = max(p.W - abs(tdx), 0);
+    cnt = hv * wv;
+    pix0 = max(-tdy, 0) * p.W + max(-tdx, 0);
+  }
+  const long steps_total = (CONV && SMALL) ? ((long)plan.R * cnt + 31) >> 5 : (p.M + 31) >> 5;
+  const int steps_per_slice = (CONV && SMALL) ? (int)((steps_total + p.slices - 1) / p.slices) : p.steps_per_slice;
+  const long step0 = (long)slice * steps_per_slice;
+  long step1 = step0 + steps_per_slice;
   if (step1 > steps_total) step1 = steps_total;
   const int nk = step1 > step0 ? (int)(step1 - step0) : 0;
 
   // ---- per-lane DMA geometry: 4 G pieces + 4 X pieces per wave per step, a piece = 2 rows x 512 B ----
   const int prow = lane >> 5, pseg = (lane & 31) >> 1, phalf = lane & 1;
-  int rows[4];          // tile row of the lane in its 4 pieces
-  long g_off[4], x_off[4];
-  int x_y[4], x_x[4];   // map position of the X row, kept incrementally (SMALL: x_x = pixel index y * W + x)
-  int m_row[4];
-  const int HW = CONV ? p.H * p.W : 1;
-  unsigned long long tap_mask = 0;  // SMALL: bit q set <=> pixel q of a map, shifted by this tap, is inside the map
-  if (CONV && SMALL) {
-    const int qy = lane / p.W, qx = lane - qy * p.W;
-    tap_mask = __ballot(lane < HW && (unsigned)(qy + tdy) < (unsigned)p.H && (unsigned)(qx + tdx) < (unsigned)p.W);
-  }
+  long g_off[4], x_off[4];  // general / 1x1 form: byte offsets of the lane's G and X rows, advanced by 32 rows per step
+  int x_y[4], x_x[4];       // general form: map position of the X row, kept incrementally
+  int m_row[4];             // general / 1x1 form: row index
+  int col_off[4];           // SMALL: byte offset of the lane's 16 B inside a row's 512 B (swizzled segment)
+  int pix[4], map0[4];  // SMALL: pixel index i inside the tap's rectangle and first row r*HW of the map, kept incrementally
+  const int cntd = cnt > 0 ? cnt : 1;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int piece = wave * 4 + i;
     const int row = piece * 2 + prow;
-    rows[i] = row;
     const int fr = (((row >> 3) & 1) << 2) | (row & 3);
     const int seg = pseg ^ fr;
-    const int m = (int)(step0 << 5) + row;
-    m_row[i] = m;
-    g_off[i] = (long)m * p.g_rs + (long)i0 * 4 + seg * 32 + phalf * 16;
-    x_off[i] = ((long)m + off_rows) * p.x_rs + (long)c0 * 4 + seg * 32 + phalf * 16;
-    x_x[i] = CONV ? (SMALL ? m % HW : m % p.W) : 0;
-    x_y[i] = (CONV && !SMALL) ? (m / p.W) % p.H : 0;
+    const int m = (int)(step0 << 5) + row;   // SMALL: the contraction index c, else the row
+    col_off[i] = seg * 32 + phalf * 16;
+    if (CONV && SMALL) {
+      const int r = m / cntd;
+      pix[i] = m - r * cntd;
+      map0[i] = r * HW;
+    } else {
+      m_row[i] = m;
+      g_off[i] = (long)m * p.g_rs + (long)i0 * 4 + col_off[i];
+      x_off[i] = ((long)m + off_rows) * p.x_rs + (long)c0 * 4 + col_off[i];
+      x_x[i] = CONV ? m % p.W : 0;
+      x_y[i] = CONV ? (m / p.W) % p.H : 0;
+    }
   }
-  const int step_q = (CONV && SMALL) ? 32 % HW : 0;
+  const int step_pix = 32 % cntd, step_map = 32 / cntd * HW;
+  const int wv_magic = (65536 + wv - 1) / max(wv, 1);  // i / wv == (i * magic) >> 16 for i < 64, wv <= 64
+  const int wgap = p.W - wv;
   const int step_dx = CONV ? 32 % p.W : 0, step_dy = CONV ? 32 / p.W : 0;
   const bool y_single = step_dy + 1 <= p.H;  // one conditional subtraction brings y back into [0, H)
   const char* zero_src = g_zero_line + (lane & 7) * 16;
   const int Mi = (int)p.M;
+  // SMALL: row strides below 2^31 bytes (the launcher checks), so a row's address is one 32 x 32 + 64-bit multiply-add
+  const unsigned g_rs32 = (unsigned)p.g_rs, x_rs32 = (unsigned)p.x_rs;
+  const char *g_col[4], *x_col[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    g_col[i] = p.G + (long)i0 * 4 + col_off[i];
+    x_col[i] = p.X + (long)off_rows * p.x_rs + (long)c0 * 4 + col_off[i];
+  }
 
-  auto issue = [&](int stage) {
+  auto issue_small = [&](int stage) {
+    char* base = smem + stage * STAGE;
+    const char *gs[4], *xs[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int y = (pix[i] * wv_magic) >> 16;
+      const int m = map0[i] + pix0 + pix[i] + y * wgap;   // G row; the X row is m + off_rows (folded into x_col)
+      const bool ok = map0[i] < Mi;                      // r < R
+      gs[i] = ok ? g_col[i] + (unsigned long)(unsigned)m * g_rs32 : zero_src;
+      xs[i] = ok ? x_col[i] + (unsigned long)(unsigned)m * x_rs32 : zero_src;
+      int q = pix[i] + step_pix, r0 = map0[i] + step_map;
+      if (q >= cnt) { q -= cnt; r0 += HW; }
+      pix[i] = q;
+      map0[i] = r0;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) glds16(gs[i], base + (wave * 4 + i) * 1024);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) glds16(xs[i], base + TILE_BYTES + (wave * 4 + i) * 1024);
+  };
+
+  auto issue_rows = [&](int stage) {
     char* base = smem + stage * STAGE;
     bool x_ok[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       x_ok[i] = m_row[i] < Mi;
-      if (CONV && SMALL) {
-        x_ok[i] = x_ok[i] && ((tap_mask >> x_x[i]) & 1ull) != 0ull;
-        int q = x_x[i] + step_q;
-        if (q >= HW) q -= HW;
-        x_x[i] = q;
-      } else if (CONV) {
+      if (CONV) {
         x_ok[i] = x_ok[i] && (unsigned)(x_y[i] + tdy) < (unsigned)p.H && (unsigned)(x_x[i] + tdx) < (unsigned)p.W;
         int x = x_x[i] + step_dx, y = x_y[i] + step_dy;
         if (x >= p.W) { x -= p.W; ++y; }
@@ -785,6 +870,9 @@ __global__ __launch_bounds__(256, 2) void split_gemm_tn_kernel(SplitGemmTnArgs p
       x_off[i] += 32 * p.x_rs;
       m_row[i] += 32;
     }
+  };
+  auto issue = [&](int stage) {
+    if (CONV && SMALL) issue_small(stage); else issue_rows(stage);
   };
 
   // ---- transpose-read addresses: lane (group gq, p): row 8*gq + p/4 (+4 second half), 8 bytes at (p%4)*8 of a segment
@@ -1281,6 +1369,107 @@ extern "C" int ovis_split_gemm_tn_slices(long m, int n, int channels, int taps) 
   return (int)best;
 }
 
+// ---- SMALL form of the weight gradient: the taps in dispatch order and the slice count ----
+namespace {
+struct TnTapClasses {
+  int ncls;
+  int ntaps[kTnMaxClasses];    // taps in class k
+  int cnt[kTnMaxClasses];      // in-map rows per map of a tap of class k, descending
+  unsigned char tap_of[kTnMaxTaps + 7];
+};
+
+// The SMALL form serves odd kernels of up to 5 x 5 taps (kTnMaxTaps; their separable in-map counts fall into at most
+// 3 x 3 = kTnMaxClasses classes) on maps of at most 64 pixels whose rows are whole maps
+// (row strides below 2^31 bytes); everything else goes to the general form.
+bool tn_map_form(long m, long g_row_bytes, long x_row_bytes, int taps_h, int taps_w, int height, int width) {
+  const int T = taps_h * taps_w;
+  return T > 1 && taps_h <= 5 && taps_w <= 5 && height > 0 && width > 0 && (long)height * width <= 64 &&
+         m % ((long)height * width) == 0 && m <= 0x7fff0000L && g_row_bytes >= 0 && g_row_bytes <= 0x7fffffffL &&
+         x_row_bytes >= 0 && x_row_bytes <= 0x7fffffffL;
+}
+
+// Taps sorted by their in-map row count, most first (stable), and the classes of equal count.  Separable counts:
+// at most 3 x 3 distinct values for up to 5 x 5 taps.
+void tn_tap_classes(int taps_h, int taps_w, int height, int width, TnTapClasses* c) {
+  const int T = taps_h * taps_w;
+  int cnt[kTnMaxTaps];
+  for (int t = 0; t < T; ++t) {
+    const int dy = t / taps_w - taps_h / 2, dx = t % taps_w - taps_w / 2;
+    const int hv = height - (dy < 0 ? -dy : dy), wv = width - (dx < 0 ? -dx : dx);
+    cnt[t] = hv > 0 && wv > 0 ? hv * wv : 0;
+    int k = t;
+    for (; k > 0 && cnt[c->tap_of[k - 1]] < cnt[t]; --k) c->tap_of[k] = c->tap_of[k - 1];
+    c->tap_of[k] = (unsigned char)t;
+  }
+  c->ncls = 0;
+  for (int k = 0; k < T; ++k) {
+    const int v = cnt[c->tap_of[k]];
+    if (c->ncls > 0 && c->cnt[c->ncls - 1] == v) { ++c->ntaps[c->ncls - 1]; continue; }
+    c->cnt[c->ncls] = v;
+    c->ntaps[c->ncls++] = 1;
+  }
+}
+
+// Time of the launch in k-steps for `slices`: the workgroups are handed to the resident slots in dispatch order
+// (class-major), each to the slot that frees first.  A workgroup costs its k-steps plus a fixed share (prologue, slab
+// write) of about 8 k-steps.
+long tn_map_makespan(const TnTapClasses& c, long maps, long tiles_per_tap, int slices, long slots) {
+  std::priority_queue<long, std::vector<long>, std::greater<long>> free_at;
+  long end = 0;
+  for (int k = 0; k < c.ncls; ++k) {
+    const long steps = (maps * c.cnt[k] + 31) / 32, len = (steps + slices - 1) / slices + 8;
+    for (long b = tiles_per_tap * c.ntaps[k] * slices; b > 0; --b) {
+      long t = len;
+      if ((long)free_at.size() >= slots) { t += free_at.top(); free_at.pop(); }
+      free_at.push(t);
+      if (t > end) end = t;
+    }
+  }
+  return end;
+}
+}  // namespace
+
+extern "C" int ovis_split_gemm_tn_map_slices(long m, int n, int channels, int taps_h, int taps_w, int height, int width) {
+  if (m <= 0 || n <= 0 || channels <= 0 || taps_h <= 0 || taps_w <= 0) return 1;
+  if (!tn_map_form(m, 0, 0, taps_h, taps_w, height, width)) return ovis_split_gemm_tn_slices(m, n, channels, taps_h * taps_w);
+  // A pure function of its arguments, asked on launch paths (the one-call bottleneck backward): the simulation below
+  // runs once per distinct shape, a step sees a handful of them.
+  struct Key { long m; int n, ch, kh, kw, h, w, slices; };
+  static std::mutex memo_mutex;
+  static std::vector<Key> memo;
+  {
+    std::lock_guard<std::mutex> lock(memo_mutex);
+    for (const Key& k : memo)
+      if (k.m == m && k.n == n && k.ch == channels && k.kh == taps_h && k.kw == taps_w && k.h == height && k.w == width)
+        return k.slices;
+  }
+  const long tiles_per_tap = (long)(n / 128) * (channels / 128), tiles = tiles_per_tap * taps_h * taps_w;
+  if (tiles <= 0) return 1;
+  TnTapClasses c;
+  tn_tap_classes(taps_h, taps_w, height, width, &c);
+  const long maps = m / ((long)height * width), slots = 2L * OVIS_NUM_CU;
+  const long steps = (maps * c.cnt[0] + 31) / 32;                        // the longest tap (the centre)
+  long s_max = (4 * slots + tiles - 1) / tiles;                          // up to ~4 rounds, as ovis_split_gemm_tn_slices
+  if (s_max > steps / 8) s_max = steps / 8;                              // at least 8 k-steps per slice
+  if (s_max > 256) s_max = 256;
+  if (s_max < 1) s_max = 1;
+  // every slice adds a slab to write and to sum: 8 bytes per element at ~3 TB/s against ~1.4 us per k-step of a slot,
+  // i.e. 4.5 k-steps per slice on the res5 shapes (512 x 4608)
+  const double slab_steps = (double)n * taps_h * taps_w * channels / 524288.0;
+  long best = 1;
+  double best_cost = -1.0;
+  for (long s = 1; s <= s_max; ++s) {
+    const double cost = (double)tn_map_makespan(c, maps, tiles_per_tap, (int)s, slots) + slab_steps * (double)s;
+    if (best_cost < 0.0 || cost < best_cost - 1e-9) { best_cost = cost; best = s; }
+  }
+  {
+    std::lock_guard<std::mutex> lock(memo_mutex);
+    if (memo.size() >= 256) memo.clear();
+    memo.push_back(Key{m, n, channels, taps_h, taps_w, height, width, (int)best});
+  }
+  return (int)best;
+}
+
 extern "C" int ovis_split_gemm_pair_tn(const void* g_pair, long g_row_bytes, const void* x_pair, long x_row_bytes,
                                        float* c_slabs, int slices, long m, int n, int channels, int taps_h,
                                        int taps_w, int height, int width, void* stream) {
@@ -1310,27 +1499,39 @@ extern "C" int ovis_split_gemm_pair_tn(const void* g_pair, long g_row_bytes, con
   if (nblocks > 0x7fffffffL) return OVIS_ERANGE;
   hipStream_t s = (hipStream_t)stream;
   const int lds = 2 * 2 * 32 * 512;
-  if (T > 1 && (long)height * width <= 64) {
+  TnMapPlan plan = {};
+  if (tn_map_form(m, g_row_bytes, x_row_bytes, taps_h, taps_w, height, width)) {
+    TnTapClasses c;
+    tn_tap_classes(taps_h, taps_w, height, width, &c);
+    plan.R = (int)(m / ((long)height * width));
+    plan.ncls = c.ncls;
+    long end = 0;
+    for (int k = 0; k < c.ncls; ++k) {
+      plan.cls_tap0[k + 1] = plan.cls_tap0[k] + c.ntaps[k];
+      end += (long)tiles_i * (channels / 128) * c.ntaps[k] * slices;
+      plan.cls_end[k] = (int)end;
+    }
+    for (int t = 0; t < T; ++t) plan.tap_of[t] = c.tap_of[t];
     static bool attr_set_s = false;
     if (!attr_set_s) {
       OVIS_HIP_TRY(hipFuncSetAttribute((const void*)split_gemm_tn_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       attr_set_s = true;
     }
-    hipLaunchKernelGGL((split_gemm_tn_kernel<true, true>), dim3((unsigned)nblocks), dim3(256), lds, s, p, tiles_i, tiles_j, (int)nblocks);
+    hipLaunchKernelGGL((split_gemm_tn_kernel<true, true>), dim3((unsigned)nblocks), dim3(256), lds, s, p, plan, tiles_i, tiles_j, (int)nblocks);
   } else if (T > 1) {
     static bool attr_set_c = false;
     if (!attr_set_c) {
       OVIS_HIP_TRY(hipFuncSetAttribute((const void*)split_gemm_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       attr_set_c = true;
     }
-    hipLaunchKernelGGL(split_gemm_tn_kernel<true>, dim3((unsigned)nblocks), dim3(256), lds, s, p, tiles_i, tiles_j, (int)nblocks);
+    hipLaunchKernelGGL(split_gemm_tn_kernel<true>, dim3((unsigned)nblocks), dim3(256), lds, s, p, plan, tiles_i, tiles_j, (int)nblocks);
   } else {
     static bool attr_set = false;
     if (!attr_set) {
       OVIS_HIP_TRY(hipFuncSetAttribute((const void*)split_gemm_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       attr_set = true;
     }
-    hipLaunchKernelGGL(split_gemm_tn_kernel<false>, dim3((unsigned)nblocks), dim3(256), lds, s, p, tiles_i, tiles_j, (int)nblocks);
+    hipLaunchKernelGGL(split_gemm_tn_kernel<false>, dim3((unsigned)nblocks), dim3(256), lds, s, p, plan, tiles_i, tiles_j, (int)nblocks);
   }
   OVIS_LAUNCH_CHECK();
   return OVIS_OK;

@@ -450,8 +450,13 @@ int ovis_split_gemm_pair_rp(const void* a_pair, long a_row_bytes, const void* b_
  * G[m, n] * X[row(m, tap), c]  (G = gated output gradient [m, n], X = the layer input [m, channels], both pair
  * rows; taps as in ovis_split_gemm_pair, X read shifted with zeros outside the map).  The rows are cut into
  * `slices` (ovis_split_gemm_tn_slices gives a count that fills the chip); the caller sums the slabs.
- * n % 128 == 0, channels % 128 == 0 (else OVIS_ERANGE); any map size. */
+ * n % 128 == 0, channels % 128 == 0 (else OVIS_ERANGE); any map size.
+ * On maps of at most 64 pixels (m a multiple of height * width, at most 5 x 5 taps) a tap contracts over its in-map rows
+ * only, every tap is cut into `slices` slices of its own rows and the taps with the most rows are dispatched first;
+ * the slab layout is the same.  ovis_split_gemm_tn_map_slices scores that work (and equals ovis_split_gemm_tn_slices
+ * for every other shape). */
 int ovis_split_gemm_tn_slices(long m, int n, int channels, int taps);
+int ovis_split_gemm_tn_map_slices(long m, int n, int channels, int taps_h, int taps_w, int height, int width);
 int ovis_split_gemm_pair_tn(const void* g_pair, long g_row_bytes, const void* x_pair, long x_row_bytes,
                             float* c_slabs, int slices, long m, int n, int channels, int taps_h,
                             int taps_w, int height, int width, void* stream);

@@ -1,5 +1,5 @@
 """3x3 weight-gradient GEMM of the res5 head at the step's size with ablation builds of the kernel (build_variants.sh
-"nomask:-DOVIS_TN_ABL_NOMASK" "noshift:-DOVIS_TN_ABL_NOMASK -DOVIS_TN_ABL_NOSHIFT"; wrong results, timing only) next to the 1x1
+"noshift:-DOVIS_TN_ABL_NOSHIFT"; wrong results, timing only) next to the 1x1
 weight gradients.  python tools/experiments/tn_ablation_probe.py [variant]"""
 import os
 import sys
