@@ -241,6 +241,9 @@ def nms_padded(dets, scores, threshold, ge_mode=False):
     return keep, num
 
 
+NMS_MAX_CANDIDATES = 131072  # csrc/nms.hip: kMaxBlocks * 64 -- what one nms / nms_grouped call accepts
+
+
 def nms_grouped_padded(dets, scores, groups, threshold, ge_mode=False):
     """NMS inside every group of boxes in one launch (groups [K] integer labels): (keep[K] int64 -- first n entries
     valid, ascending indices into the K candidates; n as a 1-element int32 device tensor).  Equals ``nms`` run on
@@ -407,6 +410,97 @@ def box_decode(rel_codes, boxes, weights, xform_clip, rows_per_image=None, image
             if i0 >= n:
                 break
     return out
+
+
+_VIEW_MERGE_MAX_SEGMENTS = 64  # include/ovis_hip.h: OVIS_VIEW_MERGE_MAX_SEGMENTS
+_VIEW_MERGE_TILE_ROWS = 64     # include/ovis_hip.h: OVIS_VIEW_MERGE_TILE_ROWS
+
+
+def _merge_segments(segments, num_rows):
+    """The (row_start, row_count, image, view_width, flip, ratio_w, ratio_h) records as checked python values: rows inside
+    [0, num_rows), images 0, 1, ... in order, each with at least one segment.  Raises before anything is launched."""
+    out, last = [], -1
+    for k, seg in enumerate(segments):
+        if len(seg) != 7:
+            raise RuntimeError(f"merge_view_detections: segment {k} must be (row_start, row_count, image, view_width, flip, "
+                               "ratio_w, ratio_h)")
+        row_start, row_count, image, width = (int(v) for v in seg[:4])
+        if row_start < 0 or row_count < 0 or row_start + row_count > num_rows:
+            raise RuntimeError(f"merge_view_detections: segment {k} covers rows [{row_start}, {row_start + row_count}) of "
+                               f"{num_rows}")
+        if image not in (last, last + 1) or width < 0:
+            raise RuntimeError(f"merge_view_detections: segment {k}: images must come in order 0, 1, ... (image-major, every "
+                               f"image with a segment) and widths be >= 0; got image {image} after {last}, width {width}")
+        last = image
+        out.append((row_start, row_count, image, width, int(bool(seg[4])), float(seg[5]), float(seg[6])))
+    return out, last + 1
+
+
+def merge_view_detections(boxes, scores, segments, num_classes, score_thresh):
+    """The candidate list of a batch's test-time-augmentation views (engine/bbox_aug.py:53-60 followed by the
+    ``scores > thresh`` of box_head/inference.py:137-143), ``ovis_view_merge_*``: boxes [R, C, 4] / scores [R, C] float32,
+    every view's class-specific detections in the view's own frame; ``segments``: one (row_start, row_count, image,
+    view_width, flip, ratio_w, ratio_h) per (image, view), image-major then view order, rows contiguous, ``ratio_*`` =
+    ``float(target) / float(view)`` (rounded to float32 here, as a float32 tensor times a python float does).
+    -> (cand_boxes [K, 4], cand_scores [K], cand_group [K] int32 = image * C + class, offsets [B * C + 1] int32): every
+    box flipped back (``BoxList.transpose(0)``) and scaled (``BoxList.resize``), the classes >= 1 with score > thresh (a NaN
+    is not kept), ordered image, class, segment, row.  Device tensors: three launches per OVIS_VIEW_MERGE_MAX_SEGMENTS (64)
+    segments -- a longer list is cut at image boundaries, one image may not have more views than that -- and ONE host read
+    (K); host tensors: the BoxList route as the reference writes it (``_cpu.merge_view_detections``)."""
+    if boxes.is_cuda != scores.is_cuda:
+        raise RuntimeError("merge_view_detections: host and device tensors mixed in one call")
+    c = int(num_classes)
+    if (scores.dim() != 2 or scores.shape[1] != c or c < 1 or boxes.dim() != 3 or boxes.shape != (scores.shape[0], c, 4)
+            or boxes.dtype != torch.float32 or scores.dtype != torch.float32):
+        raise RuntimeError(f"merge_view_detections: expected float32 boxes [R, {c}, 4] and scores [R, {c}], got "
+                           f"{boxes.dtype} {tuple(boxes.shape)} and {scores.dtype} {tuple(scores.shape)}")
+    r = scores.shape[0]
+    segs, b = _merge_segments(segments, r)
+    if r * c >= 2 ** 31 or b * c >= 2 ** 31 - 1:
+        raise RuntimeError("merge_view_detections: R * C and B * C must stay below 2^31")
+    if not boxes.is_cuda:
+        return _cpu.merge_view_detections(boxes, scores, segs, c, b, float(score_thresh))
+    boxes, scores = _dev(boxes, "boxes"), _dev(scores, "scores")
+    dev = boxes.device
+    offsets = torch.empty((b * c + 1,), dtype=torch.int32, device=dev)
+    # launches: whole images, at most _VIEW_MERGE_MAX_SEGMENTS segments each; (first segment, count, first count entry)
+    per_image = [0] * b
+    for seg in segs:
+        per_image[seg[2]] += 1
+    if b and max(per_image) > _VIEW_MERGE_MAX_SEGMENTS:
+        raise RuntimeError(f"merge_view_detections: image {per_image.index(max(per_image))} has {max(per_image)} views, more "
+                           f"than the {_VIEW_MERGE_MAX_SEGMENTS} segments of one launch")
+    calls, first, entries, image = [], 0, 0, 0
+    while image < b:
+        n = 0
+        while image < b and n + per_image[image] <= _VIEW_MERGE_MAX_SEGMENTS:
+            n += per_image[image]
+            image += 1
+        part = segs[first:first + n]
+        num = c * sum(max(1, -(-seg[1] // _VIEW_MERGE_TILE_ROWS)) for seg in part)
+        ints = (ctypes.c_int32 * (5 * n))(*[int(v) for seg in part for v in seg[:5]])
+        ratios = (ctypes.c_float * (2 * n))(*[v for seg in part for v in seg[5:]])
+        calls.append((ints, ratios, n, entries, num))
+        entries += num
+        first += n
+    counts = torch.empty((max(entries, 1),), dtype=torch.int32, device=dev)
+    with _on(dev):
+        stream = _stream()
+        for ints, ratios, n, at, num in calls:
+            _lib.check(_L.ovis_view_merge_count_f32(scores.data_ptr(), r, c, b, ints, ratios, n, score_thresh,
+                                                    counts.data_ptr() + 4 * at, num, stream), "merge_view_detections (count)")
+        _lib.check(_L.ovis_view_merge_scan_i32(counts.data_ptr(), entries, offsets.data_ptr() + 4 * b * c, stream),
+                   "merge_view_detections (scan)")
+        k = int(offsets[-1].item())   # the one host read: the outputs' size (nms_grouped needs K on the host as well)
+        cand_boxes = torch.empty((k, 4), dtype=torch.float32, device=dev)
+        cand_scores = torch.empty((k,), dtype=torch.float32, device=dev)
+        cand_group = torch.empty((k,), dtype=torch.int32, device=dev)
+        for ints, ratios, n, at, num in calls:
+            _lib.check(_L.ovis_view_merge_scatter_f32(boxes.data_ptr(), scores.data_ptr(), r, c, b, ints, ratios, n,
+                                                      score_thresh, counts.data_ptr() + 4 * at, num, k,
+                                                      cand_boxes.data_ptr(), cand_scores.data_ptr(), cand_group.data_ptr(),
+                                                      offsets.data_ptr(), stream), "merge_view_detections (scatter)")
+    return cand_boxes, cand_scores, cand_group, offsets
 
 
 def rois_from_boxes(boxes, image_ids=None):

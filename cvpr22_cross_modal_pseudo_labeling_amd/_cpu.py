@@ -217,3 +217,46 @@ def text_embed(table, input_ids, special_tokens_mask):
     keep = (1 - special_tokens_mask).to(torch.float32)
     emb = (table[input_ids] * keep[:, :, None]).sum(1) / keep.sum(1)[:, None]
     return F.normalize(emb, dim=-1)
+
+
+# ---- engine/bbox_aug.py:53-60 + box_head/inference.py:137-143: the merge of test-time-augmentation views ------------------
+def merge_view_detections(boxes, scores, segments, num_classes, num_images, score_thresh):
+    """Host tensors: the reference's route as it writes it -- per view ``BoxList.transpose(0)`` when flipped, the two
+    multiplications of ``BoxList.resize`` (the records carry the ratios ``resize`` computes from the two sizes, so the
+    products are formed here with its expressions), ``torch.cat`` over an image's views, then per class
+    ``nonzero(scores > thresh)``.  -> (cand_boxes, cand_scores, cand_group, offsets) as ``_C.merge_view_detections``."""
+    from .modeling.structures import BoxList
+
+    boxes, scores = _host(boxes, "boxes"), _host(scores, "scores")
+    c = num_classes
+    out_boxes, out_scores, out_group, offsets = [], [], [], [0]
+    for image in range(num_images):
+        view_boxes, view_scores = [], []
+        for row_start, row_count, img, width, flip, ratio_w, ratio_h in segments:
+            if img != image:
+                continue
+            view = BoxList(boxes[row_start:row_start + row_count].reshape(-1, 4), (width, 1))
+            if flip:
+                view = view.transpose(0)
+            ratio_w, ratio_h = (float(torch.tensor(v, dtype=torch.float32)) for v in (ratio_w, ratio_h))
+            if ratio_w == ratio_h:  # BoxList.resize
+                scaled = view.bbox * ratio_w
+            else:
+                xmin, ymin, xmax, ymax = view.bbox.split(1, dim=-1)
+                scaled = torch.cat((xmin * ratio_w, ymin * ratio_h, xmax * ratio_w, ymax * ratio_h), dim=-1)
+            view_boxes.append(scaled.reshape(-1, c, 4))
+            view_scores.append(scores[row_start:row_start + row_count])
+        all_boxes, all_scores = torch.cat(view_boxes, 0), torch.cat(view_scores, 0)
+        inds_all = all_scores > score_thresh
+        offsets.append(offsets[-1])  # class 0, the background, is an empty run
+        for j in range(1, c):
+            inds = inds_all[:, j].nonzero().squeeze(1)
+            out_boxes.append(all_boxes[inds, j])
+            out_scores.append(all_scores[inds, j])
+            out_group.append(torch.full((inds.numel(),), image * c + j, dtype=torch.int32))
+            offsets.append(offsets[-1] + inds.numel())
+    if not out_boxes:
+        return (torch.zeros((0, 4)), torch.zeros((0,)), torch.zeros((0,), dtype=torch.int32),
+                torch.tensor(offsets, dtype=torch.int32))
+    return (torch.cat(out_boxes, 0).reshape(-1, 4), torch.cat(out_scores, 0), torch.cat(out_group, 0),
+            torch.tensor(offsets, dtype=torch.int32))

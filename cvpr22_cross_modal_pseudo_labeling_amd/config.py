@@ -160,7 +160,9 @@ def get_defaults():
             "LOG_PERIOD": 20, "IMS_PER_BATCH": 16, "CLIP_GRAD_NORM_AT": -1.0, "GRADIENT_ACCUMULATION_STEPS": 1,
             "SKIP_VAL_LOSS": False, "UNCERTAINTY_LR_FACTOR": 1.0,
         },
-        "TEST": {"IMS_PER_BATCH": 8, "DETECTIONS_PER_IMG": 100},
+        "TEST": {"IMS_PER_BATCH": 8, "DETECTIONS_PER_IMG": 100,
+                 # :547-562 multi-scale / flip testing (engine/bbox_aug.py)
+                 "BBOX_AUG": {"ENABLED": False, "H_FLIP": False, "SCALES": (), "MAX_SIZE": 4000, "SCALE_H_FLIP": False}},
         "OUTPUT_DIR": ".",
         "DTYPE": "float32",
     })

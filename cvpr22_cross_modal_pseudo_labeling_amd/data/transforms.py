@@ -103,8 +103,102 @@ class InputTransform:
         return (self.device(batch[0]),) + tuple(batch[1:])
 
 
+class ViewBatch:
+    """The test-time-augmentation views of one batch (TEST.BBOX_AUG): ``views[v]`` is the ``ImageList`` of view v over the
+    same images, ``flips[v]`` whether that view is mirrored left-right.  View 0 is the un-augmented one: detections are
+    reported in its frame and size."""
+
+    def __init__(self, views, flips):
+        self.views, self.flips = list(views), [bool(f) for f in flips]
+        if not self.views or len(self.views) != len(self.flips):
+            raise ValueError("ViewBatch: one flip flag per view, at least one view")
+
+    def __len__(self):
+        return len(self.views)
+
+    def to(self, *args, **kwargs):
+        return ViewBatch([v.to(*args, **kwargs) for v in self.views], self.flips)
+
+    def device_tensors(self):
+        return [v.tensors for v in self.views]
+
+
+class ViewTransform:
+    """The input transform of multi-scale / flip testing, with ``InputTransform``'s interface.  ``plan`` lists the views as
+    (min_size, max_size, flip) in the reference's order (engine/bbox_aug.py:26-51).  The reference re-runs PIL per view in
+    the loader; here ``host`` packs the bytes ONCE and emits one descriptor table per view over the same byte offsets (sizes
+    from ``get_size``, the flip forced, not drawn; the flip acts after the resize, as Resize -> RandomHorizontalFlip(1.0)
+    does), and ``device`` makes every view from the one upload, one ``_C.transform_images`` call per view."""
+
+    def __init__(self, plan, mean, std, to_bgr255, size_divisible=0):
+        self.plan = [(int(lo), int(hi), bool(flip)) for lo, hi, flip in plan]
+        if not self.plan:
+            raise ValueError("ViewTransform: at least one view")
+        self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
+        self.to_bgr255, self.size_divisible = bool(to_bgr255), int(size_divisible)
+
+    def host(self, images, targets=None, rng=None):
+        """-> (raw, None): ``raw["data"]`` the packed bytes; per view v ``raw["desc"][v]`` its [B, 7] descriptors,
+        ``raw["image_sizes"][v]`` and ``raw["pad_hw"][v]`` (DATALOADER.SIZE_DIVISIBILITY applied per view).  The tensors sit
+        at the top level of ``raw``, as ``InputTransform``'s do.  Evaluation only: targets are not transformed."""
+        if targets is not None:
+            raise ValueError("ViewTransform.host: test-time augmentation is an evaluation transform, it takes no targets")
+        if len(images) == 0:
+            raise ValueError("ViewTransform.host: an empty batch has no padded size")
+        chunks, geom, offset = [], [], 0
+        for i, img in enumerate(images):
+            img = torch.as_tensor(np.ascontiguousarray(img) if isinstance(img, np.ndarray) else img)
+            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+                raise ValueError(f"image {i}: expected uint8 [h, w, 3], got {img.dtype} {tuple(img.shape)}")
+            h, w = int(img.shape[0]), int(img.shape[1])
+            geom.append((offset, h, w))
+            chunks.append(img.contiguous().view(-1))
+            offset += h * w * 3
+            if offset >= 2 ** 31:
+                raise ValueError("a batch of raw images is limited to 2 GiB")
+        descs, view_sizes, pads = [], [], []
+        for min_size, max_size, flip in self.plan:
+            sizes = [get_size(w, h, min_size, max_size) for _, h, w in geom]
+            desc = [[off, h, w, oh, ow, int(flip), 0] for (off, h, w), (oh, ow) in zip(geom, sizes)]
+            pad_h, pad_w = max(s[0] for s in sizes), max(s[1] for s in sizes)
+            if self.size_divisible > 0:  # image_list.py:54-61
+                d = self.size_divisible
+                pad_h, pad_w = -(-pad_h // d) * d, -(-pad_w // d) * d
+            descs.append(desc)
+            view_sizes.append(sizes)
+            pads.append((pad_h, pad_w))
+        raw = {"data": torch.cat(chunks), "desc": torch.tensor(descs, dtype=torch.int32), "image_sizes": view_sizes, "pad_hw": pads,
+               "max_in_hw": (max(g[1] for g in geom), max(g[2] for g in geom))}
+        return raw, None
+
+    def device(self, raw):
+        """-> ViewBatch on the device ``raw``'s tensors live on."""
+        lists = []
+        for desc, sizes, pad_hw in zip(raw["desc"], raw["image_sizes"], raw["pad_hw"]):
+            tensors = _C.transform_images(raw["data"], desc, self.mean, self.std, self.to_bgr255, pad_hw, raw["max_in_hw"])
+            lists.append(ImageList(tensors, [tuple(s) for s in sizes]))
+        return ViewBatch(lists, [flip for _, _, flip in self.plan])
+
+    def __call__(self, batch):
+        return (self.device(batch[0]),) + tuple(batch[1:])
+
+
+def view_plan(cfg):
+    """The (min_size, max_size, flip) of every view of TEST.BBOX_AUG, in the order engine/bbox_aug.py:26-51 runs them."""
+    aug = cfg.TEST.BBOX_AUG
+    plan = [(cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST, False)]
+    if aug.H_FLIP:
+        plan.append((cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST, True))
+    for scale in aug.SCALES:
+        plan.append((scale, aug.MAX_SIZE, False))
+        if aug.SCALE_H_FLIP:
+            plan.append((scale, aug.MAX_SIZE, True))
+    return plan
+
+
 def build_transforms(cfg, is_train=True, seed=0):
-    """build.py:5-46 for this package's split transform."""
+    """build.py:5-46 for this package's split transform; the evaluation transform of TEST.BBOX_AUG.ENABLED makes every
+    view (``ViewTransform``)."""
     if is_train:
         min_size, max_size = cfg.INPUT.MIN_SIZE_TRAIN, cfg.INPUT.MAX_SIZE_TRAIN
         flip_h, flip_v = cfg.INPUT.HORIZONTAL_FLIP_PROB_TRAIN, cfg.INPUT.VERTICAL_FLIP_PROB_TRAIN
@@ -112,6 +206,9 @@ def build_transforms(cfg, is_train=True, seed=0):
         if any(v != 0 for v in jitter.values()):
             raise NotImplementedError(f"colour jitter is not implemented in the device input transform: INPUT {jitter}")
     else:
+        if cfg.TEST.BBOX_AUG.ENABLED:
+            return ViewTransform(view_plan(cfg), cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD, cfg.INPUT.TO_BGR255,
+                                 cfg.DATALOADER.SIZE_DIVISIBILITY)
         min_size, max_size = cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST
         flip_h = flip_v = 0.0
     return InputTransform(min_size, max_size, flip_h, flip_v, cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD, cfg.INPUT.TO_BGR255,

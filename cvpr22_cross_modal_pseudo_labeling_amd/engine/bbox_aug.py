@@ -1,0 +1,76 @@
+"""Multi-scale / flip testing (TEST.BBOX_AUG): maskrcnn_benchmark/engine/bbox_aug.py:11-69.
+
+The reference runs the whole detector per view, maps every view's detections back per view and per image
+(``BoxList.transpose`` / ``BoxList.resize``), concatenates them and filters the concatenation with the box
+post-processor's per-class loop.  Here the views of a batch come from one upload (data/transforms.py::ViewTransform), the
+detector's unfiltered pass runs per view, and ONE ``_C.merge_view_detections`` writes the flipped-back, rescaled,
+thresholded, class-major candidate list of the whole batch, which ``PostProcessor.filter_merged`` hands to the grouped NMS
+as it is.  Detections are in the first view's frame and size, as in the reference.
+
+Deviation: the reference returns boxes only under augmentation; with MODEL.MASK_ON the merged boxes get
+their masks here from the mask head on the FIRST (un-augmented) view's features, so mask scoring and pictures keep working.
+"""
+import torch
+
+from .. import _C
+
+# ``filter_merged`` cuts the candidate list into slices of about this many candidates, at (image, class) boundaries, one
+# grouped NMS each.  A call tests every pair of its candidates whatever their groups (K^2 / 2 IoU tests) and its sequential
+# reduce has its pipelined form up to 12288 candidates (csrc/nms.hip: kFastBlocks), so one call over a batch's ~50 000
+# candidates costs more than the per-image calls it replaces; 8192 was the fastest of 2048 ... 131072 at 2 images x 6 views
+# x 1000 proposals x 66 classes (profiles/ab_view_merge.txt).
+NMS_SLICE_CANDIDATES = 8192
+
+
+def view_segments(detections_per_view, flips, num_classes):
+    """The segment records of ``_C.merge_view_detections`` for ``detections_per_view[v][i]`` (view v, image i; bbox
+    [n * C, 4], ``scores`` [n * C]), rows laid out image-major then view order -> (boxes [R, C, 4], scores [R, C], segments).
+    ``ratio_*`` = float(first view's size) / float(view's size), what ``BoxList.resize`` computes (bbox_aug.py:20-24); a
+    mirrored view is flipped back first, in its own width (bbox_aug.py:106-107)."""
+    boxes, scores, segments, row = [], [], [], 0
+    num_images = len(detections_per_view[0])
+    for i in range(num_images):
+        target_w, target_h = detections_per_view[0][i].size
+        for view, flip in zip(detections_per_view, flips):
+            det = view[i]
+            w, h = det.size
+            n = len(det) // num_classes
+            boxes.append(det.bbox.reshape(n, num_classes, 4))
+            scores.append(det.get_field("scores").reshape(n, num_classes))
+            segments.append((row, n, i, w, int(flip), float(target_w) / float(w), float(target_h) / float(h)))
+            row += n
+    return torch.cat(boxes, 0), torch.cat(scores, 0), segments
+
+
+def _unwrap(model):
+    return model.module if hasattr(model, "module") and not hasattr(model, "detect_unfiltered") else model
+
+
+def model_cfg(model):
+    """The configuration a detector's heads were built from (None for a module without such heads)."""
+    return getattr(getattr(_unwrap(model), "roi_heads", None), "cfg", None)
+
+
+@torch.no_grad()
+def im_detect_bbox_aug(model, view_batch, cfg=None):
+    """``view_batch``: data.transforms.ViewBatch on the model's device -> one BoxList per image (``scores``, ``labels``,
+    and ``mask`` when MODEL.MASK_ON), in the first view's frame.  ``cfg``: the model's configuration (default: the one
+    its heads were built from)."""
+    model = _unwrap(model)
+    heads = model.roi_heads_student if hasattr(model, "roi_heads_student") else model.roi_heads
+    box_head, cfg = heads["box"], (heads.cfg if cfg is None else cfg)
+    features, per_view = None, []
+    for images in view_batch.views:
+        view_features, detections = model.detect_unfiltered(images)
+        if features is None:
+            features = view_features  # the masks come from the un-augmented view
+        per_view.append(detections)
+    sizes = [det.size for det in per_view[0]]
+    num_classes = model.roi_heads["box"].predictor.num_classes   # bbox_aug.py:66, the classifier's matrix
+    boxes, scores, segments = view_segments(per_view, view_batch.flips, num_classes)
+    post = box_head.post_processor
+    merged = _C.merge_view_detections(boxes, scores, segments, num_classes, post.score_thresh)
+    results = post.filter_merged(merged, sizes, num_classes, slice_candidates=NMS_SLICE_CANDIDATES)
+    if cfg.MODEL.MASK_ON:
+        results = model.segment(features, results)
+    return results

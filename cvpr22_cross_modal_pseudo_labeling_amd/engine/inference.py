@@ -19,18 +19,31 @@ import torch
 import torch.distributed as dist
 
 from . import comm
+from .bbox_aug import im_detect_bbox_aug, model_cfg
+from ..data.transforms import ViewBatch
 from ..modeling.structures import BoxList
 
 
 @torch.no_grad()
 def compute_on_dataset(model, batches, device, timer=None):
-    """batches: iterable of (images, targets, image_ids) -> {image_id: BoxList on CPU} (inference.py:25-47)."""
+    """batches: iterable of (images, targets, image_ids) -> {image_id: BoxList on CPU} (inference.py:25-47).  A batch whose
+    images are a ``ViewBatch`` (TEST.BBOX_AUG: build_transforms(cfg, False) made every view) goes through
+    ``im_detect_bbox_aug`` (inference.py:34-35).  A model configured with TEST.BBOX_AUG.ENABLED that is handed ready-made
+    images instead raises: the views are made from raw bytes, which such a stream (``tools/test_net.py``'s float32 synthetic
+    one) does not have -- ``tools/infer_net.py`` reads datasets through the raw input path."""
     model.eval()
+    augmented = model_cfg(model) is not None and model_cfg(model).TEST.BBOX_AUG.ENABLED
     results = {}
     cpu = torch.device("cpu")
     for images, targets, image_ids in batches:
         t0 = time.perf_counter()
-        output = model(images.to(device), targets)
+        if isinstance(images, ViewBatch):
+            output = im_detect_bbox_aug(model, images.to(device))
+        elif augmented:
+            raise ValueError("TEST.BBOX_AUG.ENABLED, but the batch holds already-transformed images: the views are made from "
+                             "raw bytes by build_transforms(cfg, is_train=False); tools/infer_net.py feeds such a stream")
+        else:
+            output = model(images.to(device), targets)
         if timer is not None:
             if torch.device(device).type == "cuda":
                 torch.cuda.synchronize()

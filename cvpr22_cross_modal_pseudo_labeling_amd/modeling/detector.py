@@ -91,6 +91,30 @@ class GeneralizedRCNN(nn.Module):
         return result
 
 
+    # -- test-time augmentation (engine/bbox_aug.py): the evaluation pass in two halves, no module state touched ------
+    @torch.no_grad()
+    def detect_unfiltered(self, images):
+        """-> (features, [BoxList with ``scores`` [n * C]]): backbone, RPN and box head of the evaluation pass, every box
+        of every class kept (no score cut, no NMS) -- one view's input to ``_C.merge_view_detections``."""
+        _require_eval(self)
+        images = to_image_list(images)
+        features = self.backbone(images.tensors)
+        proposals, _ = self.rpn(images, features, None)
+        _, detections, _ = self.roi_heads(features, proposals, None, bbox_only=True, unfiltered=True)
+        return features, detections
+
+    @torch.no_grad()
+    def segment(self, features, detections):
+        """The mask head's evaluation pass on given boxes (BoxLists with ``labels``) -> the detections with ``mask``."""
+        _require_eval(self)
+        return self.roi_heads["mask"](features, detections)[1]
+
+
+def _require_eval(model):
+    if model.training:
+        raise RuntimeError("evaluation-only entry point: call model.eval() first (no module state is changed here)")
+
+
 class STGeneralizedRCNN(nn.Module):
     LOSS_NAMES = ("loss_box_reg", "loss_classifier", "loss_mask")
 
@@ -229,6 +253,25 @@ class STGeneralizedRCNN(nn.Module):
         frozen = self.forward_frozen(images, targets, features=features)
         return self.forward_student(frozen, targets, eps=eps)
 
+    # -- test-time augmentation (engine/bbox_aug.py): the evaluation pass in two halves, no module state touched ------
+    @torch.no_grad()
+    def detect_unfiltered(self, images):
+        """-> (features, [BoxList with ``scores`` [n * C]]): backbone, RPN and the student's box head as ``forward``
+        runs them in evaluation, every box of every class kept."""
+        _require_eval(self)
+        images = to_image_list(images)
+        features = self.backbone(images.tensors)
+        proposals, _ = self.rpn(images, features, None)
+        _, detections, _ = self.roi_heads_student(features, proposals, None, bbox_only=True, unfiltered=True,
+                                                  cls_embs=self.combine_embs(self.roi_heads["box"].predictor.cls_score))
+        return features, detections
+
+    @torch.no_grad()
+    def segment(self, features, detections):
+        """The student's mask head, evaluation pass, on given boxes (BoxLists with ``labels``) -> detections with ``mask``."""
+        _require_eval(self)
+        return self.roi_heads_student["mask"](features, detections)[1]
+
     @torch.no_grad()
     def forward_frozen(self, images, targets, features=None):
         """Everything of the training step that only uses FROZEN modules (trunk, RPN, teacher heads; __init__ turns
@@ -352,6 +395,9 @@ def check_supported(cfg):
             node = getattr(node, part)
         if node != only:
             raise NotImplementedError(f"{key} = {node!r}: only {only!r} is built (the hot path of the shipped configurations)")
+    if cfg.TEST.BBOX_AUG.ENABLED and cfg.MODEL.GT_BOX_EVAL:
+        raise NotImplementedError("TEST.BBOX_AUG.ENABLED with MODEL.GT_BOX_EVAL: ground-truth boxes are classified once, "
+                                  "there are no views to merge")
 
 
 def build_detection_model(cfg):

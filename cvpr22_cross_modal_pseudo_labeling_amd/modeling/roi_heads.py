@@ -18,6 +18,8 @@ projection, no per-mask python loop there), the fg/bg class weights are built on
 device instead of a hard-coded ``.cuda()``, and the mask head handles any number of
 images per process.
 """
+import bisect
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -323,7 +325,9 @@ class PostProcessor(nn.Module):
         if self.gt_box_eval:
             self.score_thresh = self.nms = 1.0
 
-    def forward(self, x, boxes):
+    def forward(self, x, boxes, unfiltered=False):
+        """``unfiltered``: hand out every box of every class with its score ([n * C] rows), as the teacher's passes do --
+        the caller filters later (test-time augmentation merges the views first: ``filter_merged``)."""
         class_logits, box_regression = x
         class_prob = F.softmax(class_logits, -1)
         if self.gt_box_eval and not self.is_teacher:  # inference.py:82-89: prob of the box's own class + 1.1, zero elsewhere
@@ -350,9 +354,94 @@ class PostProcessor(nn.Module):
         for prob, prop, b in zip(class_prob.split(per_img, 0), proposals.split(per_img, 0), boxes):
             boxlist = BoxList(prop.reshape(-1, 4), b.size)  # already clipped (remove_empty=False: nothing else to do)
             boxlist.add_field("scores", prob.reshape(-1))
-            if not self.is_teacher:
+            if not self.is_teacher and not unfiltered:
                 boxlist = self.filter_results(boxlist, num_classes)
             results.append(boxlist)
+        return results
+
+    def filter_merged(self, merged, image_sizes, num_classes, max_candidates=None, slice_candidates=None):
+        """``filter_results`` for the candidate list of ``_C.merge_view_detections`` (``merged`` = cand_boxes, cand_scores,
+        cand_group, offsets; already above the score threshold and class-major per image): per-class NMS, then the
+        DETECTIONS_PER_IMG best of every image -> one BoxList per image of ``image_sizes`` ((width, height)), with
+        ``scores`` and int64 ``labels``.  On the device ONE grouped NMS serves the whole batch (group = image * C + class).
+        ``max_candidates`` (default: what ``_C.nms_grouped`` accepts, its workspace grows with K^2) cuts a longer list into
+        consecutive slices at (image, class) boundaries, one NMS each; a single class of one image above it raises.
+        ``slice_candidates`` asks for slices of about that size although the list would fit one call -- a call visits every
+        pair of its candidates, so two half-size calls do half the work -- and never raises: a larger single run gets a
+        slice of its own, up to ``max_candidates``.  Same detections either way.  Host tensors: the reference's per-class
+        loop (``filter_results_per_class``) over the runs of the list."""
+        cand_boxes, cand_scores, cand_group, offsets = merged
+        c, b = int(num_classes), len(image_sizes)
+        if offsets.numel() != b * c + 1:
+            raise ValueError(f"filter_merged: offsets must have {b} * {c} + 1 entries, got {offsets.numel()}")
+        limit = _C.NMS_MAX_CANDIDATES if max_candidates is None else int(max_candidates)
+        k = cand_boxes.shape[0]
+        if not cand_boxes.is_cuda:
+            return self._filter_merged_per_class(merged, image_sizes, c)
+        if k == 0:
+            keep = torch.zeros((0,), dtype=torch.int64, device=cand_boxes.device)
+        elif k <= (limit if slice_candidates is None else min(limit, int(slice_candidates))):
+            keep = _C.nms_grouped(cand_boxes, cand_scores, cand_group, self.nms)
+        else:
+            starts = offsets.tolist()
+            if slice_candidates is not None:
+                limit = min(limit, max(int(slice_candidates), max(hi - lo for lo, hi in zip(starts, starts[1:]))))
+            parts, lo = [], 0
+            while lo < k:
+                hi = starts[bisect.bisect_right(starts, lo + limit) - 1]   # the last run boundary within the limit
+                if hi <= lo:
+                    run = bisect.bisect_right(starts, lo) - 1               # the (non-empty) run that starts at lo
+                    raise RuntimeError(f"filter_merged: class {run % c} of image {run // c} has {starts[run + 1] - lo} "
+                                       f"candidates, more than one NMS call takes ({limit})")
+                keep_part, num = _C.nms_grouped_padded(cand_boxes[lo:hi], cand_scores[lo:hi], cand_group[lo:hi], self.nms)
+                parts.append((keep_part, num, lo))
+                lo = hi
+            keep = _cat([kp[: int(num.item())] + at for kp, num, at in parts], 0)
+        bounds = torch.searchsorted(keep, offsets[::c].to(torch.int64)).tolist()   # the images' shares of the survivors
+        results = []
+        for i, size in enumerate(image_sizes):
+            idx = keep[bounds[i]:bounds[i + 1]]
+            result = BoxList(cand_boxes[idx], size)
+            result.add_field("scores", cand_scores[idx])
+            result.add_field("labels", cand_group[idx].to(torch.int64) - i * c)
+            n = len(result)
+            if n > self.detections_per_img > 0:
+                s = result.get_field("scores")
+                thresh = torch.kthvalue(s, n - self.detections_per_img + 1).values
+                result = result[torch.nonzero(s >= thresh).squeeze(1)]
+            results.append(result)
+        return results
+
+    def _filter_merged_per_class(self, merged, image_sizes, num_classes):
+        """inference.py:137-163 over a merged candidate list: the (image, class) runs are what ``nonzero(scores > thresh)``
+        selects from the concatenated views, in that order."""
+        cand_boxes, cand_scores, _, offsets = merged
+        starts = offsets.tolist()
+        results = []
+        for i, size in enumerate(image_sizes):
+            result = []
+            for j in range(1, num_classes):
+                lo, hi = starts[i * num_classes + j], starts[i * num_classes + j + 1]
+                if hi == lo:
+                    continue
+                cls_boxes = BoxList(cand_boxes[lo:hi], size)
+                cls_boxes.add_field("scores", cand_scores[lo:hi])
+                cls_boxes = boxlist_nms(cls_boxes, self.nms)
+                cls_boxes.add_field("labels", torch.full((len(cls_boxes),), j, dtype=torch.int64, device=cand_scores.device))
+                result.append(cls_boxes)
+            if not result:
+                empty = BoxList(cand_boxes.new_zeros((0, 4)), size)
+                empty.add_field("scores", cand_scores.new_zeros((0,)))
+                empty.add_field("labels", torch.zeros((0,), dtype=torch.int64, device=cand_scores.device))
+                results.append(empty)
+                continue
+            result = cat_boxlist(result)
+            n = len(result)
+            if n > self.detections_per_img > 0:
+                s = result.get_field("scores")
+                thresh = torch.kthvalue(s, n - self.detections_per_img + 1).values
+                result = result[torch.nonzero(s >= thresh).squeeze(1)]
+            results.append(result)
         return results
 
     def filter_results(self, boxlist, num_classes):  # inference.py:121-163
@@ -419,7 +508,7 @@ class ROIBoxHead(nn.Module):
                 p.requires_grad = False
         self.is_teacher = is_teacher
 
-    def forward(self, features, proposals, targets=None, cls_embs=None):
+    def forward(self, features, proposals, targets=None, cls_embs=None, unfiltered=False):
         if self.training:
             with torch.no_grad():
                 proposals = self.loss_evaluator.subsample(proposals, targets)
@@ -433,7 +522,7 @@ class ROIBoxHead(nn.Module):
         x = feats.pooled if (pooled_only and feats.pooled is not None) else feats.maps
         class_logits, box_regression = self.predictor(feats.pooled if feats.pooled is not None else x, cls_embs)
         if not self.training:
-            return x, self.post_processor((class_logits, box_regression), proposals), {}
+            return x, self.post_processor((class_logits, box_regression), proposals, unfiltered=unfiltered), {}
         loss_classifier, loss_box_reg = self.loss_evaluator(class_logits, box_regression, proposals)
         return x, proposals, dict(loss_classifier=loss_classifier, loss_box_reg=loss_box_reg)
 
@@ -862,7 +951,7 @@ class CombinedROIHeads(nn.ModuleDict):
         return out
 
     def forward(self, features, proposals, targets=None, bbox_only=False, compute_uncertain=False, eps=None,
-                is_eval_func=False, cls_embs=None):
+                is_eval_func=False, cls_embs=None, unfiltered=False):
         losses, package_x = {}, {}
         # MODEL.GT_BOX_EVAL (roi_heads.py:31-49): the evaluation pass of a detector -- not the teacher's passes inside
         # generate_pseudo_label, which leave ``is_eval_func`` False -- classifies and segments the ground-truth boxes
@@ -874,7 +963,7 @@ class CombinedROIHeads(nn.ModuleDict):
                 det = t.copy_with_fields(["labels"])
                 det.add_field("objectness", t.get_field("labels") * 0.0 + 1.0)
                 proposals.append(det.to(device))
-        x, detections, loss_box = self.box(features, proposals, targets, cls_embs)
+        x, detections, loss_box = self.box(features, proposals, targets, cls_embs, unfiltered=unfiltered)
         if gt_boxes:
             for det, tar in zip(detections, targets):
                 assert len(det) == len(tar), "GT_BOX_EVAL keeps one detection per ground-truth box"

@@ -213,6 +213,38 @@ int ovis_box_decode_f32(const float* rel_codes, long codes_row_stride, const flo
                         float weight_h, float xform_clip, int num_images, const int32_t* rows_per_image,
                         const float* image_wh, float* decoded, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Merge of the detections of test-time-augmentation views   mb/engine/bbox_aug.py:53-60 (flip back, resize to the first
+ *   view's size, concatenate), mb/structures/bounding_box.py:91-166, mb/modeling/roi_heads/box_head/inference.py:137-143
+ *   (`scores > thresh` per class)                                                                 csrc/view_merge.hip
+ * boxes [num_rows, num_classes, 4] / scores [num_rows, num_classes] f32: every view's class-specific detections in the
+ * view's own frame.  A SEGMENT is the contiguous rows of one (image, view); the records are HOST arrays, image-major then
+ * view order: segments [num_segments, 5] int32 = (row_start, row_count >= 0, image, view_width, flip), ratios
+ * [num_segments, 2] f32 = (ratio_w, ratio_h).  At most OVIS_VIEW_MERGE_MAX_SEGMENTS per call (they travel as kernel
+ * arguments; more: OVIS_ERANGE); a longer list is several calls over whole images, each with its own part of `counts`.
+ * Images of one call are consecutive and each owns at least one segment; rows outside [0, num_rows): OVIS_EINVAL before any
+ * launch.  A box becomes ((W - x2) - 1, y1, (W - x1) - 1, y2) when flip, then (x * ratio_w, y * ratio_h), as two float
+ * operations each in that order; class c >= 1 of a row is a candidate iff scores[row, c] > score_thresh (NaN: no).
+ * The candidate list is ordered image, class, segment, row.  Three enqueue-only steps, one launch each:
+ *   count    counts [num_counts] int32, num_counts = num_classes * sum over the call's segments of
+ *            max(1, ceil(row_count / OVIS_VIEW_MERGE_TILE_ROWS)); laid out [image][class][tile of the image]
+ *   scan     exclusive scan of ALL calls' counts in place (one workgroup); *total = K, the number of candidates
+ *   scatter  starts = the scanned counts of this call; cand_boxes [K, 4] (16-byte aligned), cand_scores [K], cand_group [K]
+ *            int32 = image * num_classes + class, offsets [num_images * num_classes (+ 1 for K, written by scan)] int32 =
+ *            the start of every (image, class) run of the call's images.  Nothing is written at or beyond num_candidates.
+ * The placement is count -> scan -> rank by wave64 ballot: deterministic, no atomics.  num_rows * num_classes < 2^31.
+ * ---------------------------------------------------------------------------------- */
+#define OVIS_VIEW_MERGE_MAX_SEGMENTS 64
+#define OVIS_VIEW_MERGE_TILE_ROWS 64
+int ovis_view_merge_count_f32(const float* scores, long num_rows, int num_classes, int num_images, const int32_t* segments,
+                              const float* ratios, int num_segments, float score_thresh, int32_t* counts, long num_counts,
+                              void* stream);
+int ovis_view_merge_scan_i32(int32_t* counts, long num_counts, int32_t* total, void* stream);
+int ovis_view_merge_scatter_f32(const float* boxes, const float* scores, long num_rows, int num_classes, int num_images,
+                                const int32_t* segments, const float* ratios, int num_segments, float score_thresh,
+                                const int32_t* starts, long num_counts, long num_candidates, float* cand_boxes,
+                                float* cand_scores, int32_t* cand_group, int32_t* offsets, void* stream);
+
 /* Pooler.convert_to_roi_format (mb/modeling/poolers.py:73-86): boxes[i] (HOST array of device pointers) holds image i's
  * [boxes_per_image[i], 4] boxes (boxes_per_image: HOST array); rois [sum, 5] receives (id_i, x1, y1, x2, y2) rows in list
  * order, id_i = image_ids[i] (HOST array) or i when image_ids is NULL.  One launch per OVIS_BOX_DECODE_MAX_IMAGES images. */

@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, polygons, transform, render (``--ops paste,polygons,transform,render``).
+Opt-in ops outside the default list: topk, paste, polygons, transform, render, view_merge (``--ops paste,...,view_merge``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -353,6 +353,99 @@ def main():
                     "paste_masks_plus_torch_ms": ms_torch, "paste_masks_plus_torch_rounds_ms": [round(v, 4) for v in t_ms],
                     "paste_masks_plus_torch_bytes_MB": nbytes_torch / 1e6, "mask_bytes_MB": k_ * px / 1e6,
                     "torch_over_kernel": ms_torch / ms, "outputs_equal": equal})
+    if "view_merge" in ops:  # opt-in: TEST.BBOX_AUG merge + filter, 2 images x 6 views x 1000 proposals x 66 classes
+        from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.roi_heads import PostProcessor
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import BoxList
+
+        n_img, rows, nc = 2, 1000, 66
+        views = [((1066, 800), 0), ((1066, 800), 1), ((533, 400), 0), ((533, 400), 1), ((1599, 1200), 0), ((1599, 1200), 1)]
+        post = PostProcessor(get_defaults())
+        lists, segments, row = [], [], 0
+        for i in range(n_img):
+            lists.append([])
+            for (w, h), flip in views:
+                xy = torch.rand(rows, nc, 2, generator=g) * torch.tensor([w * 0.7, h * 0.7])
+                wh = torch.rand(rows, nc, 2, generator=g) * torch.tensor([w * 0.3, h * 0.3]) + 4
+                bl = BoxList(torch.cat([xy, (xy + wh).clamp(max=min(w, h) - 1)], 2).reshape(-1, 4).to(dev), (w, h))
+                # softmax scores as the box head makes them: a few per cent of the (row, class) pairs pass SCORE_THRESH 0.05
+                bl.add_field("scores", torch.softmax(torch.randn(rows, nc, generator=g) * 2.0, 1).reshape(-1).to(dev))
+                lists[i].append((bl, flip))
+                segments.append((row, rows, i, w, flip, float(views[0][0][0]) / float(w), float(views[0][0][1]) / float(h)))
+                row += rows
+        all_boxes = torch.cat([bl.bbox for per in lists for bl, _ in per]).reshape(-1, nc, 4)
+        all_scores = torch.cat([bl.get_field("scores") for per in lists for bl, _ in per]).reshape(-1, nc)
+        sizes = [views[0][0]] * n_img
+
+        from cvpr22_cross_modal_pseudo_labeling_amd.engine.bbox_aug import NMS_SLICE_CANDIDATES
+
+        def kernel_route(limit=NMS_SLICE_CANDIDATES):  # as engine/bbox_aug.py::im_detect_bbox_aug runs the stage
+            merged = _C.merge_view_detections(all_boxes, all_scores, segments, nc, post.score_thresh)
+            return post.filter_merged(merged, sizes, nc, slice_candidates=limit), merged[0].shape[0]
+
+        def boxlist_route():  # engine/bbox_aug.py:53-69 of the reference with the tensors on the device
+            out = []
+            for per in lists:
+                mapped = []
+                for bl, flip in per:
+                    if flip:
+                        bl = bl.transpose(0)
+                    mapped.append(bl if not mapped else bl.resize(mapped[0].size))
+                cat = BoxList(torch.cat([m.bbox for m in mapped]), mapped[0].size)
+                cat.add_field("scores", torch.cat([m.get_field("scores") for m in mapped]))
+                out.append(post.filter_results(cat, nc))
+            return out
+
+        def candidates_by_tensor_ops():  # the part of boxlist_route the merge kernels replace: map, cat, threshold, gather
+            out = []
+            for per in lists:
+                mapped = []
+                for bl, flip in per:
+                    if flip:
+                        bl = bl.transpose(0)
+                    mapped.append(bl if not mapped else bl.resize(mapped[0].size))
+                boxes = torch.cat([m.bbox for m in mapped]).reshape(-1, nc, 4)
+                scores = torch.cat([m.get_field("scores") for m in mapped]).reshape(-1, nc)
+                cls, row = (scores.t()[1:] > post.score_thresh).nonzero(as_tuple=True)  # PostProcessor.filter_results
+                out.append((boxes[row, cls + 1], scores[row, cls + 1], cls + 1))
+            return out
+
+        def kernels(fn):  # device kernels of one call, from the profiler; None where it is unavailable
+            try:
+                from torch.profiler import ProfilerActivity, profile
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    fn()
+                    torch.cuda.synchronize()
+                return sum(str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower() and "memset" not in e.name.lower()
+                           for e in prof.events())
+            except Exception:  # noqa: BLE001 -- a number for the report, not part of the result
+                return None
+
+        got, k_ = kernel_route()
+        want = boxlist_route()
+        equal = all(torch.equal(a.bbox, b.bbox) and torch.equal(a.get_field("scores"), b.get_field("scores"))
+                    and torch.equal(a.get_field("labels"), b.get_field("labels")) for a, b in zip(got, want))
+        k_ms, t_ms = [], []
+        for _ in range(3):  # the two routes alternate inside this one call
+            k_ms.append(timeit(kernel_route, args.iters))
+            t_ms.append(timeit(boxlist_route, args.iters))
+        # the parts: the merge alone, and the filter at other slice limits (the grouped NMS visits all K^2 / 2 pairs of a call)
+        def merge_only():
+            return _C.merge_view_detections(all_boxes, all_scores, segments, nc, post.score_thresh)
+
+        merge_ms, tensor_ms = timeit(merge_only, args.iters), timeit(candidates_by_tensor_ops, args.iters)
+        by_limit = {str(lim): round(timeit(lambda: kernel_route(lim), args.iters), 4)
+                    for lim in (_C.NMS_MAX_CANDIDATES, 32768, 16384, 8192, 4096, 2048)}
+        res.append({"op": "merge_view_detections + filter_merged", "shape": f"{n_img} images x {len(views)} views x {rows} rows x {nc} classes",
+                    "ms": sorted(k_ms)[1], "rounds_ms": [round(v, 4) for v in k_ms], "candidates": k_,
+                    "nms_slice_candidates": NMS_SLICE_CANDIDATES, "merge_only_ms": merge_ms, "merge_only_kernels": kernels(merge_only),
+                    "candidates_by_tensor_ops_ms": tensor_ms, "candidates_by_tensor_ops_kernels": kernels(candidates_by_tensor_ops),
+                    "ms_by_slice_limit": by_limit,
+                    "fraction_above_threshold": k_ / (all_scores.numel() * (nc - 1) / nc),
+                    "boxlist_route_ms": sorted(t_ms)[1], "boxlist_route_rounds_ms": [round(v, 4) for v in t_ms],
+                    "boxlist_over_kernel": sorted(t_ms)[1] / sorted(k_ms)[1],
+                    "kernels": kernels(kernel_route), "boxlist_route_kernels": kernels(boxlist_route),
+                    "outputs_equal": equal})
     for r_ in res:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r_.items()}))
 

@@ -14,7 +14,10 @@ sizes.  ``--visualize N`` (rank 0) also renders the first N images of every test
 against its own annotation file on the device (engine/coco_eval.py: COCO box AP, and mask AP when MODEL.MASK_ON, plus AP50
 per class and per seen / unseen split), logs the reference's ``Task: ... / names / values`` table and writes
 ``<OUTPUT_DIR>/inference/<name>/coco_results.json``; it needs OUTPUT_DIR and MODEL.DEVICE cuda -- there is no host-only
-scoring.  ``tools/test_net.py`` stays the synthetic-stream tool; LVIS scoring is outside this build.
+scoring.  ``TEST.BBOX_AUG.ENABLED True`` (with H_FLIP / SCALES / MAX_SIZE / SCALE_H_FLIP) turns on multi-scale / flip testing:
+``build_transforms(cfg, False)`` then makes every view on the device from the one upload and ``engine/bbox_aug.py`` merges the
+views' detections; the saved BoxLists are in the first view's frame and keep their masks.  ``tools/test_net.py`` stays the
+synthetic-stream tool; LVIS scoring is outside this build.
 """
 import argparse
 import json
