@@ -842,6 +842,62 @@ def paste_masks(probs, boxes, image_size, threshold=0.5):
     return out
 
 
+def _pasted_runs(name, probs, boxes, sizes, threshold, with_chars):
+    """-> (counts int32 [total], offsets int64 [P + 1], the strings' lengths int32 [P] or None), all on the device.  The
+    one host read: the P run totals, which also carry the kernel's verdict on every size."""
+    probs, boxes, sizes = _dev(probs, "probs"), _dev(boxes, "boxes"), _dev(sizes, "sizes", torch.int32)
+    if probs.dim() != 3 or probs.shape[1] != probs.shape[2] or probs.shape[1] < 1 or boxes.shape != (probs.shape[0], 4) \
+            or sizes.shape != (probs.shape[0], 2):
+        raise RuntimeError(f"{name}: expected probs [P,M,M], boxes [P,4] and sizes int32 [P,2] (height, width)")
+    p, m, dev = probs.shape[0], probs.shape[1], probs.device
+    num_runs = torch.empty(p, dtype=torch.int32, device=dev)
+    with _on(dev):
+        rc = _L.ovis_pasted_rle_count(probs.data_ptr(), boxes.data_ptr(), sizes.data_ptr(), p, m, float(threshold),
+                                      num_runs.data_ptr(), _stream())
+    _lib.check(rc, name)
+    totals = num_runs.cpu()
+    if p and int(totals.min()) < 1:
+        raise RuntimeError(f"{name}: every size needs height >= 1, width >= 1 and height * width <= 0x7fffffef")
+    offsets_host = torch.zeros(p + 1, dtype=torch.int64)
+    torch.cumsum(totals, 0, out=offsets_host[1:])
+    offsets = offsets_host.to(dev)
+    counts = torch.empty(int(offsets_host[-1]), dtype=torch.int32, device=dev)
+    num_chars = torch.empty(p, dtype=torch.int32, device=dev) if with_chars else None
+    with _on(dev):
+        rc = _L.ovis_pasted_rle_runs(probs.data_ptr(), boxes.data_ptr(), sizes.data_ptr(), p, m, float(threshold),
+                                     offsets.data_ptr(), counts.data_ptr(), num_chars.data_ptr() if with_chars else 0, _stream())
+    _lib.check(rc, name)
+    return counts, offsets, num_chars
+
+
+def pasted_masks_runs(probs, boxes, sizes, threshold=0.5):
+    """(counts int32 [total], offsets int64 [P + 1]), both on the device: ``counts[offsets[p]:offsets[p + 1]]`` is the
+    uncompressed COCO RLE (pycocotools' ``rleEncode``: column-major, zeros first) of the mask ``paste_masks`` would make of
+    probs[p] [M, M] and boxes[p] xyxy on an image of sizes[p] = (height, width) -- per mask, so one call serves images of
+    different sizes (``ovis_pasted_rle_count`` / ``_runs``; coco_eval.py:108-144).  No canvas is written; the host reads
+    the P run totals once.  Device tensors only, as in the reference there is no host form."""
+    counts, offsets, _ = _pasted_runs("pasted_masks_runs", probs, boxes, sizes, threshold, False)
+    return counts, offsets
+
+
+def pasted_masks_rle(probs, boxes, sizes, threshold=0.5):
+    """(data uint8 [total_chars], offsets int64 [P + 1]), both on the device: ``bytes(data[offsets[p]:offsets[p + 1]])`` is
+    the compressed ``counts`` string (pycocotools' ``rleToString``) of mask p of ``pasted_masks_runs`` -- what
+    ``mask_util.encode`` returns for the pasted mask (``ovis_pasted_rle_*``; coco_eval.py:139-144).  Two host reads: the
+    run totals and the string lengths."""
+    counts, run_offsets, num_chars = _pasted_runs("pasted_masks_rle", probs, boxes, sizes, threshold, True)
+    p, dev = num_chars.shape[0], num_chars.device
+    offsets_host = torch.zeros(p + 1, dtype=torch.int64)
+    torch.cumsum(num_chars.cpu(), 0, out=offsets_host[1:])
+    offsets = offsets_host.to(dev)
+    data = torch.empty(int(offsets_host[-1]), dtype=torch.uint8, device=dev)
+    with _on(dev):
+        rc = _L.ovis_pasted_rle_string(counts.data_ptr(), run_offsets.data_ptr(), offsets.data_ptr(), p, data.data_ptr(),
+                                       _stream())
+    _lib.check(rc, "pasted_masks_rle")
+    return data, offsets
+
+
 def render_instances(image, maps, boxes, colors, kinds=None, params=None, alpha=0.5, outline_colors=None, outline_thickness=2):
     """uint8 [H, W, 3]: box outlines, filled masks and uncertainty heat layers composited onto ``image`` uint8 [H, W, 3]
     (``ovis_render_instances_u8``; engine/inference.py:519-589 over the Masker paste).  Layer i is (maps[i] [M, M] f32,

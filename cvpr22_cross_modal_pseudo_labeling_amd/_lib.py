@@ -37,6 +37,9 @@ SIGNATURES = {
     "ovis_sample_fg_bg": (_i, [_vp, _i, _i, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "ovis_project_pasted_masks_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "ovis_paste_masks_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "ovis_pasted_rle_count": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
+    "ovis_pasted_rle_runs": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "ovis_pasted_rle_string": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "ovis_render_instances_u8": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp]),
     "ovis_nms_presorted_workspace_bytes": (_sz, [_i, _i]),
     "ovis_nms_presorted_batched_f32": (_i, [_vp, _vp, _i, _i, _f, _i, _i, _vp, _sz, _vp, _vp, _vp]),

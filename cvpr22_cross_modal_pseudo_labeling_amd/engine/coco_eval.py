@@ -40,6 +40,9 @@ AREA_RANGES = np.array([[0, 1e10], [0, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1
 METRICS = ("AP", "AP50", "AP75", "APs", "APm", "APl")
 MAX_CHUNK_IMAGES = 4096
 MAX_CALL_MASKS = 65535  # what one paste_masks / polygons_to_masks call takes: masks, instances or polygons
+# the masks of one pasted_masks_rle call of the results export (engine/coco_results.py): inside MAX_CALL_MASKS, and small
+# enough that a chunk's maps (25 MB at M = 28) and runs (a few hundred int32 per mask) are no burden on the device
+MAX_EXPORT_MASKS = 8192
 
 
 # ---- host: COCOeval.accumulate / summarize --------------------------------------------------------------------------------
@@ -176,15 +179,36 @@ def _ground_truth(dataset):
     return cat_ids, images
 
 
+def detection_boxes(pred, width, height):
+    """(xyxy, xywh) float32 [K, 4] on the host: the prediction's boxes resized to the file's ``width`` x ``height``, and the
+    reference's ``BoxList.convert("xywh")`` of them, w = x2 - x1 + 1 (coco_eval.py:82-83)."""
+    xyxy = BoxList(pred.bbox.detach().cpu(), pred.size).resize((width, height)).bbox
+    x1, y1, x2, y2 = xyxy.unbind(1)
+    return xyxy, torch.stack((x1, y1, x2 - x1 + 1, y2 - y1 + 1), 1)
+
+
+def mask_maps(pred):
+    """The prediction's ``mask`` field, which must hold the mask head's [K, 1, M, M] probability maps."""
+    if not pred.has_field("mask"):
+        raise ValueError("evaluate_coco: segm scoring needs the predictions' 'mask' field (MODEL.MASK_ON)")
+    maps = pred.get_field("mask")
+    if not torch.is_tensor(maps) or not maps.is_floating_point() or maps.dim() != 4 or maps.shape[1] != 1 \
+            or maps.shape[2] != maps.shape[3] or maps.shape[0] != len(pred):
+        raise ValueError(
+            f"evaluate_coco: field 'mask' must hold the mask head's [K, 1, M, M] probability maps, got "
+            f"{getattr(maps, 'dtype', type(maps).__name__)} {tuple(getattr(maps, 'shape', ()))}; masks that are already "
+            "pasted into the image (MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS True) cannot be scored -- run inference with "
+            "MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS False")
+    return maps
+
+
 def _detections(pred, image, label_to_cat, with_masks):
     """One image's prediction as rows sorted by (category index, descending score), stably, at most 100 per category
     (coco_eval.py:71-105 / :108-162 and the ``dt[0:maxDets[-1]]`` of COCOeval.computeIoU)."""
     empty = {"cats": np.zeros(0, np.int64), "scores": np.zeros(0), "xywh": np.zeros((0, 4)), "xyxy": None, "maps": None}
     if pred is None or len(pred) == 0:
         return empty
-    xyxy = BoxList(pred.bbox.detach().cpu(), pred.size).resize((image["width"], image["height"])).bbox
-    x1, y1, x2, y2 = xyxy.unbind(1)
-    xywh = torch.stack((x1, y1, x2 - x1 + 1, y2 - y1 + 1), 1)  # float32, as BoxList.convert("xywh") of the reference
+    xyxy, xywh = detection_boxes(pred, image["width"], image["height"])
     scores = pred.get_field("scores").detach().cpu().double().numpy()
     cats = np.asarray([label_to_cat[int(l)] for l in pred.get_field("labels").tolist()], dtype=np.int64)
     order = np.lexsort((-scores, cats))  # stable: ties keep prediction order
@@ -192,16 +216,7 @@ def _detections(pred, image, label_to_cat, with_masks):
     order = order[rank < MAX_DETS[-1]]
     out = {"cats": cats[order], "scores": scores[order], "xywh": xywh.double().numpy()[order], "xyxy": None, "maps": None}
     if with_masks:
-        if not pred.has_field("mask"):
-            raise ValueError("evaluate_coco: segm scoring needs the predictions' 'mask' field (MODEL.MASK_ON)")
-        maps = pred.get_field("mask")
-        if not torch.is_tensor(maps) or not maps.is_floating_point() or maps.dim() != 4 or maps.shape[1] != 1 \
-                or maps.shape[2] != maps.shape[3] or maps.shape[0] != len(pred):
-            raise ValueError(
-                f"evaluate_coco: field 'mask' must hold the mask head's [K, 1, M, M] probability maps, got "
-                f"{getattr(maps, 'dtype', type(maps).__name__)} {tuple(getattr(maps, 'shape', ()))}; masks that are already "
-                "pasted into the image (MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS True) cannot be scored -- run inference with "
-                "MODEL.ROI_MASK_HEAD.POSTPROCESS_MASKS False")
+        maps = mask_maps(pred)
         index = torch.from_numpy(order)
         out["maps"], out["xyxy"] = maps.detach().cpu()[index, 0].float(), xyxy[index]
     return out

@@ -551,6 +551,29 @@ int ovis_project_pasted_masks_f32(const float* mask_probs, const float* gt_boxes
  * prob_resolution <= 120, num <= 65535, image_height * image_width < 2^31, else OVIS_ERANGE. */
 int ovis_paste_masks_u8(const float* mask_probs, const float* boxes, int num, int prob_resolution, int image_height,
                         int image_width, float threshold, uint8_t* out, void* stream);
+/* ovis_pasted_rle_*: the COCO run-length encodings of the masks ovis_paste_masks_u8 would write, without writing them --
+ * prepare_for_coco_segmentation (mb/data/datasets/evaluation/coco/coco_eval.py:108-162: Masker paste, copy to the host,
+ * pycocotools' encode per mask) for a chunk of images in three launches and two small host reads.  Mask p is
+ * (mask_probs[p] [prob_resolution, prob_resolution] f32, boxes[p] xyxy in the frame of its image (the array 16-byte
+ * aligned), image_sizes[p] = (height, width) int32), thresholded with `>`; its pixels are those of ovis_paste_masks_u8
+ * (csrc/pasted_geom.h), bit for bit.  Runs: pycocotools' rleEncode -- column-major, zeros first, so a mask whose pixel
+ * (0, 0) is set starts with a count of 0, an empty one is [height * width].  Text: pycocotools' rleToString.  The order
+ * of every output comes from scans: no atomics, the same bytes on every call.
+ *   _count:  num_runs[p] = the number of counts of mask p (>= 1), or -1 when image_sizes[p] has height < 1, width < 1 or
+ *            height * width > 0x7fffffef (such a mask is skipped by _runs; the caller refuses it).
+ *   _runs:   run_offsets [num + 1] int64 = the exclusive sum of num_runs (made by the caller); runs[run_offsets[p] ..
+ *            run_offsets[p + 1]) = the counts of mask p, int32; never written outside that range.  num_chars[p] = the
+ *            length of its compressed string (NULL: not computed).
+ *   _string: char_offsets [num + 1] int64 = the exclusive sum of num_chars; out[char_offsets[p] .. char_offsets[p + 1]) =
+ *            the `counts` string of mask p (ASCII, not terminated).
+ * Enqueue only.  num == 0: OVIS_OK without a launch.  prob_resolution <= 120, num <= 65535, else OVIS_ERANGE. */
+int ovis_pasted_rle_count(const float* mask_probs, const float* boxes, const int32_t* image_sizes, int num,
+                          int prob_resolution, float threshold, int32_t* num_runs, void* stream);
+int ovis_pasted_rle_runs(const float* mask_probs, const float* boxes, const int32_t* image_sizes, int num,
+                         int prob_resolution, float threshold, const int64_t* run_offsets, int32_t* runs,
+                         int32_t* num_chars, void* stream);
+int ovis_pasted_rle_string(const int32_t* runs, const int64_t* run_offsets, const int64_t* char_offsets, int num,
+                           uint8_t* out, void* stream);
 /* ovis_render_instances_u8: the prediction compositor -- overlay_boxes, overlay_filled_mask and overlay_uncertainty_mask
  * (mb/engine/inference.py:519-540, :557-569, :571-589) over the Masker paste (mb/modeling/roi_heads/mask_head/
  * inference.py:124-165, padding 1; thresholded for fills, un-thresholded :150-155 for heat) in ONE launch, without building

@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, polygons, transform, render, view_merge (``--ops paste,...,view_merge``).
+Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, render, view_merge (``--ops paste,...,view_merge``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -255,12 +255,13 @@ def main():
                     "backward_ms": ms_fb_col - ms_col})
         res.append({"op": "deform_conv forward+backward (rows route)", "shape": "[2,512,100,168] 3x3 -> 512", "ms": ms_fb,
                     "backward_ms": ms_fb - ms, "backward_over_forward": (ms_fb - ms) / ms})
-    if "paste" in ops:  # opt-in: the evaluation pass's Masker paste, 100 detections of one 800 x 1333 image, M = 14
-        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.roi_heads import Masker
-        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import BoxList
+    if "paste" in ops or "mask_rle" in ops:  # the inputs both entries share: 100 detections of one 800 x 1333 image, M = 14
         p_, m_, h_, w_ = 100, 14, 800, 1333
         probs = torch.rand(p_, m_, m_, generator=g).to(dev)
         boxes = bench_rois(p_, 1, g, "rpn_like")[:, 1:].contiguous().to(dev)
+    if "paste" in ops:  # opt-in: the evaluation pass's Masker paste
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.roi_heads import Masker
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import BoxList
         masks, boxlist, masker = probs[:, None], BoxList(boxes, (w_, h_)), Masker(0.5, 1)
         equal = torch.equal(_C.paste_masks(probs, boxes, (h_, w_)), masker._loop(masks, boxlist)[:, 0])
         k_ms, l_ms = [], []
@@ -272,6 +273,46 @@ def main():
                     "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6, "frac_hbm_write_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS,
                     "masker_loop_ms": ms_loop, "masker_loop_rounds_ms": [round(v, 4) for v in l_ms], "loop_over_kernel": ms_loop / ms,
                     "outputs_equal": equal})
+    if "mask_rle" in ops:  # opt-in: the results export's mask encoder against what it replaces, strings on the host either way
+        import time
+
+        from tests import coco_rle_reference as rle
+        sizes = torch.tensor([[h_, w_]] * p_, dtype=torch.int32).to(dev)
+
+        def fused():  # three launches, two reads of P totals, then the strings and their offsets
+            data, offsets = _C.pasted_masks_rle(probs, boxes, sizes)
+            return data.cpu(), offsets.cpu()
+
+        def paste_and_copy():  # the canvases, all of them across the link
+            return _C.paste_masks(probs, boxes, (h_, w_)).cpu()
+
+        def wall(fn, n):
+            fn()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(n):
+                out = fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / n * 1e3, out
+
+        f_ms, c_ms = [], []
+        for _ in range(3):  # the two routes alternate inside this one call
+            ms, (data, offsets) = wall(fused, args.iters)
+            f_ms.append(ms)
+            ms, masks = wall(paste_and_copy, max(3, args.iters // 4))
+            c_ms.append(ms)
+        t0 = time.perf_counter()
+        strings = [rle.rle_to_string(rle.rle_encode(m)) for m in masks.numpy()]
+        encode_ms = (time.perf_counter() - t0) * 1e3
+        o = offsets.tolist()
+        equal = strings == [bytes(data[a:b].numpy()) for a, b in zip(o[:-1], o[1:])]
+        ms, ms_copy = sorted(f_ms)[1], sorted(c_ms)[1]
+        res.append({"op": "pasted_masks_rle (3 launches + copies of the strings)", "shape": "P=100 M=14 800x1333 rpn_like boxes",
+                    "ms": ms, "rounds_ms": [round(v, 4) for v in f_ms], "to_host_bytes": data.numel() + 8 * (p_ + 1) + 2 * 4 * p_,
+                    "string_bytes": data.numel(), "runs": int(_C.pasted_masks_runs(probs, boxes, sizes)[0].numel()),
+                    "paste_masks_plus_copy_ms": ms_copy, "paste_masks_plus_copy_rounds_ms": [round(v, 4) for v in c_ms],
+                    "numpy_encode_ms": encode_ms, "replaced_total_ms": ms_copy + encode_ms, "replaced_to_host_bytes": p_ * h_ * w_,
+                    "replaced_over_fused": (ms_copy + encode_ms) / ms, "copy_alone_over_fused": ms_copy / ms, "outputs_equal": equal})
     if "polygons" in ops:  # opt-in: whole-image ground-truth masks, 20 instances of 30-200 vertices at 800 x 1333
         import math
         import time

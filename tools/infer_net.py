@@ -14,7 +14,10 @@ sizes.  ``--visualize N`` (rank 0) also renders the first N images of every test
 against its own annotation file on the device (engine/coco_eval.py: COCO box AP, and mask AP when MODEL.MASK_ON, plus AP50
 per class and per seen / unseen split), logs the reference's ``Task: ... / names / values`` table and writes
 ``<OUTPUT_DIR>/inference/<name>/coco_results.json``; it needs OUTPUT_DIR and MODEL.DEVICE cuda -- there is no host-only
-scoring.  ``TEST.BBOX_AUG.ENABLED True`` (with H_FLIP / SCALES / MAX_SIZE / SCALE_H_FLIP) turns on multi-scale / flip testing:
+scoring.  ``--export-results`` (rank 0, after the gather, independent of ``--evaluate``) writes the detections as COCO results
+files next to ``predictions.pth`` (engine/coco_results.py): ``bbox.json``, and ``segm.json`` when MODEL.MASK_ON -- every
+detection, boxes as xywh and masks as compressed RLE at the ORIGINAL image sizes, the masks encoded on the device; it needs
+OUTPUT_DIR, and MODEL.DEVICE cuda when MODEL.MASK_ON.  ``TEST.BBOX_AUG.ENABLED True`` (with H_FLIP / SCALES / MAX_SIZE / SCALE_H_FLIP) turns on multi-scale / flip testing:
 ``build_transforms(cfg, False)`` then makes every view on the device from the one upload and ``engine/bbox_aug.py`` merges the
 views' detections; the saved BoxLists are in the first view's frame and keep their masks.  ``tools/test_net.py`` stays the
 synthetic-stream tool; LVIS scoring is outside this build.
@@ -37,7 +40,7 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  
 from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem_bn, make_batch, make_embeddings  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, comm, inference, visualize  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, coco_results, comm, inference, visualize  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
@@ -66,7 +69,8 @@ def save_evaluation(dataset, predictions, folder, iou_types, device, logger):
     return results
 
 
-def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False):
+def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
+                 export_results=False):
     """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}."""
     transform = build_transforms(cfg, is_train=False)
     results = {}
@@ -84,9 +88,15 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
             save_visualizations(dataset, results[name], os.path.join(out, "vis"), visualize_count, vis_threshold, device)
         if evaluate and not out:
             raise ValueError("run_datasets: evaluate=True writes OUTPUT_DIR/inference/<name>/coco_results.json: set OUTPUT_DIR")
+        if export_results and not out:
+            raise ValueError("run_datasets: export_results=True writes OUTPUT_DIR/inference/<name>/bbox.json and segm.json: "
+                             "set OUTPUT_DIR")
         if evaluate and results[name] is not None:
             save_evaluation(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",), device,
                             logger or logging.getLogger("ovis.inference"))
+        if export_results and results[name] is not None:
+            coco_results.export_coco_results(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",),
+                                             device)
     return results
 
 
@@ -104,6 +114,9 @@ def main(argv=None):
     parser.add_argument("--evaluate", action="store_true",
                         help="score every test set on the device (COCO box / mask AP, AP50 per class and split) and write "
                              "OUTPUT_DIR/inference/<name>/coco_results.json (rank 0)")
+    parser.add_argument("--export-results", action="store_true",
+                        help="write every test set's detections as COCO results files, OUTPUT_DIR/inference/<name>/bbox.json "
+                             "and (MODEL.MASK_ON) segm.json with the masks RLE-encoded on the device (rank 0)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args(argv)
 
@@ -120,6 +133,11 @@ def main(argv=None):
     if args.evaluate and cfg.MODEL.DEVICE != "cuda":
         parser.error("--evaluate scores on the HIP device (mask IoU and matching have no host implementation): "
                      "set MODEL.DEVICE cuda")
+    if args.export_results and not cfg.OUTPUT_DIR:
+        parser.error("--export-results writes OUTPUT_DIR/inference/<name>/bbox.json and segm.json: set OUTPUT_DIR")
+    if args.export_results and cfg.MODEL.MASK_ON and cfg.MODEL.DEVICE != "cuda":
+        parser.error("--export-results encodes the masks of segm.json on the HIP device (the run-length encoder has no host "
+                     "implementation): set MODEL.DEVICE cuda")
     device = torch.device(cfg.MODEL.DEVICE, args.local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
@@ -143,7 +161,7 @@ def main(argv=None):
     _, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
     model.set_class_embeddings(e_seen)  # stands until a dataset brings its own (DATASETS.DATASET_ARGS.LOAD_EMBEDDINGS)
     for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
-                                    args.evaluate).items():
+                                    args.evaluate, args.export_results).items():
         if preds is not None:
             logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:
