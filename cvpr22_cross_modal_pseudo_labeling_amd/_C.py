@@ -59,6 +59,32 @@ def _dev(t, name, dtype=torch.float32):
     return t
 
 
+# ---- what every shim does around a launch ------------------------------------------------------
+def _ptr(t):
+    """The device pointer of an optional tensor: NULL for None."""
+    return 0 if t is None else t.data_ptr()
+
+
+def _workspace(nbytes, device, at_least=0):
+    """uint8 device scratch of max(nbytes, at_least) bytes, or None (NULL through ``_ptr``) when that is 0.  ``at_least``
+    is the entry point's convention for a problem that needs no scratch: a 1-byte dummy (RoIAlign, transform_images), 256
+    bytes (bottleneck_identity_backward), nothing (everything else)."""
+    nbytes = max(nbytes, at_least)
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None
+
+
+def _check_pairs(op, **operands):
+    for name, t in operands.items():
+        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1):
+            raise RuntimeError(f"{op}: {name} must be a 2-D bfloat16 HIP tensor in pair layout")
+
+
+def _gemm_results(m, n, out_f32, out_pair, device):
+    """(C f32 [M, N] or None, C in pair layout [M, 2N] or None) of the split-GEMM family, uninitialised."""
+    return (torch.empty((m, n), dtype=torch.float32, device=device) if out_f32 else None,
+            torch.empty((m, 2 * n), dtype=torch.bfloat16, device=device) if out_pair else None)
+
+
 # ---- RoIAlign (csrc/ROIAlign.h:11-46) ---------------------------------------------------------
 def _roi_align_forward(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, exact):
     if not input.is_cuda:
@@ -77,7 +103,7 @@ def _roi_align_forward(input, rois, spatial_scale, pooled_height, pooled_width, 
                                                pooled_height, pooled_width, spatial_scale, sampling_ratio, _stream())
         else:
             nbytes = _L.ovis_roi_align_forward_workspace_bytes(r, h, w)
-            ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=input.device)
+            ws = _workspace(nbytes, input.device, at_least=1)
             rc = _L.ovis_roi_align_forward_ws_f32(input.data_ptr(), rois.data_ptr(), out.data_ptr(), r, n, c, h, w,
                                                   pooled_height, pooled_width, spatial_scale, sampling_ratio,
                                                   ws.data_ptr(), nbytes, _stream())
@@ -147,26 +173,37 @@ def roi_align_forward_strided_pair(input, rois, spatial_scale, pooled_height, po
                                       sampling_ratio, bin_stride, True)
 
 
+def _roi_align_backward(name, entry, ws_query, grad, rois, batch_size, channels, height, width, tail, none_if_unsupported):
+    """What the three backward shims share: grad_input [N, C, H, W] and the plan workspace (``ws_query``: the size query and
+    its arguments behind the RoI count) are allocated, ``entry`` is launched (``tail``: its arguments between width and the
+    workspace), and OVIS_ERANGE comes back as None where the shim's contract says so."""
+    r = rois.size(0)
+    gin = torch.empty((batch_size, channels, height, width), dtype=grad.dtype, device=grad.device)
+    if gin.numel() == 0:
+        return gin
+    with _on(grad.device):
+        nbytes = ws_query[0](r, *ws_query[1:])
+        ws = _workspace(nbytes, grad.device, at_least=1)
+        rc = entry(grad.data_ptr(), rois.data_ptr(), gin.data_ptr(), r, batch_size, channels, height, width, *tail,
+                   ws.data_ptr(), nbytes, _stream())
+    if none_if_unsupported and rc == _lib.OVIS_ERANGE:
+        return None
+    _lib.check(rc, name)
+    return gin
+
+
 def roi_align_backward(grad, rois, spatial_scale, pooled_height, pooled_width, batch_size, channels, height,
                        width, sampling_ratio):
     if not grad.is_cuda:
         return _cpu.roi_align_backward(grad, rois, spatial_scale, pooled_height, pooled_width, batch_size, channels, height,
                                        width, sampling_ratio)
     grad, rois = _dev(grad, "grad"), _dev(rois, "rois")
-    r = rois.size(0)
-    gin = torch.empty((batch_size, channels, height, width), dtype=grad.dtype, device=grad.device)
-    if gin.numel() == 0:
-        return gin
-    with _on(grad.device):
-        # plane-owner MFMA kernel when the H x W plane fits LDS (needs a per-call table workspace); the
-        # library falls back to the window-gather + atomic kernel for larger maps
-        nbytes = _L.ovis_roi_align_backward_workspace_bytes(r, batch_size, height, width)
-        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=grad.device)
-        rc = _L.ovis_roi_align_backward_ws_f32(grad.data_ptr(), rois.data_ptr(), gin.data_ptr(), r, batch_size,
-                                               channels, height, width, pooled_height, pooled_width,
-                                               spatial_scale, sampling_ratio, ws.data_ptr(), nbytes, _stream())
-    _lib.check(rc, "roi_align_backward")
-    return gin
+    # plane-owner MFMA kernel when the H x W plane fits LDS (needs a per-call table workspace); the
+    # library falls back to the window-gather + atomic kernel for larger maps
+    return _roi_align_backward("roi_align_backward", _L.ovis_roi_align_backward_ws_f32,
+                               (_L.ovis_roi_align_backward_workspace_bytes, batch_size, height, width), grad, rois,
+                               batch_size, channels, height, width,
+                               (pooled_height, pooled_width, spatial_scale, sampling_ratio), False)
 
 
 def roi_align_backward_strided(grad, rois, spatial_scale, pooled_height, pooled_width, batch_size, channels, height,
@@ -175,20 +212,10 @@ def roi_align_backward_strided(grad, rois, spatial_scale, pooled_height, pooled_
     the strided pooler produced) -> grad_input [N, C, H, W].  Returns None when the plane-owner kernel does not cover the
     shape (the caller scatters into a full tile and uses ``roi_align_backward``)."""
     grad, rois = _dev(grad, "grad"), _dev(rois, "rois")
-    r = rois.size(0)
-    gin = torch.empty((batch_size, channels, height, width), dtype=grad.dtype, device=grad.device)
-    if gin.numel() == 0:
-        return gin
-    with _on(grad.device):
-        nbytes = _L.ovis_roi_align_backward_workspace_bytes(r, batch_size, height, width)
-        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=grad.device)
-        rc = _L.ovis_roi_align_backward_strided_ws_f32(grad.data_ptr(), rois.data_ptr(), gin.data_ptr(), r, batch_size,
-                                                       channels, height, width, pooled_height, pooled_width, bin_stride,
-                                                       spatial_scale, sampling_ratio, ws.data_ptr(), nbytes, _stream())
-    if rc == -3:  # OVIS_ERANGE
-        return None
-    _lib.check(rc, "roi_align_backward_strided")
-    return gin
+    return _roi_align_backward("roi_align_backward_strided", _L.ovis_roi_align_backward_strided_ws_f32,
+                               (_L.ovis_roi_align_backward_workspace_bytes, batch_size, height, width), grad, rois,
+                               batch_size, channels, height, width,
+                               (pooled_height, pooled_width, bin_stride, spatial_scale, sampling_ratio), True)
 
 
 def roi_align_backward_strided_nhwc(grad_nhwc, rois, spatial_scale, pooled_height, pooled_width, batch_size, channels,
@@ -203,67 +230,54 @@ def roi_align_backward_strided_nhwc(grad_nhwc, rois, spatial_scale, pooled_heigh
         raise RuntimeError(f"roi_align_backward_strided_nhwc: gradient {tuple(grad_nhwc.shape)} for {rois.size(0)} RoIs x {channels} channels")
     if th > 8 or tw > 8:
         return None
-    gin = torch.empty((batch_size, channels, height, width), dtype=grad_nhwc.dtype, device=grad_nhwc.device)
-    if gin.numel() == 0:
-        return gin
-    with _on(grad_nhwc.device):
-        nbytes = _L.ovis_roi_align_backward_strided_nhwc_workspace_bytes(r, batch_size, channels, height, width)
-        ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=grad_nhwc.device)
-        rc = _L.ovis_roi_align_backward_strided_nhwc_ws_f32(grad_nhwc.data_ptr(), rois.data_ptr(), gin.data_ptr(), r, batch_size,
-                                                            channels, height, width, pooled_height, pooled_width, bin_stride,
-                                                            spatial_scale, sampling_ratio, ws.data_ptr(), nbytes, _stream())
-    if rc == -3:  # OVIS_ERANGE
-        return None
-    _lib.check(rc, "roi_align_backward_strided_nhwc")
-    return gin
+    return _roi_align_backward("roi_align_backward_strided_nhwc", _L.ovis_roi_align_backward_strided_nhwc_ws_f32,
+                               (_L.ovis_roi_align_backward_strided_nhwc_workspace_bytes, batch_size, channels, height, width),
+                               grad_nhwc, rois, batch_size, channels, height, width,
+                               (pooled_height, pooled_width, bin_stride, spatial_scale, sampling_ratio), True)
 
 
 # ---- NMS (csrc/nms.h:10-28) -------------------------------------------------------------------
-def nms_padded(dets, scores, threshold, ge_mode=False):
-    """Sync-free form: returns (keep[K] int64 -- first n entries valid, ascending; n as a
-    1-element int32 device tensor).  Extension of the reference API for device pipelines."""
-    if not dets.is_cuda:
-        return _cpu.nms_padded(dets, scores, threshold)
+NMS_MAX_CANDIDATES = _lib.OVIS_NMS_MAX_CANDIDATES  # what one nms / nms_grouped call accepts
+
+
+def _nms_padded(dets, scores, groups, threshold, ge_mode):
+    """``ovis_nms_f32``, or ``ovis_nms_grouped_f32`` when ``groups`` is given."""
+    what = "nms" if groups is None else "nms_grouped"
     dets, scores = _dev(dets, "dets"), _dev(scores, "scores")
+    if groups is not None:
+        groups = _dev(groups.to(torch.int32), "groups", torch.int32)
     k = dets.size(0)
     keep = torch.empty((k,), dtype=torch.int64, device=dets.device)
     num = torch.zeros((1,), dtype=torch.int32, device=dets.device)
     if k == 0:
         return keep, num
-    if dets.dim() != 2 or dets.size(1) != 4 or scores.numel() != k:
-        raise RuntimeError("nms: expected dets [K,4] and scores [K]")
+    if dets.dim() != 2 or dets.size(1) != 4 or scores.numel() != k or (groups is not None and groups.numel() != k):
+        raise RuntimeError(f"{what}: expected dets [K,4]" + (" and scores [K]" if groups is None else ", scores [K] and groups [K]"))
     with _on(dets.device):
         nbytes = _L.ovis_nms_workspace_bytes(k)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dets.device)
-        rc = _L.ovis_nms_f32(dets.data_ptr(), scores.data_ptr(), k, threshold, int(bool(ge_mode)), ws.data_ptr(),
-                             nbytes, keep.data_ptr(), num.data_ptr(), _stream())
-    _lib.check(rc, "nms")
+        ws = _workspace(nbytes, dets.device)
+        tail = (k, threshold, int(bool(ge_mode)), _ptr(ws), nbytes, keep.data_ptr(), num.data_ptr(), _stream())
+        if groups is None:
+            rc = _L.ovis_nms_f32(dets.data_ptr(), scores.data_ptr(), *tail)
+        else:
+            rc = _L.ovis_nms_grouped_f32(dets.data_ptr(), scores.data_ptr(), groups.data_ptr(), *tail)
+    _lib.check(rc, what)
     return keep, num
 
 
-NMS_MAX_CANDIDATES = 131072  # csrc/nms.hip: kMaxBlocks * 64 -- what one nms / nms_grouped call accepts
+def nms_padded(dets, scores, threshold, ge_mode=False):
+    """Sync-free form: returns (keep[K] int64 -- first n entries valid, ascending; n as a
+    1-element int32 device tensor).  Extension of the reference API for device pipelines."""
+    if not dets.is_cuda:
+        return _cpu.nms_padded(dets, scores, threshold)
+    return _nms_padded(dets, scores, None, threshold, ge_mode)
 
 
 def nms_grouped_padded(dets, scores, groups, threshold, ge_mode=False):
     """NMS inside every group of boxes in one launch (groups [K] integer labels): (keep[K] int64 -- first n entries
     valid, ascending indices into the K candidates; n as a 1-element int32 device tensor).  Equals ``nms`` run on
     every group separately (the per-class loop of box_head/inference.py:137-150)."""
-    dets, scores = _dev(dets, "dets"), _dev(scores, "scores")
-    groups = _dev(groups.to(torch.int32), "groups", torch.int32)
-    k = dets.size(0)
-    keep = torch.empty((k,), dtype=torch.int64, device=dets.device)
-    num = torch.zeros((1,), dtype=torch.int32, device=dets.device)
-    if k == 0:
-        return keep, num
-    if dets.dim() != 2 or dets.size(1) != 4 or scores.numel() != k or groups.numel() != k:
-        raise RuntimeError("nms_grouped: expected dets [K,4], scores [K] and groups [K]")
-    with _on(dets.device):
-        nbytes = _L.ovis_nms_workspace_bytes(k)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dets.device)
-        rc = _L.ovis_nms_grouped_f32(dets.data_ptr(), scores.data_ptr(), groups.data_ptr(), k, threshold,
-                                     int(bool(ge_mode)), ws.data_ptr(), nbytes, keep.data_ptr(), num.data_ptr(), _stream())
-    _lib.check(rc, "nms_grouped")
-    return keep, num
+    return _nms_padded(dets, scores, groups, threshold, ge_mode)
 
 
 def nms_grouped(dets, scores, groups, threshold):
@@ -298,10 +312,9 @@ def nms_presorted_batched(boxes, drop, threshold, below=0, ge_mode=False):
             raise RuntimeError("nms_presorted_batched: drop must be [N,K] int32")
     with _on(boxes.device):
         nbytes = _nms_presorted_ws_bytes(n, k)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=boxes.device)
-        rc = _L.ovis_nms_presorted_batched_f32(boxes.data_ptr(), 0 if drop is None else drop.data_ptr(), n, k, threshold,
-                                               int(bool(ge_mode)), int(below), ws.data_ptr(), nbytes, keep.data_ptr(),
-                                               counts.data_ptr(), _stream())
+        ws = _workspace(nbytes, boxes.device)
+        rc = _L.ovis_nms_presorted_batched_f32(boxes.data_ptr(), _ptr(drop), n, k, threshold, int(bool(ge_mode)), int(below),
+                                               _ptr(ws), nbytes, keep.data_ptr(), counts.data_ptr(), _stream())
     _lib.check(rc, "nms_presorted_batched")
     return keep, counts
 
@@ -324,7 +337,7 @@ def topk_sorted(scores, k):
     need = _topk_ws_bytes(n, a)
     if need == 0:
         raise RuntimeError(f"topk_sorted: unsupported size [{n}, {a}]")
-    ws = torch.empty((need,), dtype=torch.uint8, device=scores.device)
+    ws = _workspace(need, scores.device)
     with _on(scores.device):
         rc = _L.ovis_topk_sorted_f32(scores.data_ptr(), scores.stride(0) if n > 1 else a, n, a, k, vals.data_ptr(),
                                      idx.data_ptr(), ws.data_ptr(), need, _stream())
@@ -363,9 +376,6 @@ def rpn_decode(box_regression, topk_idx, cell_anchors, image_wh, weights, xform_
     return boxes, drop
 
 
-_BOX_DECODE_MAX_IMAGES = 16  # include/ovis_hip.h: OVIS_BOX_DECODE_MAX_IMAGES
-
-
 def box_decode(rel_codes, boxes, weights, xform_clip, rows_per_image=None, image_sizes=None):
     """``BoxCoder.decode`` (modeling/box_coder.py:49-95) in one launch (``ovis_box_decode_f32``): rel_codes [R, 4K] (any row
     stride), boxes [R, 4] -> [R, 4K].  With ``rows_per_image`` (ints, image-major rows) and ``image_sizes`` ((width, height)
@@ -385,14 +395,14 @@ def box_decode(rel_codes, boxes, weights, xform_clip, rows_per_image=None, image
         return out
     n = 0 if rows_per_image is None else len(rows_per_image)
     wx, wy, ww, wh_ = weights
-    # image sizes travel as kernel arguments, at most _BOX_DECODE_MAX_IMAGES per launch: rows are image-major, so a longer
+    # image sizes travel as kernel arguments, at most OVIS_BOX_DECODE_MAX_IMAGES per launch: rows are image-major, so a longer
     # batch is a few launches over consecutive row ranges (as ovis_rois_from_boxes_f32 does internally)
     if n and (len(image_sizes) != n or sum(int(c) for c in rows_per_image) != r):
         raise RuntimeError(f"box_decode: rows_per_image must list {r} rows over {n} images with one (width, height) each")
     i0 = row0 = 0
     with _on(rel_codes.device):
         while True:
-            m = min(n - i0, _BOX_DECODE_MAX_IMAGES)
+            m = min(n - i0, _lib.OVIS_BOX_DECODE_MAX_IMAGES)
             counts = wh = None
             rows = r
             if n:
@@ -410,10 +420,6 @@ def box_decode(rel_codes, boxes, weights, xform_clip, rows_per_image=None, image
             if i0 >= n:
                 break
     return out
-
-
-_VIEW_MERGE_MAX_SEGMENTS = 64  # include/ovis_hip.h: OVIS_VIEW_MERGE_MAX_SEGMENTS
-_VIEW_MERGE_TILE_ROWS = 64     # include/ovis_hip.h: OVIS_VIEW_MERGE_TILE_ROWS
 
 
 def _merge_segments(segments, num_rows):
@@ -463,21 +469,21 @@ def merge_view_detections(boxes, scores, segments, num_classes, score_thresh):
     boxes, scores = _dev(boxes, "boxes"), _dev(scores, "scores")
     dev = boxes.device
     offsets = torch.empty((b * c + 1,), dtype=torch.int32, device=dev)
-    # launches: whole images, at most _VIEW_MERGE_MAX_SEGMENTS segments each; (first segment, count, first count entry)
+    # launches: whole images, at most OVIS_VIEW_MERGE_MAX_SEGMENTS segments each; (first segment, count, first count entry)
     per_image = [0] * b
     for seg in segs:
         per_image[seg[2]] += 1
-    if b and max(per_image) > _VIEW_MERGE_MAX_SEGMENTS:
+    if b and max(per_image) > _lib.OVIS_VIEW_MERGE_MAX_SEGMENTS:
         raise RuntimeError(f"merge_view_detections: image {per_image.index(max(per_image))} has {max(per_image)} views, more "
-                           f"than the {_VIEW_MERGE_MAX_SEGMENTS} segments of one launch")
+                           f"than the {_lib.OVIS_VIEW_MERGE_MAX_SEGMENTS} segments of one launch")
     calls, first, entries, image = [], 0, 0, 0
     while image < b:
         n = 0
-        while image < b and n + per_image[image] <= _VIEW_MERGE_MAX_SEGMENTS:
+        while image < b and n + per_image[image] <= _lib.OVIS_VIEW_MERGE_MAX_SEGMENTS:
             n += per_image[image]
             image += 1
         part = segs[first:first + n]
-        num = c * sum(max(1, -(-seg[1] // _VIEW_MERGE_TILE_ROWS)) for seg in part)
+        num = c * sum(max(1, -(-seg[1] // _lib.OVIS_VIEW_MERGE_TILE_ROWS)) for seg in part)
         ints = (ctypes.c_int32 * (5 * n))(*[int(v) for seg in part for v in seg[:5]])
         ratios = (ctypes.c_float * (2 * n))(*[v for seg in part for v in seg[5:]])
         calls.append((ints, ratios, n, entries, num))
@@ -543,9 +549,8 @@ def smooth_l1_picked_fwd_bwd(box_regression, regression_targets, positives, labe
     with _on(box_regression.device):
         rc = _L.ovis_smooth_l1_picked_fwd_bwd_f32(box_regression.data_ptr(), box_regression.stride(0), r, c,
                                                   regression_targets.data_ptr(), regression_targets.stride(0),
-                                                  positives.data_ptr(), 0 if labels is None else labels.data_ptr(),
-                                                  positives.numel(), column0, beta, float(denominator), loss.data_ptr(),
-                                                  0 if grad is None else grad.data_ptr(), _stream())
+                                                  positives.data_ptr(), _ptr(labels), positives.numel(), column0, beta,
+                                                  float(denominator), loss.data_ptr(), _ptr(grad), _stream())
     _lib.check(rc, "smooth_l1_picked_fwd_bwd")
     return loss[0], grad
 
@@ -719,7 +724,7 @@ def match_encode(gt_boxes, gt_labels, proposals, high, low, weights=None, betwee
         with _on(proposals.device):
             rc = _L.ovis_match_encode_f32(gt_boxes.data_ptr(), gt_labels.data_ptr(), proposals.data_ptr(), g, p, high, low,
                                           int(bool(between_keeps_label)), wx, wy, ww, wh, idx.data_ptr(), lab.data_ptr(),
-                                          0 if reg is None else reg.data_ptr(), _stream())
+                                          _ptr(reg), _stream())
         _lib.check(rc, "match_encode")
     return idx, lab, reg
 
@@ -796,10 +801,9 @@ def gather_rows(index, boxes_a=None, boxes_b=None, ints_a=None, ints_b=None):
             raise RuntimeError("gather_rows: int64 sources must be [P]")
     outs = [None if t is None else torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in srcs]
     if n:
-        ptr = lambda t: 0 if t is None else t.data_ptr()
         with _on(index.device):
-            rc = _L.ovis_gather_rows(index.data_ptr(), n, ptr(srcs[0]), ptr(outs[0]), ptr(srcs[1]), ptr(outs[1]), ptr(srcs[2]),
-                                     ptr(outs[2]), ptr(srcs[3]), ptr(outs[3]), _stream())
+            rc = _L.ovis_gather_rows(index.data_ptr(), n, _ptr(srcs[0]), _ptr(outs[0]), _ptr(srcs[1]), _ptr(outs[1]),
+                                     _ptr(srcs[2]), _ptr(outs[2]), _ptr(srcs[3]), _ptr(outs[3]), _stream())
         _lib.check(rc, "gather_rows")
     return tuple(outs)
 
@@ -997,12 +1001,9 @@ def gate_split_pair(dy, gate=None, want_f32=False, pooled=None, pool_rows=0, sel
                 selected.shape[0] % pool_rows or group_slot.numel() != rows // pool_rows:
             raise RuntimeError("gate_split_pair: selected must be [S * pool_rows, cols] and group_slot [rows / pool_rows]")
     with _on(dev):
-        rc = _L.ovis_gate_split_pair_rows_f32(0 if dy is None else dy.data_ptr(), 0 if dy is None else dy.stride(0),
-                                              0 if gate is None else gate.data_ptr(), is_pair, out.data_ptr(),
-                                              0 if g32 is None else g32.data_ptr(), rows, cols,
-                                              0 if pooled is None else pooled.data_ptr(), pool_rows,
-                                              0 if selected is None else selected.data_ptr(),
-                                              0 if group_slot is None else group_slot.data_ptr(), _stream())
+        rc = _L.ovis_gate_split_pair_rows_f32(_ptr(dy), 0 if dy is None else dy.stride(0), _ptr(gate), is_pair, out.data_ptr(),
+                                              _ptr(g32), rows, cols, _ptr(pooled), pool_rows, _ptr(selected),
+                                              _ptr(group_slot), _stream())
     _lib.check(rc, "gate_split_pair")
     return out, g32
 
@@ -1092,6 +1093,12 @@ def _gemm_cfg(config):
     return config | (0x10000 if getattr(_GEMM_TLS, "co", False) else 0)
 
 
+def _gemm_workspace(device, m, n, ch, ch2, kh, kw, w, config):
+    """(split-K scratch of the launch plan or None, its size); config bit 8 = no K slices."""
+    nbytes = 0 if config & 8 else _gemm_ws_bytes(m, n, ch, ch2, kh, kw, w, config)
+    return _workspace(nbytes, device), nbytes
+
+
 def split_gemm_pair(a_pair, b_pair, bias=None, residual=None, relu=False, out_f32=True, out_pair=False, conv=None,
                     config=0, a2_pair=None, residual_pair=None):
     """act(A @ B^T + bias + residual) with A [M, 2*ch] / B [N, 2*K] in pair layout (``split_pair``); fp32-accurate
@@ -1100,13 +1107,12 @@ def split_gemm_pair(a_pair, b_pair, bias=None, residual=None, relu=False, out_f3
     implicit GEMM.  a2_pair [M, 2*ch2]: a second operand whose products follow A's along K (B = [N, 2*(ch + ch2)]):
     conv3 + projection shortcut of a bottleneck as one product.  ``config``: 0 = choose; test / measurement bits as in
     include/ovis_hip.h.  Returns (C f32 [M, N] or None, C in pair layout [M, 2*N] or None)."""
-    for t, name in ((a_pair, "a_pair"), (b_pair, "b_pair")) + (((a2_pair, "a2_pair"),) if a2_pair is not None else ()):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError(f"split_gemm_pair: {name} must be a 2-D bfloat16 HIP tensor in pair layout")
+    _check_pairs("split_gemm_pair", a_pair=a_pair, b_pair=b_pair)
     m, ch = a_pair.shape[0], a_pair.shape[1] // 2
     n, k = b_pair.shape[0], b_pair.shape[1] // 2
     ch2 = 0
     if a2_pair is not None:
+        _check_pairs("split_gemm_pair", a2_pair=a2_pair)
         if conv is not None or a2_pair.shape[0] != m:
             raise RuntimeError("split_gemm_pair: a2_pair needs a plain product and as many rows as a_pair")
         ch2 = a2_pair.shape[1] // 2
@@ -1120,8 +1126,7 @@ def split_gemm_pair(a_pair, b_pair, bias=None, residual=None, relu=False, out_f3
     if k != kh * kw * ch + ch2:
         raise RuntimeError(f"split_gemm_pair: contraction mismatch (A has {ch} channels x {kh * kw} taps + {ch2}, B has {k})")
     dev = a_pair.device
-    c = torch.empty((m, n), dtype=torch.float32, device=dev) if out_f32 else None
-    cp = torch.empty((m, 2 * n), dtype=torch.bfloat16, device=dev) if out_pair else None
+    c, cp = _gemm_results(m, n, out_f32, out_pair, dev)
     if m == 0 or n == 0:
         return c, cp
     if bias is not None:
@@ -1134,13 +1139,11 @@ def split_gemm_pair(a_pair, b_pair, bias=None, residual=None, relu=False, out_f3
             raise RuntimeError("split_gemm_pair: residual_pair must be [M, 2N] bfloat16 pair rows of a plain product")
         with _on(dev):
             config = _gemm_cfg(config)
-            nbytes = _gemm_ws_bytes(m, n, ch, 0, 1, 1, 0, config) if not (config & 8) else 0
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+            ws, nbytes = _gemm_workspace(dev, m, n, ch, 0, 1, 1, 0, config)
             rc = _L.ovis_split_gemm_pair_rp(a_pair.data_ptr(), 2 * a_pair.stride(0), b_pair.data_ptr(), 2 * b_pair.stride(0),
-                                            0 if c is None else c.data_ptr(), n, 0 if cp is None else cp.data_ptr(), 4 * n,
-                                            0 if bias is None else bias.data_ptr(), residual_pair.data_ptr(),
-                                            2 * residual_pair.stride(0), m, n, ch, int(bool(relu)),
-                                            0 if ws is None else ws.data_ptr(), nbytes, config, _stream())
+                                            _ptr(c), n, _ptr(cp), 4 * n, _ptr(bias), residual_pair.data_ptr(),
+                                            2 * residual_pair.stride(0), m, n, ch, int(bool(relu)), _ptr(ws), nbytes, config,
+                                            _stream())
         _lib.check(rc, "split_gemm_pair_rp")
         return c, cp
     if residual is not None and not (residual.is_cuda and residual.dtype == torch.float32 and residual.dim() == 2
@@ -1148,18 +1151,12 @@ def split_gemm_pair(a_pair, b_pair, bias=None, residual=None, relu=False, out_f3
         raise RuntimeError("split_gemm_pair: residual must be a float32 [M, N] HIP tensor with unit column stride")
     with _on(dev):
         config = _gemm_cfg(config)
-        nbytes = _gemm_ws_bytes(m, n, ch, ch2, kh, kw, w, config) if not (config & 8) else 0
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
-        rc = _L.ovis_split_gemm_pair(a_pair.data_ptr(), 2 * a_pair.stride(0),
-                                     0 if a2_pair is None else a2_pair.data_ptr(),
-                                     0 if a2_pair is None else 2 * a2_pair.stride(0),
-                                     b_pair.data_ptr(), 2 * b_pair.stride(0),
-                                     0 if c is None else c.data_ptr(), n, 0 if cp is None else cp.data_ptr(), 4 * n,
-                                     0 if bias is None else bias.data_ptr(),
-                                     0 if residual is None else residual.data_ptr(),
+        ws, nbytes = _gemm_workspace(dev, m, n, ch, ch2, kh, kw, w, config)
+        rc = _L.ovis_split_gemm_pair(a_pair.data_ptr(), 2 * a_pair.stride(0), _ptr(a2_pair),
+                                     0 if a2_pair is None else 2 * a2_pair.stride(0), b_pair.data_ptr(), 2 * b_pair.stride(0),
+                                     _ptr(c), n, _ptr(cp), 4 * n, _ptr(bias), _ptr(residual),
                                      0 if residual is None else residual.stride(0), m, n, ch, ch2, kh, kw, h, w,
-                                     int(bool(flip)), int(bool(relu)), 0 if ws is None else ws.data_ptr(), nbytes,
-                                     config, _stream())
+                                     int(bool(flip)), int(bool(relu)), _ptr(ws), nbytes, config, _stream())
     _lib.check(rc, "split_gemm_pair")
     return c, cp
 
@@ -1173,16 +1170,15 @@ def split_gemm_pair_rp_pool(a_pair, b_pair, bias, residual_pair, relu, out_f32, 
     epilogue (``ovis_split_gemm_pair_rp_pool``): also returns the mean of the result over every group of ``pool_rows`` rows
     ([M / pool_rows, N] fp32); with ``out_f32`` and ``out_pair`` both False the result itself is never written.
     -> (C f32 or None, C pair or None, pooled)."""
-    for t, name in ((a_pair, "a_pair"), (b_pair, "b_pair")) + (((residual_pair, "residual_pair"),) if residual_pair is not None else ()):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError(f"split_gemm_pair_rp_pool: {name} must be a 2-D bfloat16 HIP tensor in pair layout")
+    _check_pairs("split_gemm_pair_rp_pool", a_pair=a_pair, b_pair=b_pair)
+    if residual_pair is not None:
+        _check_pairs("split_gemm_pair_rp_pool", residual_pair=residual_pair)
     m, ch = a_pair.shape[0], a_pair.shape[1] // 2
     n, k = b_pair.shape[0], b_pair.shape[1] // 2
     if k != ch or m % pool_rows or (residual_pair is not None and residual_pair.shape != (m, 2 * n)):
         raise RuntimeError("split_gemm_pair_rp_pool: shape mismatch")
     dev = a_pair.device
-    c = torch.empty((m, n), dtype=torch.float32, device=dev) if out_f32 else None
-    cp = torch.empty((m, 2 * n), dtype=torch.bfloat16, device=dev) if out_pair else None
+    c, cp = _gemm_results(m, n, out_f32, out_pair, dev)
     pooled = torch.zeros((m // pool_rows, n), dtype=torch.float32, device=dev)
     if m == 0 or n == 0:
         return c, cp, pooled
@@ -1190,9 +1186,7 @@ def split_gemm_pair_rp_pool(a_pair, b_pair, bias, residual_pair, relu, out_f32, 
         bias = _dev(bias, "bias")
     with _on(dev):
         rc = _L.ovis_split_gemm_pair_rp_pool(a_pair.data_ptr(), 2 * a_pair.stride(0), b_pair.data_ptr(), 2 * b_pair.stride(0),
-                                             0 if c is None else c.data_ptr(), n, 0 if cp is None else cp.data_ptr(), 4 * n,
-                                             0 if bias is None else bias.data_ptr(),
-                                             0 if residual_pair is None else residual_pair.data_ptr(),
+                                             _ptr(c), n, _ptr(cp), 4 * n, _ptr(bias), _ptr(residual_pair),
                                              0 if residual_pair is None else 2 * residual_pair.stride(0), m, n, ch,
                                              int(bool(relu)), pooled.data_ptr(), int(pool_rows), 1.0 / pool_rows, _stream())
     _lib.check(rc, "split_gemm_pair_rp_pool")
@@ -1212,8 +1206,7 @@ def weight_prep_pair(w, scale=None, want_transposed=False):
     if scale is not None:
         scale = _dev(scale.detach(), "scale")
     with _on(w.device):
-        rc = _L.ovis_weight_prep_pair_f32(w.data_ptr(), 0 if scale is None else scale.data_ptr(), fwd.data_ptr(),
-                                          0 if bwd is None else bwd.data_ptr(), n, c, t, _stream())
+        rc = _L.ovis_weight_prep_pair_f32(w.data_ptr(), _ptr(scale), fwd.data_ptr(), _ptr(bwd), n, c, t, _stream())
     _lib.check(rc, "weight_prep_pair")
     return fwd, bwd
 
@@ -1221,9 +1214,7 @@ def weight_prep_pair(w, scale=None, want_transposed=False):
 def split_gemm_pair_gated(a_pair, b_pair, gate_pair, conv=None, out_f32=False, out_pair=True, config=0):
     """(A @ B^T) * (y > 0) with y given in pair layout (``gate_pair`` [M, 2N]): the data gradient of a layer behind a
     ReLU, gated and split for the next backward GEMM in the epilogue.  Returns (f32 or None, pair or None)."""
-    for t, name in ((a_pair, "a_pair"), (b_pair, "b_pair"), (gate_pair, "gate_pair")):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError(f"split_gemm_pair_gated: {name} must be a 2-D bfloat16 HIP tensor in pair layout")
+    _check_pairs("split_gemm_pair_gated", a_pair=a_pair, b_pair=b_pair, gate_pair=gate_pair)
     m, ch = a_pair.shape[0], a_pair.shape[1] // 2
     n, k = b_pair.shape[0], b_pair.shape[1] // 2
     h = w = 0
@@ -1234,20 +1225,17 @@ def split_gemm_pair_gated(a_pair, b_pair, gate_pair, conv=None, out_f32=False, o
     if k != kh * kw * ch or gate_pair.shape != (m, 2 * n):
         raise RuntimeError("split_gemm_pair_gated: shape mismatch")
     dev = a_pair.device
-    c = torch.empty((m, n), dtype=torch.float32, device=dev) if out_f32 else None
-    cp = torch.empty((m, 2 * n), dtype=torch.bfloat16, device=dev) if out_pair else None
+    c, cp = _gemm_results(m, n, out_f32, out_pair, dev)
     if m == 0 or n == 0:
         return c, cp
     with _on(dev):
         # under-filled grids take the plan's K slices (the slab reduction applies the gate)
         config = _gemm_cfg(config)
-        nbytes = _gemm_ws_bytes(m, n, ch, 0, kh, kw, w, config) if not (config & 8) else 0
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev) if nbytes else None
+        ws, nbytes = _gemm_workspace(dev, m, n, ch, 0, kh, kw, w, config)
         rc = _L.ovis_split_gemm_pair_gated_ws(a_pair.data_ptr(), 2 * a_pair.stride(0), b_pair.data_ptr(),
-                                              2 * b_pair.stride(0), 0 if c is None else c.data_ptr(), n,
-                                              0 if cp is None else cp.data_ptr(), 4 * n, gate_pair.data_ptr(),
+                                              2 * b_pair.stride(0), _ptr(c), n, _ptr(cp), 4 * n, gate_pair.data_ptr(),
                                               2 * gate_pair.stride(0), m, n, ch, kh, kw, h, w, int(bool(flip)),
-                                              0 if ws is None else ws.data_ptr(), nbytes, config, _stream())
+                                              _ptr(ws), nbytes, config, _stream())
     _lib.check(rc, "split_gemm_pair_gated")
     return c, cp
 
@@ -1256,22 +1244,18 @@ def split_gemm_pair_rp_gated(a_pair, b_pair, residual_pair, gate_pair, out_f32=F
     """(A @ B^T + r) * (x > 0) with r (``residual_pair``) and x (``gate_pair``) [M, 2N] in pair layout: the input gradient
     of an identity bottleneck, gated by the ReLU of the block below and split for its backward GEMMs in the epilogue
     (``ovis_split_gemm_pair_rp_gated``).  Returns (f32 or None, pair or None)."""
-    for t, name in ((a_pair, "a_pair"), (b_pair, "b_pair"), (residual_pair, "residual_pair"), (gate_pair, "gate_pair")):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError(f"split_gemm_pair_rp_gated: {name} must be a 2-D bfloat16 HIP tensor in pair layout")
+    _check_pairs("split_gemm_pair_rp_gated", a_pair=a_pair, b_pair=b_pair, residual_pair=residual_pair, gate_pair=gate_pair)
     m, ch = a_pair.shape[0], a_pair.shape[1] // 2
     n, k = b_pair.shape[0], b_pair.shape[1] // 2
     if k != ch or gate_pair.shape != (m, 2 * n) or residual_pair.shape != (m, 2 * n):
         raise RuntimeError("split_gemm_pair_rp_gated: shape mismatch")
     dev = a_pair.device
-    c = torch.empty((m, n), dtype=torch.float32, device=dev) if out_f32 else None
-    cp = torch.empty((m, 2 * n), dtype=torch.bfloat16, device=dev) if out_pair else None
+    c, cp = _gemm_results(m, n, out_f32, out_pair, dev)
     if m == 0 or n == 0:
         return c, cp
     with _on(dev):
         rc = _L.ovis_split_gemm_pair_rp_gated(a_pair.data_ptr(), 2 * a_pair.stride(0), b_pair.data_ptr(),
-                                              2 * b_pair.stride(0), 0 if c is None else c.data_ptr(), n,
-                                              0 if cp is None else cp.data_ptr(), 4 * n, residual_pair.data_ptr(),
+                                              2 * b_pair.stride(0), _ptr(c), n, _ptr(cp), 4 * n, residual_pair.data_ptr(),
                                               2 * residual_pair.stride(0), gate_pair.data_ptr(), 2 * gate_pair.stride(0), m, n,
                                               ch, config, _stream())
     _lib.check(rc, "split_gemm_pair_rp_gated")
@@ -1292,9 +1276,7 @@ def split_gemm_pair_tn(g_pair, x_pair, conv=None, scale=None, weight_shape=None)
     NHWC tensor read shifted by every tap (the 3x3 weight gradient without im2col rows).  With ``weight_shape`` =
     (N, ch, kh, kw) the slabs are reduced straight into that layout, times ``scale[N]`` (the folded FrozenBN scale) --
     the gradient of the raw convolution weight in one extra launch.  csrc/split_gemm.hip."""
-    for t, name in ((g_pair, "g_pair"), (x_pair, "x_pair")):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError(f"split_gemm_pair_tn: {name} must be a 2-D bfloat16 HIP tensor in pair layout")
+    _check_pairs("split_gemm_pair_tn", g_pair=g_pair, x_pair=x_pair)
     m, n, ch = g_pair.shape[0], g_pair.shape[1] // 2, x_pair.shape[1] // 2
     if x_pair.shape[0] != m:
         raise RuntimeError("split_gemm_pair_tn: row counts differ")
@@ -1321,8 +1303,7 @@ def split_gemm_pair_tn(g_pair, x_pair, conv=None, scale=None, weight_shape=None)
         dw = torch.empty(weight_shape, dtype=torch.float32, device=dev)
         if scale is not None:
             scale = _dev(scale.detach(), "scale")
-        rc = _L.ovis_slab_reduce_f32(slabs.data_ptr(), 0 if scale is None else scale.data_ptr(), dw.data_ptr(), slices, n,
-                                     ch, kh * kw, _stream())
+        rc = _L.ovis_slab_reduce_f32(slabs.data_ptr(), _ptr(scale), dw.data_ptr(), slices, n, ch, kh * kw, _stream())
     _lib.check(rc, "slab_reduce")
     return dw
 
@@ -1336,9 +1317,7 @@ def bias_act_(y, bias=None, residual=None, relu=True):
     if y.numel() == 0:
         return y
     with _on(y.device):
-        rc = _L.ovis_bias_act_f32(y.data_ptr(), 0 if bias is None else bias.data_ptr(),
-                                  0 if residual is None else residual.data_ptr(), y.shape[0], y.shape[1],
-                                  int(bool(relu)), _stream())
+        rc = _L.ovis_bias_act_f32(y.data_ptr(), _ptr(bias), _ptr(residual), y.shape[0], y.shape[1], int(bool(relu)), _stream())
     _lib.check(rc, "bias_act")
     return y
 
@@ -1364,7 +1343,7 @@ def gemm_nt(a, b, bias=None):
         bias = _dev(bias, "bias")
     with _on(a.device):
         _gemm_raw(a.data_ptr(), a.stride(0), a.stride(1), b.data_ptr(), b.stride(0), b.stride(1), out.data_ptr(), n, m, n, k,
-                  bias_ptr=0 if bias is None else bias.data_ptr(), device=a.device)
+                  bias_ptr=_ptr(bias), device=a.device)
     return out
 
 
@@ -1447,10 +1426,10 @@ def polygons_to_masks(coords, polygon_start, instance_start, size):
     if g:
         with _on(out.device):
             nbytes = _L.ovis_polygons_to_masks_workspace_bytes(npoly, w, h)
-            ws = torch.empty((nbytes,), dtype=torch.uint8, device=out.device)
+            ws = _workspace(nbytes, out.device)
             rc = _L.ovis_polygons_to_masks_u8(coords.data_ptr() if coords.numel() else 0, polygon_start.data_ptr(),
-                                              instance_start.data_ptr(), g, npoly, w, h, ws.data_ptr() if nbytes else 0, nbytes,
-                                              out.data_ptr(), _stream())
+                                              instance_start.data_ptr(), g, npoly, w, h, _ptr(ws), nbytes, out.data_ptr(),
+                                              _stream())
         _lib.check(rc, "polygons_to_masks")
     return out
 
@@ -1473,7 +1452,7 @@ def transform_images(data, desc, mean, std, to_bgr255, pad_hw, max_in_hw=None):
         nbytes = _L.ovis_transform_images_workspace_bytes(b, max_h, pad_w)
         out = torch.empty((b, 3, pad_h, pad_w), dtype=torch.float32, device=data.device)
         if b:
-            ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=data.device)
+            ws = _workspace(nbytes, data.device, at_least=1)
             rc = _L.ovis_transform_images_u8(data.data_ptr(), data.numel(), desc.data_ptr(), b, max_h, max_w, m3, s3,
                                              int(bool(to_bgr255)), pad_h, pad_w, ws.data_ptr(), nbytes, out.data_ptr(), _stream())
             _lib.check(rc, "transform_images")
@@ -1491,8 +1470,7 @@ def weighted_ce_fwd_bwd(logits, labels, bg_weight, need_grad=True):
     scratch = torch.empty((max(p, 1),), dtype=torch.float32, device=logits.device)
     with _on(logits.device):
         rc = _L.ovis_weighted_ce_fwd_bwd_f32(logits.data_ptr(), labels.data_ptr(), bg_weight, loss.data_ptr(),
-                                             0 if dlogits is None else dlogits.data_ptr(), scratch.data_ptr(), p, c,
-                                             _stream())
+                                             _ptr(dlogits), scratch.data_ptr(), p, c, _stream())
     _lib.check(rc, "weighted_ce_fwd_bwd")
     return loss[0], dlogits
 
@@ -1515,19 +1493,18 @@ def mask_bce_stochastic_fwd_bwd(mu, sigma, eps, pos_index, targets, channel, nee
     dsigma = torch.empty((p, 1, mu.shape[2], mu.shape[3]), dtype=torch.float32, device=mu.device) \
         if (need_grad and sigma is not None) else None
     scratch = torch.empty((max(npos, 1),), dtype=torch.float32, device=mu.device)
-    ptr = lambda t: 0 if t is None else t.data_ptr()
     with _on(mu.device):
         if torch.is_tensor(channel):
             channel = _dev(channel, "channel", torch.int64)
             if channel.numel() != npos:
                 raise RuntimeError(f"mask_bce_stochastic_fwd_bwd: {channel.numel()} channels for {npos} positives")
-            rc = _L.ovis_mask_bce_stochastic_classes_fwd_bwd_f32(mu.data_ptr(), ptr(sigma), ptr(eps), pos_index.data_ptr(),
+            rc = _L.ovis_mask_bce_stochastic_classes_fwd_bwd_f32(mu.data_ptr(), _ptr(sigma), _ptr(eps), pos_index.data_ptr(),
                                                                  channel.data_ptr(), targets.data_ptr(), loss.data_ptr(),
-                                                                 ptr(dmu), ptr(dsigma), scratch.data_ptr(), p, npos, c, mm,
+                                                                 _ptr(dmu), _ptr(dsigma), scratch.data_ptr(), p, npos, c, mm,
                                                                  _stream())
         else:
-            rc = _L.ovis_mask_bce_stochastic_fwd_bwd_f32(mu.data_ptr(), ptr(sigma), ptr(eps), pos_index.data_ptr(),
-                                                         targets.data_ptr(), loss.data_ptr(), ptr(dmu), ptr(dsigma),
+            rc = _L.ovis_mask_bce_stochastic_fwd_bwd_f32(mu.data_ptr(), _ptr(sigma), _ptr(eps), pos_index.data_ptr(),
+                                                         targets.data_ptr(), loss.data_ptr(), _ptr(dmu), _ptr(dsigma),
                                                          scratch.data_ptr(), p, npos, c, mm, channel, _stream())
     _lib.check(rc, "mask_bce_stochastic_fwd_bwd")
     return loss[0], dmu, dsigma
@@ -1539,10 +1516,9 @@ def _gemm_raw(a_ptr, a_rs, a_ks, b_ptr, b_rs, b_ks, c_ptr, c_rs, m, n, k, bias_p
     """C = alpha * A . B^T (+ C) + bias on raw pointers.  Products with too few tiles to fill the chip are cut along K
     into slabs of a workspace allocated here (summed in slice order by the library: no atomics)."""
     ws_bytes = _gemm_f32_ws_bytes(m, n, k)
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=device or torch.device("cuda", torch.cuda.current_device())) \
-        if ws_bytes else None
+    ws = _workspace(ws_bytes, device or torch.device("cuda", torch.cuda.current_device()))
     rc = _L.ovis_gemm_ex_ws_f32(a_ptr, a_rs, a_ks, b_ptr, b_rs, b_ks, bias_ptr, bias_per_row, alpha, accumulate, c_ptr,
-                                c_rs, m, n, k, 0 if ws is None else ws.data_ptr(), ws_bytes, _stream())
+                                c_rs, m, n, k, _ptr(ws), ws_bytes, _stream())
     _lib.check(rc, "gemm_ex_ws_f32")
 
 
@@ -1587,7 +1563,7 @@ def _dcn_forward(input, weight, bias, offset, mask, output, kH, kW, dH, dW, padH
         rows = torch.empty((b * plane, cout), dtype=torch.float32, device=input.device)
         with _on(input.device):
             rc = _L.ovis_deform_conv_implicit_f32(x_nhwc.data_ptr(), offset.data_ptr(),
-                                                  0 if mask is None else mask.data_ptr(), wp.data_ptr(), 2 * wp.stride(0),
+                                                  _ptr(mask), wp.data_ptr(), 2 * wp.stride(0),
                                                   0 if bias is None else _dev(bias, "bias").data_ptr(), rows.data_ptr(),
                                                   cout, b, cin, h, w, cout, ho, wo, kH, kW, dH, dW, padH, padW, dilH, dilW,
                                                   dg, _stream())
@@ -1687,7 +1663,7 @@ def _dcn_backward_rows(input, weight, offset, mask, grad_output, grad_input, gra
     gy = grad_output.permute(0, 2, 3, 1).reshape(rows, cout)              # NHWC rows of dY
     gyp = split_pair(gy.contiguous())
     geom = (b, cin, h, w, ho, wo, kH, kW, dH, dW, padH, padW, dilH, dilW, dg)
-    mptr = 0 if mask is None else mask.data_ptr()
+    mptr = _ptr(mask)
     if grad_input is not None or grad_offset is not None:
         wt = split_pair(weight.permute(2, 3, 1, 0).reshape(T * cin, cout).contiguous())   # B[(t, c), n] = w[n, c, t]
         dcol, _ = split_gemm_pair(gyp, wt)                                                   # [rows, T * cin] f32
@@ -1698,9 +1674,7 @@ def _dcn_backward_rows(input, weight, offset, mask, grad_output, grad_input, gra
                 grad_mask.zero_()
         with _on(dev):
             rc = _L.ovis_deform_col2im_rows_f32(dcol.data_ptr(), dcol.stride(0), x_nhwc.data_ptr(), offset.data_ptr(), mptr,
-                                                0 if dx is None else dx.data_ptr(),
-                                                0 if grad_offset is None else grad_offset.data_ptr(),
-                                                0 if grad_mask is None else grad_mask.data_ptr(), *geom, _stream())
+                                                _ptr(dx), _ptr(grad_offset), _ptr(grad_mask), *geom, _stream())
         _lib.check(rc, "deform_col2im_rows")
         if dx is not None:
             grad_input += dx.permute(0, 3, 1, 2)
@@ -1753,7 +1727,9 @@ def modulated_deform_conv_backward(input, weight, bias, ones, offset, mask, colu
 
 
 # ---- optimizer (engine/solver.py) ------------------------------------------------------------------------------------
-_BB_WS = {}
+@functools.lru_cache(maxsize=None)
+def _bottleneck_bwd_ws_bytes(m, cin, mid, kh, kw, w, config):
+    return int(_L.ovis_bottleneck_identity_backward_workspace_bytes(m, cin, mid, kh, kw, w, config))
 
 
 def bottleneck_identity_backward(g3p, xp, o1p, o2p, t1, t2, t3, scales, geom, weight_shapes, side_stream=None):
@@ -1762,9 +1738,7 @@ def bottleneck_identity_backward(g3p, xp, o1p, o2p, t1, t2, t3, scales, geom, we
     g3p [M, 2C] gated output gradient, xp / o1p / o2p the block's input and conv1 / conv2 outputs, t1 / t2 / t3 the transposed
     weight pair forms, scales (s1, s2, s3) or Nones, geom (h, w, kh, kw), weight_shapes (w1, w2, w3 shapes) ->
     (gx pair [M, 2C], dw1, dw2, dw3).  Pair tensors: 2-D bfloat16 with unit column stride."""
-    for t in (g3p, xp, o1p, o2p, t1, t2, t3):
-        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1):
-            raise RuntimeError("bottleneck_identity_backward: 2-D bfloat16 HIP tensors in pair layout expected")
+    _check_pairs("bottleneck_identity_backward", g3p=g3p, xp=xp, o1p=o1p, o2p=o2p, t1=t1, t2=t2, t3=t3)
     m, cin, mid = g3p.shape[0], g3p.shape[1] // 2, o1p.shape[1] // 2
     h, w, kh, kw = geom
     if (xp.shape != (m, 2 * cin) or o1p.shape[0] != m or o2p.shape != (m, 2 * mid) or t1.shape != (cin, 2 * mid)
@@ -1776,20 +1750,15 @@ def bottleneck_identity_backward(g3p, xp, o1p, o2p, t1, t2, t3, scales, geom, we
     gx = torch.empty((m, 2 * cin), dtype=torch.bfloat16, device=dev)
     dw1, dw2, dw3 = (torch.empty(tuple(sh), dtype=torch.float32, device=dev) for sh in weight_shapes)
     config = _gemm_cfg(0)
-    key = (m, cin, mid, kh, kw, w, config)
-    nbytes = _BB_WS.get(key)
-    if nbytes is None:
-        nbytes = _BB_WS[key] = int(_L.ovis_bottleneck_identity_backward_workspace_bytes(m, cin, mid, kh, kw, w, config))
-    ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    ws = _workspace(_bottleneck_bwd_ws_bytes(m, cin, mid, kh, kw, w, config), dev, at_least=256)
     s1, s2, s3 = (None if s is None else _dev(s.detach(), "scale") for s in scales)
     with _on(dev):
         rc = _L.ovis_bottleneck_identity_backward(
             g3p.data_ptr(), 2 * g3p.stride(0), xp.data_ptr(), 2 * xp.stride(0), o1p.data_ptr(), 2 * o1p.stride(0),
             o2p.data_ptr(), 2 * o2p.stride(0), t1.data_ptr(), 2 * t1.stride(0), t2.data_ptr(), 2 * t2.stride(0),
-            t3.data_ptr(), 2 * t3.stride(0), 0 if s1 is None else s1.data_ptr(), 0 if s2 is None else s2.data_ptr(),
-            0 if s3 is None else s3.data_ptr(), m, cin, mid, kh, kw, h, w, g2p.data_ptr(), g1p.data_ptr(), gx.data_ptr(),
-            dw1.data_ptr(), dw2.data_ptr(), dw3.data_ptr(), ws.data_ptr(), ws.numel(), config, _stream(),
-            0 if side_stream is None else side_stream.cuda_stream)
+            t3.data_ptr(), 2 * t3.stride(0), _ptr(s1), _ptr(s2), _ptr(s3), m, cin, mid, kh, kw, h, w, g2p.data_ptr(),
+            g1p.data_ptr(), gx.data_ptr(), dw1.data_ptr(), dw2.data_ptr(), dw3.data_ptr(), ws.data_ptr(), ws.numel(), config,
+            _stream(), 0 if side_stream is None else side_stream.cuda_stream)
     _lib.check(rc, "bottleneck_identity_backward")
     return gx, dw1, dw2, dw3
 

@@ -1,117 +1,87 @@
-"""ctypes binding of libovis_hip.so (C ABI: include/ovis_hip.h).  No torch types cross it."""
+"""ctypes binding of libovis_hip.so (C ABI: include/ovis_hip.h).  No torch types cross it.
+
+The header is the single source of the binding: every ``.hip`` file includes it, so the compiler checks each definition
+against its declaration, and ``parse_header`` below turns the same declarations into the ``(restype, argtypes)`` table
+and the ``OVIS_*`` constants at import.  It reads only the subset of C the two headers (this one and include/ovis_cpu.h)
+use, and raises on anything else -- a type it does not know is never given a default.  Both libraries are built in-tree
+by csrc/Makefile, so the headers are found in the checkout's ``include/``."""
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libovis_hip.so")
+INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
-OVIS_OK = 0
-_ERRORS = {-1: "OVIS_EINVAL (bad size or null pointer)",
-           -2: "OVIS_ENOSPC (workspace too small)",
-           -3: "OVIS_ERANGE (problem size not supported by the kernel)"}
+_BY_VALUE = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
+             "uint64_t": ctypes.c_uint64}
+_POINTEES = {"void", "float", "double", "int32_t", "int64_t", "uint32_t", "uint64_t", "uint8_t"}
 
-_vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
 
-# name -> (restype, argtypes); must list every symbol include/ovis_hip.h declares
-SIGNATURES = {
-    "ovis_version": (ctypes.c_char_p, []),
-    "ovis_roi_align_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
-    "ovis_roi_align_forward_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ovis_roi_align_forward_mfma_supported": (_i, [_i, _i, _i, _i]),
-    "ovis_roi_align_forward_ws_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
-    "ovis_roi_align_forward_strided_from_nhwc_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _vp]),
-    "ovis_roi_align_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
-    "ovis_roi_align_backward_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ovis_roi_align_backward_plane_supported": (_i, [_i, _i, _i, _i]),
-    "ovis_roi_align_backward_ws_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
-    "ovis_roi_align_backward_strided_ws_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
-    "ovis_roi_align_backward_strided_nhwc_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ovis_roi_align_backward_strided_nhwc_ws_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
-    "ovis_roi_pool_forward_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp]),
-    "ovis_roi_pool_backward_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "ovis_deform_psroi_pool_forward_f32": (_i, [_vp] * 5 + [_i] * 7 + [_f] + [_i] * 5 + [_f, _vp]),
-    "ovis_deform_psroi_pool_backward_f32": (_i, [_vp] * 7 + [_i] * 7 + [_f] + [_i] * 5 + [_f, _vp]),
-    "ovis_nms_workspace_bytes": (_sz, [_i]),
-    "ovis_nms_f32": (_i, [_vp, _vp, _i, _f, _i, _vp, _sz, _vp, _vp, _vp]),
-    "ovis_nms_grouped_f32": (_i, [_vp, _vp, _vp, _i, _f, _i, _vp, _sz, _vp, _vp, _vp]),
-    "ovis_sample_fg_bg": (_i, [_vp, _i, _i, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
-    "ovis_project_pasted_masks_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
-    "ovis_paste_masks_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
-    "ovis_pasted_rle_count": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp]),
-    "ovis_pasted_rle_runs": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
-    "ovis_pasted_rle_string": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
-    "ovis_render_instances_u8": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp]),
-    "ovis_nms_presorted_workspace_bytes": (_sz, [_i, _i]),
-    "ovis_nms_presorted_batched_f32": (_i, [_vp, _vp, _i, _i, _f, _i, _i, _vp, _sz, _vp, _vp, _vp]),
-    "ovis_box_decode_f32": (_i, [_vp, _l, _vp, _l, _l, _i, _f, _f, _f, _f, _f, _i, _vp, _vp, _vp, _vp]),
-    "ovis_view_merge_count_f32": (_i, [_vp, _l, _i, _i, _vp, _vp, _i, _f, _vp, _l, _vp]),
-    "ovis_view_merge_scan_i32": (_i, [_vp, _l, _vp, _vp]),
-    "ovis_view_merge_scatter_f32": (_i, [_vp, _vp, _l, _i, _i, _vp, _vp, _i, _f, _vp, _l, _l, _vp, _vp, _vp, _vp, _vp]),
-    "ovis_smooth_l1_picked_fwd_bwd_f32": (_i, [_vp, _l, _i, _i, _vp, _l, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp]),
-    "ovis_gather_rows": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ovis_rois_from_boxes_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
-    "ovis_deform_conv_implicit_f32": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _l] + [_i] * 16 + [_vp]),
-    "ovis_topk_sorted_workspace_bytes": (_sz, [_i, _i]),
-    "ovis_topk_sorted_f32": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ovis_rpn_decode_f32": (_i, [_vp, _l, _l, _l, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
-    "ovis_sigmoid_focal_loss_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
-    "ovis_sigmoid_focal_loss_backward_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _vp]),
-    "ovis_split_bf16x3_f32": (_i, [_vp, _l, _vp, _l, _i, _i, _vp]),
-    "ovis_im2col_split_bf16x3_f32": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _i, _vp]),
-    "ovis_bias_act_f32": (_i, [_vp, _vp, _vp, _l, _i, _i, _vp]),
-    "ovis_split_pair_f32": (_i, [_vp, _l, _vp, _l, _i, _vp]),
-    "ovis_gate_split_pair_rows_f32": (_i, [_vp, _l, _vp, _i, _vp, _vp, _l, _i, _vp, _i, _vp, _vp, _vp]),
-    "ovis_gate_split_pair_f32": (_i, [_vp, _l, _vp, _i, _vp, _vp, _l, _i, _vp, _i, _vp]),
-    "ovis_im2col_nchw_pair_f32": (_i, [_vp, _vp] + [_i] * 9 + [_vp]),
-    "ovis_weight_prep_pair_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ovis_slab_reduce_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ovis_im2col_pair": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
-    "ovis_split_gemm_tn_slices": (_i, [_l, _i, _i, _i]),
-    "ovis_split_gemm_tn_map_slices": (_i, [_l, _i, _i, _i, _i, _i, _i]),
-    "ovis_split_gemm_pair_tn": (_i, [_vp, _l, _vp, _l, _vp, _i, _l, _i, _i, _i, _i, _i, _i, _vp]),
-    "ovis_split_gemm_pair_gated": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _l] + [_i] * 8 + [_vp]),
-    "ovis_split_gemm_pair_gated_ws": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _l] + [_i] * 7 + [_vp, _sz, _i, _vp]),
-    "ovis_split_gemm_pair_workspace_bytes": (_sz, [_l, _i, _i, _i, _i, _i, _i]),
-    "ovis_split_gemm_pair_workspace_bytes_ex": (_sz, [_l, _i, _i, _i, _i, _i, _i, _i]),
-    "ovis_split_gemm_pair_rp_gated": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _l, _i, _i, _i, _vp]),
-    "ovis_split_gemm_pair_pool_supported": (_i, [_l, _i, _i, _i]),
-    "ovis_split_gemm_pair_rp_pool": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _l, _l, _i, _i, _i, _vp, _i, _f, _vp]),
-    "ovis_split_gemm_pair_rp": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _l, _l, _i, _i, _i, _vp, _sz, _i, _vp]),
-    "ovis_split_gemm_pair": (_i, [_vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _l, _vp, _vp, _l, _l] + [_i] * 9
-                             + [_vp, _sz, _i, _vp]),
-    "ovis_match_encode_f32": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "ovis_rpn_match_encode_f32": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
-    "ovis_project_masks_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ovis_gemm_f32": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _vp, _l, _i, _i, _i, _vp]),
-    "ovis_gemm_ex_f32": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _i, _f, _i, _vp, _l, _i, _i, _i, _vp]),
-    "ovis_gemm_f32_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ovis_gemm_ex_ws_f32": (_i, [_vp, _l, _l, _vp, _l, _l, _vp, _i, _f, _i, _vp, _l, _i, _i, _i, _vp, _sz, _vp]),
-    "ovis_deform_im2col_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp]),
-    "ovis_deform_col2im_f32": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp]),
-    "ovis_deform_col2im_coord_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 13 + [_vp]),
-    "ovis_deform_im2col_pair_rows_f32": (_i, [_vp, _vp, _vp, _vp, _l] + [_i] * 15 + [_vp]),
-    "ovis_deform_col2im_rows_f32": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 15 + [_vp]),
-    "ovis_region_noun_align_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "ovis_text_embed_f32": (_i, [_vp, _l, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "ovis_project_polygon_masks_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "ovis_polygons_to_masks_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ovis_polygons_to_masks_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
-    "ovis_transform_images_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ovis_transform_images_u8": (_i, [_vp, _l, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
-    "ovis_sgd_momentum_multi_f32": (_i, [_vp, _vp, _i, _f, _f, _f, _i, _vp]),
-    "ovis_bottleneck_identity_backward_workspace_bytes": (_sz, [_l, _i, _i, _i, _i, _i, _i]),
-    "ovis_bottleneck_identity_backward": (_i, [_vp, _l] * 7 + [_vp] * 3 + [_l, _i, _i, _i, _i, _i, _i] + [_vp] * 7 + [_sz, _i, _vp, _vp]),
-    "ovis_weight_prep_pair_multi_f32": (_i, [_vp, _vp, _i, _i, _vp]),
-    "ovis_weight_prep_tile": (_i, []),
-    "ovis_sgd_chunk_elements": (_i, []),
-    "ovis_weighted_ce_fwd_bwd_f32": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp]),
-    "ovis_mask_bce_stochastic_fwd_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "ovis_mask_bce_stochastic_classes_fwd_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ovis_coco_box_iou_f64": (_i, [_vp, _vp, _vp, _vp, _i, _l, _vp, _vp]),
-    "ovis_coco_pack_masks_u64": (_i, [_vp, _i, _l, _vp, _vp, _vp]),
-    "ovis_coco_mask_iou_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _vp, _vp]),
-    "ovis_coco_match": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _l, _l, _vp, _vp, _vp, _vp]),
-}
+def _ctype(decl, where, is_return=False):
+    """The ctypes type of one parameter (``const float* const* boxes``, ``float mean[3]``, ``long m``) or return type."""
+    tokens = [t[0] if t[0] in "*[" else t for t in re.findall(r"\*|\[\d*\]|\w+", decl)]
+    words = [t for t in tokens if t not in ("*", "[", "const")]
+    # nothing but those tokens; at most the type and, for a parameter, its name
+    if re.sub(r"\*|\[\d*\]|\w+|\s", "", decl) or not words or len(words) > (1 if is_return else 2):
+        raise TypeError(f"{where}: cannot read '{decl.strip()}'")
+    base, pointer = words[0], "*" in tokens or "[" in tokens
+    if not pointer and base in _BY_VALUE:
+        return _BY_VALUE[base]
+    if pointer and is_return and base == "char":
+        return ctypes.c_char_p
+    if pointer and not is_return and base in _POINTEES:
+        return ctypes.c_void_p
+    raise TypeError(f"{where}: type '{decl.strip()}' is outside the vocabulary of the binding")
+
+
+def parse_header(text):
+    """-> ({name: (restype, argtypes)} of every ``ovis_*`` prototype, {name: value} of every integer ``#define OVIS_*``).
+    Anything that is left over once comments, preprocessor lines, the ``extern "C"`` braces and the prototypes are taken
+    out raises: a declaration this parser cannot read is never skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(OVIS_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    signatures = {}
+
+    def take(m):
+        name = m[2]
+        params = [] if m[3].strip() in ("", "void") else m[3].split(",")
+        signatures[name] = (_ctype(m[1], f"{name}: return type", True),
+                            [_ctype(p, f"{name}: parameter {i}") for i, p in enumerate(params)])
+        return " "
+
+    rest = re.sub(r"([\w\s*]+?)\b(ovis_\w+)\s*\(([^()]*)\)\s*;", take, text)
+    rest = re.sub(r'extern\s+"C"\s*\{|\}', " ", rest).strip()
+    if rest:
+        raise TypeError(f"header text the binding cannot read: '{rest[:80]}'")
+    return signatures, constants
+
+
+def read_header(name):
+    path = os.path.join(INCLUDE_DIR, name)
+    if not os.path.exists(path):
+        raise ImportError(f"{path} is missing: the binding of the native libraries is derived from it")
+    with open(path) as f:
+        return parse_header(f.read())
+
+
+def bind(path, signatures):
+    lib = ctypes.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
+# name -> (restype, argtypes) of every symbol include/ovis_hip.h declares, and its constants as OVIS_OK, OVIS_ERANGE,
+# OVIS_BOX_DECODE_MAX_IMAGES, ... attributes of this module
+SIGNATURES, CONSTANTS = read_header("ovis_hip.h")
+globals().update(CONSTANTS)
+_ERRORS = {CONSTANTS[name]: f"{name} ({text})" for name, text in (
+    ("OVIS_EINVAL", "bad size or null pointer"), ("OVIS_ENOSPC", "workspace too small"),
+    ("OVIS_ERANGE", "problem size not supported by the kernel"))}
 
 _lib = None
 
@@ -124,17 +94,12 @@ def load():
             raise ImportError(
                 f"{LIB_PATH} is missing: build the HIP extension first "
                 "(make -C cvpr22_cross_modal_pseudo_labeling_amd/csrc). There is no CPU fallback.")
-        lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = lib
+        _lib = bind(LIB_PATH, SIGNATURES)
     return _lib
 
 
 def check(rc, what):
-    if rc == OVIS_OK:
+    if rc == OVIS_OK:  # noqa: F821 -- from the header
         return
     if rc < 0:
         raise RuntimeError(f"{what}: {_ERRORS.get(rc, rc)}")

@@ -23,6 +23,7 @@ namespace {
 constexpr int kTile = 64;          // == wavefront size == bits per mask word
 constexpr int kReduceThreads = 1024;
 constexpr int kMaxBlocks = 2048;   // K <= 131072 (keeps the reduce kernel under 64 KB of LDS)
+static_assert(kMaxBlocks * kTile == OVIS_NMS_MAX_CANDIDATES, "include/ovis_hip.h states the bound callers plan with");
 
 __device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
   unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);

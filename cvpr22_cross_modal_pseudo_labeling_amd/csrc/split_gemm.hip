@@ -1233,13 +1233,6 @@ extern "C" int ovis_split_pair_f32(const float* src, long src_row_stride, void* 
   return OVIS_OK;
 }
 
-extern "C" int ovis_gate_split_pair_f32(const float* dy, long dy_row_stride, const void* gate, int gate_is_pair,
-                                        void* dst_pair, float* g_f32, long rows, int cols, const float* g_pooled,
-                                        int pool_rows, void* stream) {
-  return ovis_gate_split_pair_rows_f32(dy, dy_row_stride, gate, gate_is_pair, dst_pair, g_f32, rows, cols, g_pooled,
-                                       pool_rows, nullptr, nullptr, stream);
-}
-
 extern "C" int ovis_gate_split_pair_rows_f32(const float* dy, long dy_row_stride, const void* gate, int gate_is_pair,
                                              void* dst_pair, float* g_f32, long rows, int cols, const float* g_pooled,
                                              int pool_rows, const float* g_selected, const int32_t* group_slot,
@@ -1794,18 +1787,8 @@ extern "C" int ovis_split_gemm_pair_rp_pool(const void* a_pair, long a_row_bytes
                               0, relu, nullptr, 0, 8, stream, pooled, pool_rows, pool_scale);
 }
 
-extern "C" int ovis_split_gemm_pair_gated(const void* a_pair, long a_row_bytes, const void* b_pair, long b_row_bytes,
-                                          float* c, long ldc, void* c_pair, long c_pair_row_bytes,
-                                          const void* gate_pair, long gate_row_bytes, long m, int n, int channels,
-                                          int taps_h, int taps_w, int height, int width, int flip, int config,
-                                          void* stream) {
-  if (!gate_pair || gate_row_bytes % 16 != 0 || ((uintptr_t)gate_pair & 15) || n % 32 != 0) return OVIS_ERANGE;
-  return split_gemm_pair_impl(a_pair, a_row_bytes, nullptr, 0, b_pair, b_row_bytes, c, ldc, c_pair, c_pair_row_bytes,
-                              nullptr, nullptr, 0, nullptr, 0, gate_pair, gate_row_bytes, m, n, channels, 0, taps_h, taps_w,
-                              height, width, flip, 0, nullptr, 0, config | 8, stream);
-}
-
-// The same with a split-K workspace (ovis_split_gemm_pair_workspace_bytes of the same problem): under-filled grids -- the
+// The data gradient behind a ReLU gate (see include/ovis_hip.h), with a split-K workspace
+// (ovis_split_gemm_pair_workspace_bytes of the same problem): under-filled grids -- the
 // data gradients of the teacher step's trainable trunk, 132 tiles walking 72 k-steps -- take the plan's K slices like
 // the forward products do; the gate is applied by the slab reduction's epilogue.
 extern "C" int ovis_split_gemm_pair_gated_ws(const void* a_pair, long a_row_bytes, const void* b_pair, long b_row_bytes,

@@ -143,8 +143,9 @@ int ovis_roi_align_backward_strided_nhwc_ws_f32(const float* grad_output_nhwc, c
  * ASCENDING original indices (int64) and n to *num_keep (device int32), entirely on the
  * device: no host round trip of the suppression mask.
  * `workspace` is caller-provided device scratch of at least
- * ovis_nms_workspace_bytes(K) bytes (256-byte aligned).
+ * ovis_nms_workspace_bytes(K) bytes (256-byte aligned).  K above OVIS_NMS_MAX_CANDIDATES: OVIS_ERANGE.
  * ---------------------------------------------------------------------------------- */
+#define OVIS_NMS_MAX_CANDIDATES 131072
 size_t ovis_nms_workspace_bytes(int num_boxes);
 int ovis_nms_f32(const float* boxes, const float* scores, int num_boxes, float threshold,
                  int ge_mode, void* workspace, size_t workspace_bytes, int64_t* keep_out,
@@ -366,12 +367,9 @@ int ovis_split_pair_f32(const float* src, long src_row_stride, void* dst_pair, l
  * a plain split).  threshold_backward of mb/modeling/backbone/resnet.py:323-344's relu_ calls.  cols % 32 == 0.
  * g_pooled != NULL: [rows / pool_rows, cols] f32, the gradient of the mean over every pool_rows consecutive rows
  * (the 7x7 average pooling of FastRCNNPredictor.forward, roi_box_predictors.py:62-66, behind the res5 head) is
- * added on the fly, g = (dy + g_pooled[row / pool_rows] / pool_rows) * (y > 0); dy may then be NULL. */
-int ovis_gate_split_pair_f32(const float* dy, long dy_row_stride, const void* gate, int gate_is_pair,
-                             void* dst_pair, float* g_f32, long rows, int cols, const float* g_pooled,
-                             int pool_rows, void* stream);
-/* The same with the gradient of a ROW-GROUP GATHER added on the fly: the rows come in groups of pool_rows (the 7x7
- * positions of one RoI); group_slot [rows / pool_rows] int32 holds, for a group that a consumer gathered (the mask
+ * added on the fly, g = (dy + g_pooled[row / pool_rows] / pool_rows) * (y > 0); dy may then be NULL.
+ * g_selected != NULL: the gradient of a ROW-GROUP GATHER is added on the fly as well: the rows come in groups of
+ * pool_rows (the 7x7 positions of one RoI); group_slot [rows / pool_rows] int32 holds, for a group that a consumer gathered (the mask
  * head reads the res5 features of the positive RoIs only: mb/modeling/roi_heads/mask_head/mask_head.py:13-41,62-66),
  * its index in g_selected [num_selected * pool_rows, cols] f32 (dense), -1 otherwise:
  * g = (dy + g_pooled[group] / pool_rows + g_selected[group_slot[group] * pool_rows + row in group]) * (y > 0).
@@ -401,17 +399,12 @@ int ovis_im2col_pair(const void* src_pair, void* dst_pair, long num, int height,
 /* ovis_split_gemm_pair for a data gradient whose result passes a ReLU gate: C = (A B^T) * (y > 0) with y the forward
  * activation in pair layout (gate_pair, rows gate_row_bytes apart; only the hi halves are read), written as fp32 (c)
  * and / or in pair layout (c_pair) -- the gate and the operand split of the NEXT backward GEMM in this epilogue.
- * n % 32 == 0. */
-int ovis_split_gemm_pair_gated(const void* a_pair, long a_row_bytes, const void* b_pair, long b_row_bytes,
-                               float* c, long ldc, void* c_pair, long c_pair_row_bytes, const void* gate_pair,
-                               long gate_row_bytes, long m, int n, int channels, int taps_h, int taps_w,
-                               int height, int width, int flip, int config, void* stream);
-
-/* ovis_split_gemm_pair_gated with a split-K workspace (size: ovis_split_gemm_pair_workspace_bytes(m, n, channels, 0,
- * taps_h, taps_w, width); NULL / too small = the un-split grid): grids that leave most CUs idle while every workgroup
- * walks a long K (the data gradients of a trainable trunk on 50 x 84 maps) are cut into K slices as in
- * ovis_split_gemm_pair; the slab reduction applies the gate and writes c / c_pair.  Same results as the un-split call up
- * to the fp32 summation order of the slices (fixed: reproducible). */
+ * n % 32 == 0.
+ * workspace: split-K scratch (size: ovis_split_gemm_pair_workspace_bytes(m, n, channels, 0, taps_h, taps_w, width);
+ * NULL / too small = the un-split grid): grids that leave most CUs idle while every workgroup walks a long K (the data
+ * gradients of a trainable trunk on 50 x 84 maps) are cut into K slices as in ovis_split_gemm_pair; the slab reduction
+ * applies the gate and writes c / c_pair.  Same results as the un-split grid up to the fp32 summation order of the slices
+ * (fixed: reproducible). */
 int ovis_split_gemm_pair_gated_ws(const void* a_pair, long a_row_bytes, const void* b_pair, long b_row_bytes,
                                   float* c, long ldc, void* c_pair, long c_pair_row_bytes, const void* gate_pair,
                                   long gate_row_bytes, long m, int n, int channels, int taps_h, int taps_w,
