@@ -1931,3 +1931,91 @@ def coco_match(iou, problems, det_areas, gt_areas, gt_crowd, area_ranges, thresh
                                 gt_ignore.data_ptr() if g else 0, _stream())
     _lib.check(rc, "coco_match")
     return dt_match, dt_ignore, gt_ignore
+
+
+COCO_RLE_STATUS = {_lib.OVIS_COCO_RLE_BAD_CHAR: "a character outside '0'..'o'",
+                   _lib.OVIS_COCO_RLE_UNTERMINATED: "the last value is not terminated",
+                   _lib.OVIS_COCO_RLE_OVERFLOW: "a value does not fit 32 bits",
+                   _lib.OVIS_COCO_RLE_NEGATIVE_RUN: "a negative run",
+                   _lib.OVIS_COCO_RLE_BAD_SUM: "the runs do not add up to height x width",
+                   _lib.OVIS_COCO_RLE_BAD_SIZE: "height < 1, width < 1 or height x width > 0x7fffffef"}
+
+
+def coco_rle_words(strings_or_runs, sizes):
+    """(words int64 [total], word_offsets int64 [P + 1], areas int64 [P], status int32 [P]), all on the device of ``sizes``:
+    the COCO RLE masks of a results file or of RLE annotations as the bit words of ``coco_pack_masks`` -- mask p's
+    ``words[word_offsets[p]:word_offsets[p + 1]]`` equals ``coco_pack_masks`` of the decoded mask, ``areas[p]`` its pixel
+    count (``ovis_coco_rle_count`` / ``_runs`` / ``ovis_coco_runs_to_words``; pycocotools' rleFrString + decode).
+    ``strings_or_runs``: a list whose items are ``str`` / ``bytes`` (the compressed ``counts``) or integer sequences (the
+    uncompressed ones), mixed freely; ``sizes``: int32 DEVICE tensor [P, 2] of (height, width), one per item -- masks of
+    different sizes share a call.  Nothing is checked here beyond dtypes and lengths: ``status[p]`` is 0 for a good mask and
+    a key of ``COCO_RLE_STATUS`` otherwise (all-zero words, area 0); the caller turns it into an error.  Integers outside
+    int32 in a list are clamped to its ends (such a list cannot add up to a valid size).  Two host reads: the sizes and the
+    value counts of the strings."""
+    sizes = _dev(sizes, "sizes", torch.int32)
+    items = list(strings_or_runs)
+    p, dev = len(items), sizes.device
+    if sizes.shape != (p, 2):
+        raise RuntimeError(f"coco_rle_words: expected sizes int32 [{p},2] (height, width), one row per mask")
+    if p > 65535:
+        raise RuntimeError("coco_rle_words: at most 65535 masks a call")
+    hw = sizes.cpu().long()
+    pixels = hw[:, 0] * hw[:, 1]
+    usable = (hw[:, 0] >= 1) & (hw[:, 1] >= 1) & (pixels <= 0x7fffffef)
+    word_offsets_host = torch.zeros(p + 1, dtype=torch.int64)
+    torch.cumsum(torch.where(usable, (pixels + 63) // 64, torch.zeros_like(pixels)), 0, out=word_offsets_host[1:])
+    words = torch.empty(int(word_offsets_host[-1]), dtype=torch.int64, device=dev)
+    areas, status = torch.empty(p, dtype=torch.int64, device=dev), torch.zeros(p, dtype=torch.int32, device=dev)
+    word_offsets = word_offsets_host.to(dev)
+    if p == 0:
+        return words, word_offsets, areas, status
+    texts, lists, lengths = [], {}, torch.zeros(p, dtype=torch.int64)
+    for k, item in enumerate(items):
+        if isinstance(item, str):
+            texts.append(item.encode("latin-1", "replace"))  # a character beyond a byte becomes '?': refused by the kernel
+        elif isinstance(item, (bytes, bytearray)):
+            texts.append(bytes(item))
+        else:
+            texts.append(b"")
+            values = torch.as_tensor(item).reshape(-1)
+            if values.is_floating_point() or values.dtype == torch.bool or values.is_complex():
+                raise RuntimeError(f"coco_rle_words: item {k} is neither a string nor a sequence of integers")
+            lists[k] = values.long().clamp(-2 ** 31, 2 ** 31 - 1).int()
+            lengths[k] = lists[k].numel()
+    char_offsets_host = torch.zeros(p + 1, dtype=torch.int64)
+    torch.cumsum(torch.tensor([len(t) for t in texts], dtype=torch.int64), 0, out=char_offsets_host[1:])
+    if int(char_offsets_host[-1]) > 2 ** 31 - 1:
+        raise RuntimeError("coco_rle_words: more than 2^31 - 1 characters in one call")
+    compressed = len(lists) < p
+    if compressed:
+        chars = torch.frombuffer(bytearray(b"".join(texts)) or bytearray(1), dtype=torch.uint8).to(dev)
+        char_offsets = char_offsets_host.to(dev)
+        num_runs = torch.empty(p, dtype=torch.int32, device=dev)
+        with _on(dev):
+            rc = _L.ovis_coco_rle_count(chars.data_ptr(), char_offsets.data_ptr(), p, num_runs.data_ptr(), _stream())
+        _lib.check(rc, "coco_rle_words")
+        lengths = lengths + num_runs.cpu().long()
+    run_offsets_host = torch.zeros(p + 1, dtype=torch.int64)
+    torch.cumsum(lengths, 0, out=run_offsets_host[1:])
+    run_offsets = run_offsets_host.to(dev)
+    total = int(run_offsets_host[-1])
+    if lists and not compressed:
+        runs = torch.cat(list(lists.values())).to(dev)
+    else:
+        runs = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    if compressed:
+        with _on(dev):
+            rc = _L.ovis_coco_rle_runs(chars.data_ptr(), char_offsets.data_ptr(), run_offsets.data_ptr(), p, runs.data_ptr(),
+                                       status.data_ptr(), _stream())
+        _lib.check(rc, "coco_rle_words")
+        if lists:  # the uncompressed items of a mixed call, into their slices
+            slots = torch.cat([torch.arange(len(v)) + run_offsets_host[k] for k, v in lists.items()])
+            runs[slots.to(dev)] = torch.cat(list(lists.values())).to(dev)
+    run_ends = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    max_words = int((word_offsets_host[1:] - word_offsets_host[:-1]).max())
+    with _on(dev):
+        rc = _L.ovis_coco_runs_to_words(runs.data_ptr(), run_offsets.data_ptr(), sizes.data_ptr(), word_offsets.data_ptr(), p,
+                                        max_words, run_ends.data_ptr(), words.data_ptr() if words.numel() else 0,
+                                        areas.data_ptr(), status.data_ptr(), _stream())
+    _lib.check(rc, "coco_rle_words")
+    return words, word_offsets, areas, status

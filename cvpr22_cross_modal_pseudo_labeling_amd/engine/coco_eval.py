@@ -18,6 +18,12 @@ a quarter of the memory free at the start is used, or ``MAX_CHUNK_IMAGES``, or u
 its polygons would exceed ``MAX_CALL_MASKS`` -- the most one ``paste_masks`` / ``polygons_to_masks`` call takes, so the
 per-size calls of a chunk stay inside their callees' limits even when every image has the same size.
 
+Detections also come from COCO RESULTS FILES (``evaluate_coco_results``: the ``bbox.json`` / ``segm.json`` of
+engine/coco_results.py, of the reference or of any other tool): ``load_coco_results`` is pycocotools' ``loadRes`` plus the
+per-category cap, and a ``segm`` row carries its RLE instead of a map and a box.  RLE masks -- those detections and RLE
+ground truth alike -- never become byte masks: ``_C.coco_rle_words`` (csrc/coco_rle_decode.hip) decodes all of an image-size
+group in one call straight to the packed words, and reports a malformed encoding as a status that is raised here.
+
 Semantics beyond pycocotools' own: images and categories are all those of the annotation file, sorted by id; an image
 without a prediction counts with zero detections; every annotation is ground truth, crowds included (``ignore =
 iscrowd``); a ground truth's ``area`` is the annotation's ``area`` when present, else its box's w * h; an IoU whose union
@@ -25,6 +31,8 @@ is 0 is 0 (pycocotools yields NaN for two zero-area boxes; clipped detections ha
 and ``box_proposal`` recall are not computed.
 """
 import contextlib
+import json
+import os
 from collections import OrderedDict
 
 import numpy as np
@@ -130,7 +138,8 @@ def format_results(results):
 # ---- host: ground truth and detections as rows ----------------------------------------------------------------------------
 def rle_decode(rle, height, width):
     """uint8 [height, width] of a COCO RLE ``{"counts", "size"}``: column-major runs, zeros first; ``counts`` an
-    uncompressed list or pycocotools' compressed string (``rleFrString``)."""
+    uncompressed list or pycocotools' compressed string (``rleFrString``).  The host statement of the format: scoring
+    itself decodes on the device (``_C.coco_rle_words``), the tests hold that decoder and the export's strings to this."""
     counts = rle["counts"]
     if list(rle.get("size", [height, width])) != [height, width]:
         raise ValueError(f"RLE of size {rle.get('size')} on an image of {height} x {width}")
@@ -222,6 +231,69 @@ def _detections(pred, image, label_to_cat, with_masks):
     return out
 
 
+def load_coco_results(dataset, results, iou_type):
+    """The detections of a COCO results file as per-image rows, for the images of ``_ground_truth(dataset)`` in its order
+    (pycocotools' ``loadRes`` and the ``dt[0:maxDets[-1]]`` of COCOeval): ``results`` is a path or the parsed list of
+    {"image_id", "category_id", "score", "bbox" (xywh) or "segmentation" ({"size": [h, w], "counts": str or list})}.  Rows
+    are what ``_detections`` makes: sorted by (category index, descending score), stably in file order, at most 100 per
+    category and image.  bbox: ``xywh`` as written (the area is w * h).  segm: ``rle`` holds the rows' segmentation dicts in
+    place of ``maps`` / ``xyxy`` (the area comes from the decoder); ``entry`` is every row's index in the file.  Entries of
+    a category the annotation file does not have are dropped (COCOeval never evaluates them).  ValueError, naming the
+    entry: an image_id the file does not have, a polygon segmentation, a ``size`` that is not the image's, a missing key."""
+    if iou_type not in ("bbox", "segm"):
+        raise ValueError(f"load_coco_results: iou_type '{iou_type}' is not supported (bbox, segm)")
+    if isinstance(results, (str, bytes, os.PathLike)):
+        with open(results) as f:
+            results = json.load(f)
+    if not isinstance(results, (list, tuple)):
+        raise ValueError(f"load_coco_results: a results file is a JSON list of detections, got {type(results).__name__}")
+    coco = dataset.coco
+    cat_index = {c: i for i, c in enumerate(coco.cat_ids())}
+    field = "bbox" if iou_type == "bbox" else "segmentation"
+    per_image = {}
+    for index, entry in enumerate(results):
+        where = f"load_coco_results: entry {index}"
+        if not isinstance(entry, dict) or "image_id" not in entry:
+            raise ValueError(f"{where} has no 'image_id'")
+        where += f" (image_id {entry['image_id']})"
+        if entry["image_id"] not in coco.imgs:
+            raise ValueError(f"{where}: the annotation file has no such image")
+        for key in ("category_id", "score", field):
+            if key not in entry:
+                raise ValueError(f"{where} has no '{key}'")
+        if entry["category_id"] not in cat_index:
+            continue
+        if iou_type == "bbox":
+            if len(entry["bbox"]) != 4:
+                raise ValueError(f"{where}: 'bbox' is not [x, y, w, h]")
+        else:
+            seg, info = entry["segmentation"], coco.imgs[entry["image_id"]]
+            if isinstance(seg, (list, tuple)):
+                raise ValueError(f"{where}: polygon segmentations in results are not supported (RLE only)")
+            if not isinstance(seg, dict) or "counts" not in seg or "size" not in seg:
+                raise ValueError(f"{where}: 'segmentation' is not an RLE {{'size', 'counts'}}")
+            if list(seg["size"]) != [int(info["height"]), int(info["width"])]:
+                raise ValueError(f"{where}: RLE of size {seg['size']} on an image of {info['height']} x {info['width']}")
+        per_image.setdefault(entry["image_id"], []).append(index)
+    rows = []
+    for img_id in sorted(coco.imgs):
+        members = per_image.get(img_id, [])
+        scores = np.asarray([results[k]["score"] for k in members], dtype=np.float64)
+        cats = np.asarray([cat_index[results[k]["category_id"]] for k in members], dtype=np.int64)
+        order = np.lexsort((-scores, cats))  # stable: ties keep file order
+        rank = np.arange(len(order)) - np.searchsorted(cats[order], cats[order], side="left")
+        order = order[rank < MAX_DETS[-1]]
+        members = [members[k] for k in order]
+        row = {"cats": cats[order], "scores": scores[order], "xywh": np.zeros((len(members), 4)), "xyxy": None, "maps": None,
+               "entry": np.asarray(members, dtype=np.int64)}
+        if iou_type == "bbox":
+            row["xywh"] = np.asarray([results[k]["bbox"] for k in members], dtype=np.float64).reshape(-1, 4)
+        else:
+            row["rle"] = [results[k]["segmentation"] for k in members]
+        rows.append(row)
+    return rows
+
+
 def _chunks(images, dets, with_masks, budget, max_images=None):
     """Lists of consecutive image indices: a chunk closes before the image that would take it over ``budget`` bytes of
     masks, over ``max_images`` (None: MAX_CHUNK_IMAGES) or -- for segm -- over MAX_CALL_MASKS detections, ground truths or
@@ -255,9 +327,25 @@ def _stage(timer, name):
     timer.setdefault(name, []).append((start, end))
 
 
-def _pack_group(group_rows, masks, words_parts, areas_out, base):
-    """Packs one image-size group's masks; -> the word offset behind it."""
+def _decode_rle(segmentations, names, height, width, device):
+    """(words int64 [n, ceil(height * width / 64)], areas int64 [n]) of n COCO RLEs of one image size, decoded on the device
+    in one ``_C.coco_rle_words`` call.  ``names[k]`` says what mask k is, for the ValueError a malformed one raises."""
+    sizes = torch.tensor([[height, width]], dtype=torch.int32).expand(len(segmentations), 2).contiguous().to(device)
+    words, _, areas, status = _C.coco_rle_words([s["counts"] for s in segmentations], sizes)
+    status = status.cpu().numpy()
+    if status.any():
+        k = int(np.flatnonzero(status)[0])
+        raise ValueError(f"{names[k]}: malformed RLE for an image of {height} x {width}: "
+                         f"{_C.COCO_RLE_STATUS.get(int(status[k]), int(status[k]))}")
+    return words.view(len(segmentations), -1), areas
+
+
+def _pack_group(group_rows, masks, words_parts, areas_out, base, rle=None):
+    """Packs one image-size group's masks; -> the word offset behind it.  ``rle``: (rows of ``masks``, their words, their
+    areas) of the group's RLE masks, which take the place of what those (empty) rows of ``masks`` pack to."""
     words, areas = _C.coco_pack_masks(masks)
+    if rle is not None:
+        words[rle[0]], areas[rle[0]] = rle[1], rle[2]
     words_parts.append(words.reshape(-1))
     areas_out[group_rows] = areas
     return base + words.numel()
@@ -265,7 +353,9 @@ def _pack_group(group_rows, masks, words_parts, areas_out, base):
 
 def score_chunk(images, dets, iou_type, device, timer=None):
     """The match tables of one chunk of images (the NumPy form ``accumulate`` takes): a constant number of launches --
-    box or mask IoU and the matching -- plus, for segm, the paste, rasterise and pack calls of every image size."""
+    box or mask IoU and the matching -- plus, for segm, the paste, rasterise and pack calls of every image size; detections
+    that carry ``rle`` (``load_coco_results``) and RLE ground truth take one ``_C.coco_rle_words`` call per image size
+    instead -- a malformed encoding raises a ValueError that names the entry or the annotation."""
     with_masks = iou_type == "segm"
     rows, det_base, gt_base, iou_off = [], 0, 0, 0
     det_image_base, gt_image_base = [], []
@@ -308,7 +398,15 @@ def score_chunk(images, dets, iou_type, device, timer=None):
                 image_words[i] = (d_off, g_off, nwords)
                 d_off += len(dets[i]["cats"]) * nwords
                 g_off += len(images[i]["cats"]) * nwords
-            if len(det_rows):
+            with_dets = [i for i in members if len(dets[i]["cats"])]
+            if len(det_rows) and dets[with_dets[0]].get("rle") is not None:  # a results file: straight to the words
+                names = [f"results entry {k} (image_id {images[i]['id']})" for i in with_dets for k in dets[i]["entry"]]
+                with _stage(timer, "decode"):
+                    words, areas = _decode_rle([s for i in with_dets for s in dets[i]["rle"]], names, height, width, device)
+                det_words.append(words.reshape(-1))
+                det_areas_i[torch.from_numpy(det_rows).to(device)] = areas
+                det_word_base += words.numel()
+            elif len(det_rows):
                 maps = torch.cat([dets[i]["maps"] for i in members if len(dets[i]["cats"])]).to(device)
                 boxes = torch.cat([dets[i]["xyxy"] for i in members if len(dets[i]["cats"])]).to(device)
                 with _stage(timer, "paste"):
@@ -327,12 +425,19 @@ def score_chunk(images, dets, iou_type, device, timer=None):
                 with _stage(timer, "rasterise"):
                     masks = polygons.convert_to_binarymask()
                 rle_rows = [r for r, a in enumerate(anns) if isinstance(a["segmentation"], dict)]
-                if rle_rows:  # decoded on the host and uploaded
-                    decoded = np.stack([rle_decode(anns[r]["segmentation"], height, width) for r in rle_rows])
-                    masks[torch.tensor(rle_rows, device=device)] = torch.from_numpy(decoded).to(device)
+                rle = None
+                if rle_rows:  # decoded on the device to the words their (empty) rows of `masks` give way to
+                    for r in rle_rows:
+                        seg = anns[r]["segmentation"]
+                        if list(seg.get("size", [height, width])) != [height, width]:
+                            raise ValueError(f"RLE of size {seg.get('size')} on an image of {height} x {width}")
+                    with _stage(timer, "decode"):
+                        rle = (torch.tensor(rle_rows, device=device),) + _decode_rle(
+                            [anns[r]["segmentation"] for r in rle_rows], [f"annotation {anns[r].get('id')}" for r in rle_rows],
+                            height, width, device)
                 with _stage(timer, "pack"):
                     gt_word_base = _pack_group(torch.from_numpy(gt_rows).to(device), masks, gt_words, gt_areas_i,
-                                               gt_word_base)
+                                               gt_word_base, rle)
                 del masks
         if len(table):  # the word columns of every problem, from its image's share of the word buffers
             img = table[:, 9]
@@ -390,24 +495,36 @@ def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None
     by_image = {dataset.id_to_img_map[idx]: pred for idx, pred in enumerate(predictions)}
     with_masks = iou_type == "segm"
     dets = [_detections(by_image.get(image["id"]), image, label_to_cat, with_masks) for image in images]
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images), cat_ids
+
+
+def _score_rows(images, dets, iou_type, device, budget, timer, max_images):
+    """The match tables of the images' ground truth and detection rows, chunk by chunk."""
     if budget is None:
         budget = torch.cuda.mem_get_info(device)[0] // 4
     parts = [score_chunk([images[i] for i in chunk], [dets[i] for i in chunk], iou_type, device, timer)
-             for chunk in _chunks(images, dets, with_masks, budget, max_images)]
-    return concatenate_tables(parts), cat_ids
+             for chunk in _chunks(images, dets, iou_type == "segm", budget, max_images)]
+    return concatenate_tables(parts)
 
 
-def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda"):
-    """{iou_type: OrderedDict of AP, AP50, AP75, APs, APm, APl, AP50_class_<name> per category (in the order of
-    ``dataset.categories``, as ``COCOResults.update`` iterates) and AP50_split_<split> per key of ``dataset.class_splits``}
-    for ``predictions``: the list ``inference()`` returns or ``torch.load`` gives from ``predictions.pth`` (BoxLists in
-    dataset-index order, fields ``scores``, ``labels`` and -- for segm -- ``mask`` [K, 1, M, M]).  ``device``: the HIP
-    device that scores; there is no host-only scoring."""
+def results_match_tables(dataset, results, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None):
+    """``match_tables`` for the detections of a results file (``results``: what ``load_coco_results`` takes)."""
+    device = torch.device(device)
+    cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset)
+    dets = load_coco_results(dataset, results, iou_type)
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images), cat_ids
+
+
+def _scoring_device(device, who):
     device = torch.device(device)
     if device.type != "cuda":
-        raise ValueError("evaluate_coco: scoring runs on the HIP device (IoU and matching have no host implementation)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+        raise ValueError(f"{who}: scoring runs on the HIP device (IoU and matching have no host implementation)")
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def _summaries(dataset, iou_types, device, tables_of):
+    """{iou_type: ``summarize`` of ``accumulate`` of ``tables_of(iou_type, ground truth)``} with the dataset's names,
+    splits and class order."""
     results = OrderedDict()
     ground_truth = _ground_truth(dataset)
     cat_ids = ground_truth[0]
@@ -416,7 +533,43 @@ def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda
     class_order = [cat_index[c] for c in dataset.categories if c in cat_index]
     with torch.cuda.device(device):
         for iou_type in iou_types:
-            tables, _ = match_tables(dataset, predictions, iou_type, device, ground_truth=ground_truth)
+            tables, _ = tables_of(iou_type, ground_truth)
             results[iou_type] = summarize(accumulate(tables, len(cat_ids)), [dataset.categories[c] for c in cat_ids], splits,
                                           class_order)
     return results
+
+
+def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda"):
+    """{iou_type: OrderedDict of AP, AP50, AP75, APs, APm, APl, AP50_class_<name> per category (in the order of
+    ``dataset.categories``, as ``COCOResults.update`` iterates) and AP50_split_<split> per key of ``dataset.class_splits``}
+    for ``predictions``: the list ``inference()`` returns or ``torch.load`` gives from ``predictions.pth`` (BoxLists in
+    dataset-index order, fields ``scores``, ``labels`` and -- for segm -- ``mask`` [K, 1, M, M]).  ``device``: the HIP
+    device that scores; there is no host-only scoring."""
+    device = _scoring_device(device, "evaluate_coco")
+    return _summaries(dataset, iou_types, device,
+                      lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt))
+
+
+def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="cuda"):
+    """``evaluate_coco``'s numbers, in the same structure, for detections that come from COCO results files: ``results`` is
+    {iou_type: a path or the parsed list} (``load_coco_results``); an iou_type it does not have is skipped.  Whatever wrote
+    the files -- ``export_coco_results``, the reference, another tool -- nothing but the annotation file is needed beside
+    them.  ``device``: the HIP device that decodes the masks and scores; there is no host-only scoring."""
+    device = _scoring_device(device, "evaluate_coco_results")
+    for iou_type in results:
+        if iou_type not in ("bbox", "segm"):
+            raise ValueError(f"evaluate_coco_results: iou_type '{iou_type}' is not supported (bbox, segm)")
+    return _summaries(dataset, [t for t in iou_types if t in results], device,
+                      lambda iou_type, gt: results_match_tables(dataset, results[iou_type], iou_type, device, ground_truth=gt))
+
+
+def annotation_dataset(ann_file):
+    """The dataset object scoring needs, from the annotation file alone: no images, no configuration.  The ``split`` keys
+    of its categories, when present, give the AP50_split_<split> rows."""
+    from ..data.datasets import COCODataset
+
+    dataset = COCODataset(ann_file, "", False)
+    for item in dataset.coco.dataset["categories"]:
+        if "split" in item:
+            dataset.class_splits.setdefault(item["split"], []).append(item["id"])
+    return dataset

@@ -881,6 +881,48 @@ int ovis_coco_match(const double* iou, const int64_t* problems, int num_problems
                     const double* thresholds, int num_thresholds, long num_dets, long num_gts, int32_t* dt_match,
                     uint8_t* dt_ignore, uint8_t* gt_ignore, void* stream);
 
+/* ovis_coco_rle_* / ovis_coco_runs_to_words (csrc/coco_rle_decode.hip): COCO run-length encodings -- the `segmentation` of a
+ * results file (what mb/data/datasets/evaluation/coco/coco_eval.py:139-144 writes and COCOeval reads back through
+ * pycocotools' rleFrString / rleDecode) or of an RLE annotation -- as the bit words of ovis_coco_pack_masks_u64, for `num`
+ * masks of any sizes in one call.  The inverse of ovis_pasted_rle_*; the caller makes the exclusive sums between the stages
+ * in the same way.  RLE: column-major runs, zeros first; compressed, value i >= 3 is stored as its difference to value
+ * i - 2, in 5-bit groups (low group first, bit 0x20 = "more", the last group's bit 0x10 = the sign), each group + 48.
+ *   _count:  chars = all strings of the call concatenated (uint8), char_offsets [num + 1] int64 -> num_runs[p] int32 = the
+ *            number of values of string p: its characters c with ((c - 48) & 0x20) == 0.  It only counts.
+ *   _runs:   run_offsets [num + 1] int64 with run_offsets[p + 1] - run_offsets[p] >= num_runs[p] -> the decoded values of
+ *            string p, differences undone, at runs[run_offsets[p] ..), int32, and status[p] for EVERY p: OVIS_COCO_RLE_OK or
+ *            the first of BAD_CHAR (a character outside '0'..'o', 48..111), UNTERMINATED (the last character has the "more"
+ *            bit), OVERFLOW (a value of more than 7 characters, or one that does not fit int32 after the sign extension or
+ *            after the difference sum).  A string without characters (an uncompressed mask of a mixed call) writes no run
+ *            and gets OVIS_COCO_RLE_OK.
+ *   ovis_coco_runs_to_words: runs / run_offsets as above -- uncompressed `counts` lists enter here, with status[p] = 0 --
+ *            sizes int32 [num, 2] = (height, width), word_offsets [num + 1] int64 (mask p owns ceil(height * width / 64)
+ *            words; max_words = the largest such slice, it sizes the grid), run_ends int32 [run_offsets[num]] = scratch (the
+ *            inclusive sums of the runs).  status[p] is read and written: a non-zero entry stays; otherwise the first of
+ *            BAD_SIZE (height < 1, width < 1 or height * width > 0x7fffffef, the encoder's bound), NEGATIVE_RUN, BAD_SUM
+ *            (the runs do not add up to height * width), else OK.  words: pixel p = y * width + x of mask m = bit p % 64
+ *            of word p / 64 of its slice, the tail of the last word zero -- ovis_coco_pack_masks_u64's layout, so slices
+ *            of both can be concatenated; areas[m] int64 = the sum of the odd-indexed runs.  A mask with non-zero status
+ *            gets all-zero words and area 0.  Every word of every slice and every areas / status entry is written.
+ * ADDRESSING: every load and store is bounded by char_offsets, run_offsets and word_offsets alone; no decoded value (a
+ * character, a run, a sum, a size) is ever an index, a loop bound or a pointer offset.  Arbitrary bytes in chars or runs
+ * cannot make a kernel touch memory outside the call's slices -- they only set status.  The offsets themselves are the
+ * caller's and are trusted (non-decreasing, inside the buffers).
+ * Enqueue only, no atomics, deterministic.  num == 0: OVIS_OK without a launch.  num <= 65535, else OVIS_ERANGE. */
+#define OVIS_COCO_RLE_OK 0
+#define OVIS_COCO_RLE_BAD_CHAR 1
+#define OVIS_COCO_RLE_UNTERMINATED 2
+#define OVIS_COCO_RLE_OVERFLOW 3
+#define OVIS_COCO_RLE_NEGATIVE_RUN 4
+#define OVIS_COCO_RLE_BAD_SUM 5
+#define OVIS_COCO_RLE_BAD_SIZE 6
+int ovis_coco_rle_count(const uint8_t* chars, const int64_t* char_offsets, int num, int32_t* num_runs, void* stream);
+int ovis_coco_rle_runs(const uint8_t* chars, const int64_t* char_offsets, const int64_t* run_offsets, int num,
+                       int32_t* runs, int32_t* status, void* stream);
+int ovis_coco_runs_to_words(const int32_t* runs, const int64_t* run_offsets, const int32_t* sizes,
+                            const int64_t* word_offsets, int num, long max_words, int32_t* run_ends, uint64_t* words,
+                            int64_t* areas, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,67 @@
+"""Score COCO results files against an annotation file on the device: COCO box / mask AP and the per-class / per-split AP50
+of ``bbox.json`` / ``segm.json`` -- the files ``tools/infer_net.py --export-results`` writes, or those of the reference
+(maskrcnn_benchmark/data/datasets/evaluation/coco/coco_eval.py: ``do_coco_evaluation`` :40-61), or of any other tool --
+without a model, a configuration or the images (engine/coco_eval.py: ``evaluate_coco_results``).  The RLE masks of
+``segm.json`` are decoded on the device straight to the scorer's bit words (csrc/coco_rle_decode.hip).
+
+  python tools/score_results.py --ann-file instances_val.json --results-dir OUTPUT_DIR/inference/<name>
+  python tools/score_results.py --ann-file instances_val.json --segm segm.json --output scores.json
+
+Prints the ``Task: ... / names / values`` table ``--evaluate`` logs; ``--output`` writes the numbers as
+``coco_results.json`` has them.  There is no host-only scoring: the device must be a HIP device.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+IOU_TYPES = ("bbox", "segm")
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="Score COCO results files (bbox.json / segm.json) on the device")
+    parser.add_argument("--ann-file", required=True, metavar="FILE", help="the COCO annotation file the results belong to")
+    parser.add_argument("--bbox", default=None, metavar="PATH", help="a bbox results file")
+    parser.add_argument("--segm", default=None, metavar="PATH", help="a segm results file (RLE masks)")
+    parser.add_argument("--results-dir", default=None, metavar="DIR", help="DIR/bbox.json and DIR/segm.json, whichever exist")
+    parser.add_argument("--output", default=None, metavar="PATH", help="write {iou_type: {metric: value}} as JSON")
+    parser.add_argument("--device", default="cuda", help="the HIP device that scores (cuda, cuda:1, ...)")
+    args = parser.parse_args(argv)
+    files = {}
+    for iou_type in IOU_TYPES:
+        path = getattr(args, iou_type)
+        if path is None and args.results_dir and os.path.exists(os.path.join(args.results_dir, iou_type + ".json")):
+            path = os.path.join(args.results_dir, iou_type + ".json")
+        if path is not None:
+            files[iou_type] = path
+    if not files:
+        parser.error("no results file: give --bbox, --segm or a --results-dir that holds bbox.json or segm.json")
+    for path in [args.ann_file] + list(files.values()):
+        if not os.path.exists(path):
+            parser.error(f"{path} does not exist")
+    try:
+        device = torch.device(args.device)
+    except RuntimeError:
+        parser.error(f"--device {args.device} is not a device")
+    if device.type != "cuda" or not torch.cuda.is_available():
+        parser.error("results are scored on the HIP device (mask decoding, IoU and matching have no host implementation): "
+                     "--device cuda on a machine that has one")
+
+    from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval
+
+    dataset = coco_eval.annotation_dataset(args.ann_file)
+    results = coco_eval.evaluate_coco_results(dataset, files, IOU_TYPES, device)
+    print(coco_eval.format_results(results))
+    if args.output:
+        with open(args.output, "w") as f:
+            json.dump(results, f, indent=1)
+    return results
+
+
+if __name__ == "__main__":
+    main()
