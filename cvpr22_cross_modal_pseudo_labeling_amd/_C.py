@@ -2004,18 +2004,85 @@ def coco_rle_words(strings_or_runs, sizes):
     else:
         runs = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
     if compressed:
-        with _on(dev):
-            rc = _L.ovis_coco_rle_runs(chars.data_ptr(), char_offsets.data_ptr(), run_offsets.data_ptr(), p, runs.data_ptr(),
-                                       status.data_ptr(), _stream())
-        _lib.check(rc, "coco_rle_words")
+        _coco_rle_runs(chars, char_offsets, run_offsets, p, runs, status)
         if lists:  # the uncompressed items of a mixed call, into their slices
             slots = torch.cat([torch.arange(len(v)) + run_offsets_host[k] for k, v in lists.items()])
             runs[slots.to(dev)] = torch.cat(list(lists.values())).to(dev)
-    run_ends = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
     max_words = int((word_offsets_host[1:] - word_offsets_host[:-1]).max())
-    with _on(dev):
+    _coco_runs_to_words(runs, run_offsets, total, sizes, word_offsets, p, max_words, words, areas, status)
+    return words, word_offsets, areas, status
+
+
+def _coco_rle_runs(chars, char_offsets, run_offsets, p, runs, status):
+    with _on(runs.device):
+        rc = _L.ovis_coco_rle_runs(chars.data_ptr(), char_offsets.data_ptr(), run_offsets.data_ptr(), p, runs.data_ptr(),
+                                   status.data_ptr(), _stream())
+    _lib.check(rc, "coco_rle_words")
+
+
+def _coco_runs_to_words(runs, run_offsets, total_runs, sizes, word_offsets, p, max_words, words, areas, status):
+    run_ends = torch.empty(max(total_runs, 1), dtype=torch.int32, device=runs.device)
+    with _on(runs.device):
         rc = _L.ovis_coco_runs_to_words(runs.data_ptr(), run_offsets.data_ptr(), sizes.data_ptr(), word_offsets.data_ptr(), p,
                                         max_words, run_ends.data_ptr(), words.data_ptr() if words.numel() else 0,
                                         areas.data_ptr(), status.data_ptr(), _stream())
     _lib.check(rc, "coco_rle_words")
-    return words, word_offsets, areas, status
+
+
+def coco_rle_words_staged(chars, char_offsets, runs, run_offsets, sizes, word_offsets, *, total_words, max_words,
+                          compressed=True):
+    """``coco_rle_words`` for inputs that are ALREADY on the device, with everything the host has to know handed in -- no
+    device-to-host copy, so it can run on a training stream (``RleMasks.decode_many``; the same ``ovis_coco_rle_runs`` /
+    ``ovis_coco_runs_to_words`` entry points; the value counts ``ovis_coco_rle_count`` would report come from the host, in
+    ``run_offsets``).  chars uint8 [C] + char_offsets int64 [P + 1]: the compressed strings back to back (an uncompressed
+    item has none); runs int32 [R] + run_offsets int64 [P + 1]: one slot per value of every item, an uncompressed item's
+    values in place (the strings' slots are overwritten: ``runs`` is modified); sizes int32 [P, 2] (height, width);
+    word_offsets int64 [P + 1] with mask p owning ceil(height * width / 64) words.  Host integers: ``total_words`` =
+    word_offsets[P], ``max_words`` = the largest slice; ``compressed``: whether any item is a string.
+    -> (words int64 [total_words], areas int64 [P], status int32 [P]) as ``coco_rle_words``."""
+    chars, runs, sizes = _dev(chars, "chars", torch.uint8), _dev(runs, "runs", torch.int32), _dev(sizes, "sizes", torch.int32)
+    char_offsets, run_offsets = _dev(char_offsets, "char_offsets", torch.int64), _dev(run_offsets, "run_offsets", torch.int64)
+    word_offsets = _dev(word_offsets, "word_offsets", torch.int64)
+    p, dev = sizes.shape[0], sizes.device
+    if sizes.dim() != 2 or sizes.shape[1] != 2 or any(t.shape != (p + 1,) for t in (char_offsets, run_offsets, word_offsets)):
+        raise RuntimeError(f"coco_rle_words_staged: expected sizes int32 [P,2] and three int64 [P + 1] offset tensors")
+    if p > 65535:
+        raise RuntimeError("coco_rle_words_staged: at most 65535 masks a call")
+    words = torch.empty(int(total_words), dtype=torch.int64, device=dev)
+    areas, status = torch.empty(p, dtype=torch.int64, device=dev), torch.zeros(p, dtype=torch.int32, device=dev)
+    if p == 0:
+        return words, areas, status
+    if not runs.numel():
+        runs = torch.empty(1, dtype=torch.int32, device=dev)
+    if compressed:
+        _coco_rle_runs(chars if chars.numel() else torch.empty(1, dtype=torch.uint8, device=dev), char_offsets, run_offsets, p,
+                       runs, status)
+    _coco_runs_to_words(runs, run_offsets, runs.numel(), sizes, word_offsets, p, int(max_words), words, areas, status)
+    return words, areas, status
+
+
+def project_rle_masks(rle_masks, gt_index, boxes, resolution):
+    """Mask targets [P, resolution, resolution] f32 for boxes [P, 4] whose ground truth gt_index[p] is an instance of
+    ``rle_masks`` (modeling/structures.py::RleMasks on the device): its recorded resize and flips, then crop + resize, from
+    the decoded bit words in one launch (``ovis_project_rle_masks_f32``).  P == 0: empty, no launch."""
+    boxes = _dev(boxes, "boxes")
+    gt_index = _dev(gt_index, "gt_index", torch.int64)
+    p = boxes.shape[0]
+    out = torch.empty((p, resolution, resolution), dtype=torch.float32, device=boxes.device)
+    if p == 0:
+        return out
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or gt_index.shape != (p,):
+        raise RuntimeError("project_rle_masks: expected boxes [P,4] and gt_index [P]")
+    m = rle_masks.decoded()
+    if m.words is None:
+        raise RuntimeError("project_rle_masks: positives but no ground-truth mask")
+    words, word_offsets = _dev(m.words, "words", torch.int64), _dev(m.word_offsets, "word_offsets", torch.int64)
+    instance = _dev(m.instance, "instance", torch.int64)
+    (h0, w0), (w1, h1) = m.source_hw, m.size
+    with _on(boxes.device):
+        rc = _L.ovis_project_rle_masks_f32(words.data_ptr(), word_offsets.data_ptr(), word_offsets.numel() - 1,
+                                           m.decoded_words_per_mask, instance.data_ptr() if instance.numel() else 0, instance.numel(),
+                                           gt_index.data_ptr(), boxes.data_ptr(), p, h0, w0, h1, w1, int(m.flip_h),
+                                           int(m.flip_v), int(resolution), out.data_ptr(), _stream())
+    _lib.check(rc, "project_rle_masks")
+    return out

@@ -21,6 +21,7 @@
 //                  resize to the integer box, > 0.5, paste) is evaluated on the fly, so the H x W canvases never exist.
 #include "ovis_common.h"
 #define OVIS_HD __device__ __forceinline__
+#include "mask_crop_geom.h"
 #include "pasted_geom.h"
 
 namespace {
@@ -160,22 +161,10 @@ __global__ __launch_bounds__(256) void project_masks_kernel(const unsigned char*
   const long total = (long)P * M * M;
   if (i >= total) return;
   const int dx = (int)(i % M), dy = (int)((i / M) % M), p = (int)(i / ((long)M * M));
-  const float4 bx = *(const float4*)(boxes + 4 * p);
-  const float b0 = rintf(bx.x), b1 = rintf(bx.y), b2 = rintf(bx.z), b3 = rintf(bx.w);  // python round(): half to even
-  const float xmin = fminf(fmaxf(b0, 0.f), (float)(W - 1)), ymin = fminf(fmaxf(b1, 0.f), (float)(H - 1));
-  const float xmax = fmaxf(fminf(fmaxf(b2, 0.f), (float)W), xmin + 1.f);
-  const float ymax = fmaxf(fminf(fmaxf(b3, 0.f), (float)H), ymin + 1.f);
-  const float w = xmax - xmin, h = ymax - ymin;
-  // scale = in / out as ONE correctly rounded division (area_pixel_compute_scale of F.interpolate; segmentation_mask.py:
-  // 150-155): a crop whose size is a multiple of M must give integer source positions -- zero weight on the second tap --
-  // which size * (1 / M) misses by an ulp (tests/test_step_golden.py: the reference's own step disagreed there)
-  const float sy = fmaxf(((float)dy + 0.5f) * (h / (float)M) - 0.5f, 0.f);
-  const float sx = fmaxf(((float)dx + 0.5f) * (w / (float)M) - 0.5f, 0.f);
-  float y0 = floorf(sy), x0 = floorf(sx);
-  const float ly = sy - y0, lx = sx - x0;
-  y0 = fminf(y0, h - 1.f);
-  x0 = fminf(x0, w - 1.f);
-  const float y1 = fminf(y0 + 1.f, h - 1.f), x1 = fminf(x0 + 1.f, w - 1.f);
+  // the crop window and the resize taps (mask_crop_geom.h)
+  const MaskCropWindow c = mask_crop_window(*(const float4*)(boxes + 4 * p), W, H);
+  const MaskAxisTap ty = mask_axis_tap(dy, c.h, (float)M), tx = mask_axis_tap(dx, c.w, (float)M);
+  const float xmin = c.xmin, ymin = c.ymin, y0 = ty.i0, y1 = ty.i1, ly = ty.lam, x0 = tx.i0, x1 = tx.i1, lx = tx.lam;
   const unsigned char* m = masks + (long)gt_index[p] * H * W;
   const long r0 = (long)(y0 + ymin) * W, r1 = (long)(y1 + ymin) * W;
   const long c0 = (long)(x0 + xmin), c1 = (long)(x1 + xmin);
@@ -447,20 +436,10 @@ __global__ __launch_bounds__(256) void project_pasted_masks_kernel(const float* 
   const long total = (long)P * M * M;
   if (i >= total) return;
   const int dx = (int)(i % M), dy = (int)((i / M) % M), p = (int)(i / ((long)M * M));
-  // the crop window and the resize taps: project_masks_kernel, expression by expression
-  const float4 bb = *(const float4*)(boxes + 4 * p);
-  const float b0 = rintf(bb.x), b1 = rintf(bb.y), b2 = rintf(bb.z), b3 = rintf(bb.w);
-  const float xmin = fminf(fmaxf(b0, 0.f), (float)(W - 1)), ymin = fminf(fmaxf(b1, 0.f), (float)(H - 1));
-  const float xmax = fmaxf(fminf(fmaxf(b2, 0.f), (float)W), xmin + 1.f);
-  const float ymax = fmaxf(fminf(fmaxf(b3, 0.f), (float)H), ymin + 1.f);
-  const float w = xmax - xmin, h = ymax - ymin;
-  const float sy = fmaxf(((float)dy + 0.5f) * (h / (float)M) - 0.5f, 0.f);
-  const float sx = fmaxf(((float)dx + 0.5f) * (w / (float)M) - 0.5f, 0.f);
-  float y0 = floorf(sy), x0 = floorf(sx);
-  const float ly = sy - y0, lx = sx - x0;
-  y0 = fminf(y0, h - 1.f);
-  x0 = fminf(x0, w - 1.f);
-  const float y1 = fminf(y0 + 1.f, h - 1.f), x1 = fminf(x0 + 1.f, w - 1.f);
+  // the crop window and the resize taps: project_masks_kernel's (mask_crop_geom.h)
+  const MaskCropWindow c = mask_crop_window(*(const float4*)(boxes + 4 * p), W, H);
+  const MaskAxisTap ty = mask_axis_tap(dy, c.h, (float)M), tx = mask_axis_tap(dx, c.w, (float)M);
+  const float xmin = c.xmin, ymin = c.ymin, y0 = ty.i0, y1 = ty.i1, ly = ty.lam, x0 = tx.i0, x1 = tx.i1, lx = tx.lam;
   // the ground truth's pasted mask: integer box of the expanded pseudo box (Masker: scale (M+2)/M, truncation)
   const long g = gt_index[p];
   const float4 gb = *(const float4*)(gt_boxes + 4 * g);

@@ -2,9 +2,11 @@
 ``COCOCapDetDataset`` (datasets/coco_cap_det.py:55-188) over the pycocotools-free index of data/coco_json.py.
 
 An item is what ``data.synthetic.make_raw_batch`` fakes: ``(image uint8 [h, w, 3] RGB numpy array, BoxList, idx)`` with
-POLYGON ground truth (``PolygonMasks``).  No transform runs here: the loader's collate function applies the host half of
-data/transforms.py to the whole batch (data/build.py) and the device half makes the pixels.  Keypoints and RLE ground truth
-are not supported (the reference's poly mode cannot hold RLE either): an RLE segmentation raises, naming the image.
+polygon ground truth (``PolygonMasks``) or, for an image whose non-crowd annotations are all RLE (compressed or not),
+bitmap ground truth (``RleMasks``: packed here, decoded on the device).  No transform runs here: the loader's collate
+function applies the host half of data/transforms.py to the whole batch (data/build.py) and the device half makes the
+pixels and decodes the RLE masks.  Polygons and RLE mixed within one image, an RLE of another size than its image and
+keypoints are not supported: they raise, naming the image and the annotation.
 """
 import os
 
@@ -13,7 +15,7 @@ import torch
 from PIL import Image
 
 from ..modeling.language_backbone import normalize_class_names
-from ..modeling.structures import BoxList, PolygonMasks
+from ..modeling.structures import BoxList, PolygonMasks, RleMasks
 from .caption_parser import CaptionParser
 from .coco_json import COCOIndex
 
@@ -82,11 +84,20 @@ class COCODataset(torch.utils.data.Dataset):
 
     def _add_masks(self, target, anno, img_id):
         if anno and "segmentation" in anno[0]:
-            for obj in anno:
-                if isinstance(obj["segmentation"], dict):
-                    raise ValueError(f"image {img_id}: annotation {obj.get('id')} has an RLE segmentation; only polygon "
-                                     "ground truth is supported (mark it iscrowd or convert it to polygons)")
-            target.add_field("masks", PolygonMasks([obj["segmentation"] for obj in anno], target.size))
+            rle = [isinstance(obj["segmentation"], dict) for obj in anno]
+            if not any(rle):
+                target.add_field("masks", PolygonMasks([obj["segmentation"] for obj in anno], target.size))
+                return
+            width, height = target.size
+            for obj, is_rle in zip(anno, rle):
+                if not is_rle:
+                    raise ValueError(f"image {img_id}: annotation {obj.get('id')} has polygons beside the RLE segmentations "
+                                     "of the image's other annotations; one kind per image is supported")
+                if [int(v) for v in obj["segmentation"].get("size", ())] != [height, width]:
+                    raise ValueError(f"image {img_id}: annotation {obj.get('id')} has an RLE segmentation of size "
+                                     f"{obj['segmentation'].get('size')}, the image is [{height}, {width}] (height, width)")
+            target.add_field("masks", RleMasks([obj["segmentation"]["counts"] for obj in anno], (height, width), image_id=img_id,
+                                               ann_ids=[obj.get("id") for obj in anno]))
 
     def __getitem__(self, idx):
         img_id, img, anno, target = self._load(idx)

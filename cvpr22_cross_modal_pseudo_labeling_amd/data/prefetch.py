@@ -27,6 +27,8 @@ def _map(obj, fn):
         return out
     if hasattr(obj, "polygon_start") and hasattr(obj, "instance_start"):  # PolygonMasks
         return type(obj)(None, obj.size, (fn(obj.coords), fn(obj.polygon_start), fn(obj.instance_start)))
+    if hasattr(obj, "map_tensors"):  # RleMasks
+        return obj.map_tensors(fn)
     return obj
 
 
@@ -45,8 +47,8 @@ def copy_stream(device):
 
 
 class DevicePrefetcher:
-    """Iterates ``source`` (host batches: tensors / BoxLists / PolygonMasks / nested lists, tuples, dicts of them; a
-    ``PolygonMasks`` field is staged and rebuilt on the device like a BoxList, whether or not ``transform`` is given) ``depth`` batches
+    """Iterates ``source`` (host batches: tensors / BoxLists / PolygonMasks / RleMasks / nested lists, tuples, dicts of them; a
+    ``PolygonMasks`` or ``RleMasks`` field is staged and rebuilt on the device like a BoxList, whether or not ``transform`` is given) ``depth`` batches
     ahead on a worker thread and yields the same structures on ``device``.  On a CPU device it is a plain look-ahead
     queue.  Exceptions of the source are re-raised in the consumer.  ``transform`` (optional) is applied to every staged
     batch in the CONSUMER's thread, on its current stream, once that stream waits for the batch's copies -- the device half
@@ -134,6 +136,8 @@ class DevicePrefetcher:
         item, ev = self.q.get()
         if item is self._END:
             self.q.put((self._END, None))
+            if hasattr(self.transform, "flush"):  # what the transform still has to report about its last batch
+                self.transform.flush()
             raise StopIteration
         if isinstance(item, BaseException):
             raise item

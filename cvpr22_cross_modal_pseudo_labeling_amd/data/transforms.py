@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import _C
-from ..modeling.structures import ImageList
+from ..modeling.structures import ImageList, RleMasks, raise_on_bad_rle
 
 FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM = 0, 1
 
@@ -52,6 +52,7 @@ class InputTransform:
         self.mean, self.std = [float(v) for v in mean], [float(v) for v in std]
         self.to_bgr255, self.size_divisible = bool(to_bgr255), int(size_divisible)
         self.rng = random.Random(seed)
+        self._pending_rle = None  # (status in pinned host memory, the event of its copy, names) of the last decoded batch
 
     # -- host half ----------------------------------------------------------------------------------------------------
     def host(self, images, targets=None, rng=None):
@@ -99,7 +100,37 @@ class InputTransform:
                                       raw["max_in_hw"])
         return ImageList(tensors, [tuple(s) for s in raw["image_sizes"]])
 
+    def decode_masks(self, targets):
+        """The RLE ground truth of a staged batch (``RleMasks`` fields of its BoxLists) as bit words, ONE decode call for
+        the batch on the current stream, sizes and value counts from the host: nothing is read back.  A malformed
+        encoding decodes to an all-zero mask; its status goes to pinned host memory without blocking and is examined when
+        the NEXT batch comes through here (``flush``: and when the iterator ends) -- a ValueError naming the image and the
+        annotation, at most one step late and without a synchronisation on the training stream."""
+        self.flush()
+        masks = []
+        for t in targets or ():
+            for v in (t.extra_fields.values() if hasattr(t, "extra_fields") else ()):
+                if isinstance(v, RleMasks) and v.chars.is_cuda:
+                    masks.append(v)
+        status, names = RleMasks.decode_many(masks)
+        if status is not None:
+            host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
+            host.copy_(status, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(status.device))
+            self._pending_rle = (host, done, names, status)
+
+    def flush(self):
+        """Examine the decode status of the last batch (its copy was enqueued a step ago)."""
+        pending, self._pending_rle = self._pending_rle, None
+        if pending is not None:
+            host, done, names, _ = pending
+            done.synchronize()
+            raise_on_bad_rle(host, names)
+
     def __call__(self, batch):
+        if len(batch) > 1:
+            self.decode_masks(batch[1])
         return (self.device(batch[0]),) + tuple(batch[1:])
 
 

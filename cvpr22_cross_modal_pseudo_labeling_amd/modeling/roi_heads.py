@@ -31,7 +31,7 @@ from ..layers.derived import derived
 from .backbone import HeadFeatures, ResNetHead
 from .box_coder import BoxCoder
 from .matcher import BalancedPositiveNegativeSampler, Matcher
-from .structures import BoxList, PastedMasks, PolygonMasks, SampledBoxList, box_iou, boxlist_nms, cat_boxlist
+from .structures import BoxList, PastedMasks, PolygonMasks, RleMasks, SampledBoxList, box_iou, boxlist_nms, cat_boxlist
 
 
 def _cat(tensors, dim=0):
@@ -676,7 +676,7 @@ class MaskRCNNLossComputation:
                 continue
             if isinstance(gt_masks, PastedMasks):
                 gt_masks = gt_masks.materialize()
-            poly = isinstance(gt_masks, PolygonMasks)
+            poly = isinstance(gt_masks, (PolygonMasks, RleMasks))  # lazy forms: projected per positive, one launch
             fused = (prop.bbox.is_cuda and not self.matcher.allow_low_quality_matches
                      and (poly or (gt_masks.dim() == 3 and gt_masks.dtype in (torch.bool, torch.uint8))))
             if fused:
@@ -688,7 +688,8 @@ class MaskRCNNLossComputation:
                 lab = tgt.get_field("labels")[idx].to(torch.int64)
                 lab[matched == Matcher.BELOW_LOW_THRESHOLD] = 0
             pos = torch.nonzero(lab > 0).squeeze(1)
-            if poly:   # crop + resize + rasterise every positive's polygons in one launch (csrc/polygons.hip)
+            if poly:   # crop + resize + rasterise every positive's polygons (csrc/polygons.hip) / test its RLE ground
+                # truth's bits (csrc/rle_targets.hip) in one launch
                 masks.append(self._project(gt_masks, idx[pos], prop.bbox[pos]))
             elif fused:  # crop + bilinear resize of every positive's mask in one launch (csrc/targets.hip)
                 masks.append(_C.project_masks(gt_masks, idx[pos], prop.bbox[pos], self.discretization_size))
@@ -707,6 +708,13 @@ class MaskRCNNLossComputation:
                 gt_masks = gt_masks.to(boxes.device)
             return _C.project_polygon_masks(gt_masks.coords, gt_masks.polygon_start, gt_masks.instance_start, gt_index, boxes,
                                             gt_masks.size, m)
+        if isinstance(gt_masks, RleMasks):  # bitmap ground truth (SegmentationMask mode 'mask'), from the decoded bit words
+            if not boxes.is_cuda:
+                raise NotImplementedError("RLE ground-truth masks under MODEL.DEVICE cpu are not supported: the decoder and "
+                                          "the target kernel are device code; train on the GPU or use polygon ground truth")
+            if gt_masks.instance.device != boxes.device:
+                gt_masks = gt_masks.to(boxes.device)
+            return _C.project_rle_masks(gt_masks, gt_index, boxes, m)
         if gt_masks.dim() == 3 and gt_masks.dtype in (torch.bool, torch.uint8):
             return _C.project_masks(gt_masks, gt_index, boxes, m)
         return project_masks_on_boxes(gt_masks, gt_index, boxes, m)

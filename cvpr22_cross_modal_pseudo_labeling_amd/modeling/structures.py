@@ -6,6 +6,7 @@ and structures/image_list.py:7-72, reduced to what the training hot path touches
 ``xyxy`` float32 tensors on the device, fields are plain tensors (or python objects), and binary
 instance masks are a ``[G, H, W]`` tensor field instead of a ``SegmentationMask`` wrapper.
 """
+import numpy as np
 import torch
 
 from ..layers import nms as _nms
@@ -63,7 +64,7 @@ class BoxList:
         for k, v in self.extra_fields.items():
             if torch.is_tensor(v):
                 out.add_field(k, v[item] if v.dim() > 0 and v.shape[0] == len(self) else v)
-            elif isinstance(v, PolygonMasks):  # per-box polygon lists follow the boxes (bounding_box.py:233-242)
+            elif isinstance(v, (PolygonMasks, RleMasks)):  # per-box masks follow the boxes (bounding_box.py:233-242)
                 out.add_field(k, v[item])
             else:
                 out.add_field(k, v)
@@ -268,6 +269,186 @@ class PolygonMasks:
             from .. import _cpu
             return _cpu.polygons_to_masks(self.coords, self.polygon_start, self.instance_start, self.size)
         return _C.polygons_to_masks(self.coords, self.polygon_start, self.instance_start, self.size)
+
+
+class RleMasks:
+    """Bitmap (COCO RLE) ground-truth masks of one image, the reference's ``SegmentationMask(rles, size, mode='mask')``
+    (``BinaryMaskList``, structures/segmentation_mask.py:33-158), kept LAZY: the encodings, the geometry that was asked
+    for, and an instance index -- never a canvas.  The mask head's targets come straight from the decoded bit words
+    (``_C.project_rle_masks``, csrc/rle_targets.hip), which evaluates resize -> flips -> crop -> resize per target pixel.
+
+    ``items``: one per instance, as ``_C.coco_rle_words`` takes them -- compressed ``counts`` (``str`` / ``bytes``) or the
+    uncompressed integer list; ``source_hw`` = the (height, width) every encoding has.  Host form (made in the loader
+    worker, NumPy only): ``chars`` uint8 + ``char_offsets`` int64 [N + 1] (the strings back to back), ``runs`` int32 +
+    ``run_offsets`` int64 [N + 1] (one slot per value of every item: the lists' values in place, the strings' slots are
+    filled by the device decoder), ``sizes`` int32 [N, 2]; the number of values of a string is counted here -- its
+    characters c with ((c - 48) & 0x20) == 0 -- so the device decode needs no host read.  ``size`` = (width, height) of the
+    frame the masks are asked for in (``resize`` records it, ``transpose`` toggles the flips, both act after the decode,
+    in the reference's order: resize, then flips); ``instance`` int64 [G]: the encoding behind each instance --
+    ``__getitem__`` indexes it and repacks nothing.  ``decoded()`` adds ``words`` / ``word_offsets`` (device) and
+    ``decoded_words_per_mask``, the words every slice was given.
+    ``image_id`` / ``ann_ids`` name the masks in the error a malformed encoding raises."""
+
+    _TENSORS = ("chars", "char_offsets", "runs", "run_offsets", "sizes", "instance", "words", "word_offsets")
+
+    def __init__(self, items, source_hw, image_id=None, ann_ids=None, _state=None):
+        if _state is not None:
+            self.__dict__.update(_state)
+            return
+        h0, w0 = int(source_hw[0]), int(source_hw[1])
+        if h0 < 1 or w0 < 1 or h0 * w0 > 0x7fffffef:
+            raise ValueError(f"RleMasks: source size {h0} x {w0} is outside what the decoder takes")
+        texts, lists = [], []
+        for k, item in enumerate(items):
+            if isinstance(item, str):
+                texts.append(item.encode("latin-1", "replace"))  # beyond a byte: '?', which the decoder refuses
+                lists.append(None)
+            elif isinstance(item, (bytes, bytearray)):
+                texts.append(bytes(item))
+                lists.append(None)
+            else:
+                values = np.asarray(item).reshape(-1)
+                if values.dtype.kind not in "iu":
+                    raise ValueError(f"RleMasks: item {k} is neither a string nor a sequence of integers")
+                texts.append(b"")
+                lists.append(np.clip(values.astype(np.int64), -2 ** 31, 2 ** 31 - 1).astype(np.int32))
+        n = len(texts)
+        chars = np.frombuffer(b"".join(texts), dtype=np.uint8)
+        char_offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum([len(t) for t in texts], out=char_offsets[1:])
+        ends = ((chars.astype(np.int32) - 48) & 0x20) == 0  # a value ends at such a character
+        ends_before = np.concatenate(([0], np.cumsum(ends, dtype=np.int64)))
+        counts = ends_before[char_offsets[1:]] - ends_before[char_offsets[:-1]]
+        counts = counts + np.array([0 if v is None else len(v) for v in lists], dtype=np.int64)
+        run_offsets = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(counts, out=run_offsets[1:])
+        runs = np.zeros(int(run_offsets[-1]), dtype=np.int32)
+        for k, v in enumerate(lists):
+            if v is not None:
+                runs[run_offsets[k]:run_offsets[k + 1]] = v
+        self.chars, self.char_offsets = torch.from_numpy(chars.copy()), torch.from_numpy(char_offsets)
+        self.runs, self.run_offsets = torch.from_numpy(runs), torch.from_numpy(run_offsets)
+        self.sizes = torch.tensor([[h0, w0]] * n, dtype=torch.int32).reshape(n, 2)
+        self.instance = torch.arange(n, dtype=torch.int64)
+        self.words = self.word_offsets = self.decoded_words_per_mask = None
+        self.num_chars, self.num_runs, self.num_items = int(char_offsets[-1]), int(run_offsets[-1]), n
+        self.source_hw, self.size = (h0, w0), (w0, h0)
+        self.flip_h = self.flip_v = False
+        self.image_id = image_id
+        self.ann_ids = list(ann_ids) if ann_ids is not None else list(range(n))
+
+    def _with(self, **changes):
+        state = dict(self.__dict__)
+        state.update(changes)
+        return RleMasks(None, None, _state=state)
+
+    def map_tensors(self, fn):
+        """A copy with ``fn`` applied to every tensor it holds (staging: data/prefetch.py::_map)."""
+        return self._with(**{k: fn(getattr(self, k)) for k in self._TENSORS if getattr(self, k) is not None})
+
+    @property
+    def words_per_mask(self):
+        return (self.source_hw[0] * self.source_hw[1] + 63) // 64
+
+    def __len__(self):
+        return self.instance.numel()
+
+    def to(self, device):
+        return self.map_tensors(lambda t: t.to(device))
+
+    def device_tensors(self):
+        return [getattr(self, k) for k in self._TENSORS if getattr(self, k) is not None]
+
+    def __getitem__(self, item):
+        """Instances selected by an int, a slice, an index tensor or a boolean mask: the instance index is indexed, the
+        encodings and the words stay as they are."""
+        if isinstance(item, int):
+            item = slice(item, item + 1) if item != -1 else slice(item, None)
+        elif not isinstance(item, slice):
+            item = torch.as_tensor(item, device=self.instance.device)
+            if item.dtype == torch.bool:
+                item = torch.nonzero(item).squeeze(1)
+            item = item.reshape(-1)
+        return self._with(instance=self.instance[item])
+
+    def resize(self, size):
+        """Records ``size`` = (width, height) as the frame the masks are resampled to (BinaryMaskList.resize,
+        segmentation_mask.py:138-156).  One resize, in front of the flips: that is the chain the kernel evaluates."""
+        size = tuple(int(s) for s in size)
+        if size == self.size:
+            return self._with()
+        if self.size != (self.source_hw[1], self.source_hw[0]):
+            raise NotImplementedError(f"RleMasks.resize: already resized to {self.size}; a second resize to {size} would be "
+                                      "a resample of a resample")
+        if self.flip_h or self.flip_v:
+            raise NotImplementedError("RleMasks.resize: a resize behind a flip is not the chain the kernel evaluates")
+        if size[0] < 1 or size[1] < 1:
+            raise ValueError(f"RleMasks.resize: {size}")
+        return self._with(size=size)
+
+    def transpose(self, method):
+        """FLIP_LEFT_RIGHT (0) / FLIP_TOP_BOTTOM (1): segmentation_mask.py:113-116."""
+        if method not in (0, 1):
+            raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
+        return self._with(flip_h=not self.flip_h) if method == 0 else self._with(flip_v=not self.flip_v)
+
+    def names(self):
+        """What every encoding is, for an error message."""
+        return [f"image {self.image_id}: annotation {a}" for a in self.ann_ids]
+
+    @staticmethod
+    def decode_many(masks):
+        """ONE ``_C.coco_rle_words_staged`` call for all the (device-resident) ``RleMasks`` of a batch: every structure gets
+        its ``words`` / ``word_offsets`` (absolute offsets into the call's shared word buffer).  Sizes and value counts are
+        the host's, so nothing is read back.  -> (status int32 [total] on the device, names: one string per encoding), or
+        (None, []) when there is nothing to decode."""
+        from .. import _C
+        masks = [m for m in masks if m.num_items > 0 and m.words is None]
+        if not masks:
+            return None, []
+        dev = masks[0].chars.device
+        chars_at = runs_at = words_at = 0
+        char_offsets, run_offsets, word_offsets, names = [], [], [], []
+        for m in masks:
+            char_offsets.append(m.char_offsets[:-1] + chars_at)
+            run_offsets.append(m.run_offsets[:-1] + runs_at)
+            m_words = torch.arange(m.num_items + 1, dtype=torch.int64, device=dev) * m.words_per_mask + words_at
+            word_offsets.append(m_words)
+            chars_at, runs_at, words_at = chars_at + m.num_chars, runs_at + m.num_runs, words_at + m.num_items * m.words_per_mask
+            names += m.names()
+        char_offsets.append(torch.full((1,), chars_at, dtype=torch.int64, device=dev))
+        run_offsets.append(torch.full((1,), runs_at, dtype=torch.int64, device=dev))
+        all_word_offsets = torch.cat([w[:-1] for w in word_offsets] + [torch.full((1,), words_at, dtype=torch.int64, device=dev)])
+        words, _, status = _C.coco_rle_words_staged(
+            torch.cat([m.chars for m in masks]), torch.cat(char_offsets), torch.cat([m.runs for m in masks]),
+            torch.cat(run_offsets), torch.cat([m.sizes for m in masks]), all_word_offsets, total_words=words_at,
+            max_words=max(m.words_per_mask for m in masks), compressed=chars_at > 0)
+        for m, w in zip(masks, word_offsets):
+            m.words, m.word_offsets, m.decoded_words_per_mask = words, w, m.words_per_mask
+        return status, names
+
+    def decoded(self):
+        """This structure with ``words`` / ``word_offsets`` on the device.  Already decoded (the input transform decodes a
+        batch in one call and checks it without a synchronisation): itself.  Else it decodes alone and CHECKS -- one host
+        read; a malformed encoding raises ValueError."""
+        if self.words is not None or self.num_items == 0:
+            return self
+        if not self.chars.is_cuda:
+            raise NotImplementedError("RleMasks.decoded: the RLE decoder is a device kernel; move the masks to the GPU first "
+                                      "(RLE ground truth under MODEL.DEVICE cpu is not supported)")
+        status, names = RleMasks.decode_many([self])
+        raise_on_bad_rle(status.cpu(), names)
+        return self
+
+
+def raise_on_bad_rle(status, names):
+    """ValueError naming the first malformed encoding of a decoded batch (``status``: host int32, one per name)."""
+    from .. import _C
+    bad = torch.nonzero(status).reshape(-1).tolist()
+    if bad:
+        k = bad[0]
+        raise ValueError(f"{names[k]}: malformed RLE segmentation: {_C.COCO_RLE_STATUS.get(int(status[k]), int(status[k]))}"
+                         + (f" (and {len(bad) - 1} more)" if len(bad) > 1 else ""))
 
 
 def cat_boxlist(boxlists):  # boxlist_ops.py:107-129

@@ -923,6 +923,28 @@ int ovis_coco_runs_to_words(const int32_t* runs, const int64_t* run_offsets, con
                             const int64_t* word_offsets, int num, long max_words, int32_t* run_ends, uint64_t* words,
                             int64_t* areas, int32_t* status, void* stream);
 
+/* ovis_project_rle_masks_f32 (csrc/rle_targets.hip): the mask targets of `num` positives of ONE image straight from the bit
+ * words ovis_coco_runs_to_words made of its RLE ground truth -- what the reference computes on a
+ * SegmentationMask(mode='mask'): BinaryMaskList.resize (mb/structures/segmentation_mask.py:138-156:
+ * F.interpolate(bilinear, align_corners=False), type_as uint8) h0 x w0 -> h1 x w1, .transpose (:113-116: the flips), then
+ * project_masks_on_boxes (mb/modeling/roi_heads/mask_head/loss.py:11-42): .crop to the rounded, clamped box
+ * (segmentation_mask.py:117-136) and .resize to resolution^2.  A truncated bilinear resample of a 0/1 mask is 1 where the
+ * interpolated value reaches 1.0; both resizes are evaluated by the exact form of that: a pixel is 1 iff EVERY tap with a
+ * non-zero weight is set (taps and weights: the fp32 expressions of ovis_project_masks_f32).  The reference's fp32 sum
+ * departs from it by one rounding on a few per cent of the pixels, in either direction.  No h1 x w1 canvas is written.
+ *   words / word_offsets [num_masks + 1]: as ovis_coco_runs_to_words wrote them (absolute offsets into words); every mask
+ *   of the image is h0 x w0 and owns words_per_mask = ceil(h0 * w0 / 64) words, else OVIS_ERANGE; pixel (y, x) = bit
+ *   (y * w0 + x) % 64 of word (y * w0 + x) / 64 of its slice.  instance [num_instances] int64: the slice of ground truth g;
+ *   gt_index [num] int64: the ground truth of positive p; boxes [num, 4] xyxy in the h1 x w1 frame (16-byte aligned);
+ *   flip_h / flip_v: the resized mask is mirrored left-right / top-bottom.  out [num, resolution, resolution] f32 in {0, 1}.
+ * ADDRESSING: a slice is read only when word_offsets gives it exactly words_per_mask words, at bits below h0 * w0; a
+ * gt_index or instance entry outside its count, or such a slice, gives all-zero targets.  No word is used as an address.
+ * resolution <= 128, sizes <= 2^24, h0 * w0 <= 0x7fffffef, else OVIS_ERANGE.  One launch, enqueue only, no atomics. */
+int ovis_project_rle_masks_f32(const uint64_t* words, const int64_t* word_offsets, int num_masks, long words_per_mask,
+                               const int64_t* instance, int num_instances, const int64_t* gt_index, const float* boxes,
+                               int num, int h0, int w0, int h1, int w1, int flip_h, int flip_v, int resolution, float* out,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

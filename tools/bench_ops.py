@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, render, view_merge (``--ops paste,...,view_merge``).
+Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -487,6 +487,84 @@ def main():
                     "boxlist_over_kernel": sorted(t_ms)[1] / sorted(k_ms)[1],
                     "kernels": kernels(kernel_route), "boxlist_route_kernels": kernels(boxlist_route),
                     "outputs_equal": equal})
+    if "rle_targets" in ops:  # opt-in: mask targets from RLE ground truth, 480 x 640 -> 800 x 1067, against the dense route
+        import numpy as np
+        import torch.nn.functional as F
+
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import RleMasks
+
+        def to_string(counts):  # pycocotools' rleToString
+            out = bytearray()
+            for i, x in enumerate(counts):
+                x = int(x) - (int(counts[i - 2]) if i > 2 else 0)
+                more = True
+                while more:
+                    c = x & 0x1f
+                    x >>= 5
+                    more = (x != -1) if (c & 0x10) else (x != 0)
+                    out.append((c | 0x20 if more else c) + 48)
+            return bytes(out)
+
+        n_img, n_gt, n_pos, m_res, (h0, w0), (h1, w1) = 2, 8, 64, 14, (480, 640), (800, 1067)
+        rs = np.random.default_rng(7)
+        yy, xx = np.mgrid[:h0, :w0]
+        host, all_boxes, all_index = [], [], []
+        for _ in range(n_img):
+            items, gt = [], []
+            for _ in range(n_gt):  # an ellipse with a hole: a few hundred runs, like an instance mask
+                cx, cy, a, b = rs.uniform(80, w0 - 80), rs.uniform(80, h0 - 80), rs.uniform(30, 150), rs.uniform(30, 150)
+                d = ((xx - cx) / a) ** 2 + ((yy - cy) / b) ** 2
+                v = ((d < 1) & (d > 0.05)).T.reshape(-1).astype(np.int8)   # column-major
+                ends = np.flatnonzero(np.diff(np.concatenate([[0], v])))
+                items.append(to_string(np.diff(np.concatenate([[0], ends, [v.size]])).tolist()))
+                gt.append([cx - a, cy - b, cx + a, cy + b])
+            host.append(RleMasks(items, (h0, w0)).resize((w1, h1)).transpose(0))
+            idx = rs.integers(0, n_gt, n_pos)
+            scale = np.array([w1 / w0, h1 / h0] * 2)
+            bx = (np.array(gt)[idx] + rs.uniform(-12, 12, (n_pos, 4))) * scale
+            bx[:, 0::2] = w1 - 1 - bx[:, [2, 0]]   # the boxes follow the flip
+            all_boxes.append(torch.from_numpy(np.clip(bx, 0, [w1 - 1, h1 - 1] * 2).astype(np.float32)).to(dev))
+            all_index.append(torch.from_numpy(idx).to(dev))
+        shifts = torch.arange(64, device=dev)
+
+        staged = [m.to(dev) for m in host]
+
+        def undecoded():
+            for m in staged:
+                m.words = m.word_offsets = None
+            return staged
+
+        def kernel_route():
+            masks = undecoded()
+            RleMasks.decode_many(masks)
+            return [_C.project_rle_masks(m, i, b, m_res) for m, i, b in zip(masks, all_index, all_boxes)]
+
+        def dense_route():  # the same decode, then a uint8 canvas per instance: unpack, resize, truncate, flip, project_masks
+            masks = undecoded()
+            RleMasks.decode_many(masks)
+            out = []
+            for m, i, b in zip(masks, all_index, all_boxes):
+                bits = ((m.words.view(len(masks), n_gt, -1)[masks.index(m)][:, :, None] >> shifts) & 1).reshape(n_gt, -1)
+                canvas = bits[:, :h0 * w0].reshape(n_gt, 1, h0, w0).float()
+                canvas = F.interpolate(canvas, size=(h1, w1), mode="bilinear", align_corners=False)[:, 0].to(torch.uint8).flip(2)
+                out.append(_C.project_masks(canvas, i, b, m_res))
+            return out
+
+        def decode_only():
+            RleMasks.decode_many(undecoded())
+
+        got, want = kernel_route(), dense_route()
+        differ = sum(int((a != b).sum()) for a, b in zip(got, want))
+        k_ms, d_ms = [], []
+        for _ in range(3):  # the two routes alternate inside this one call
+            k_ms.append(timeit(kernel_route, args.iters))
+            d_ms.append(timeit(dense_route, args.iters))
+        res.append({"op": "decode_many + project_rle_masks", "shape": f"{n_img} images x {n_gt} masks {h0}x{w0} -> {h1}x{w1}, flipped, "
+                    f"{n_pos} positives each, M = {m_res}", "ms": sorted(k_ms)[1], "rounds_ms": [round(v, 4) for v in k_ms],
+                    "decode_only_ms": timeit(decode_only, args.iters), "dense_route_ms": sorted(d_ms)[1],
+                    "dense_route_rounds_ms": [round(v, 4) for v in d_ms], "dense_over_kernel": sorted(d_ms)[1] / sorted(k_ms)[1],
+                    "dense_canvas_MB": n_img * n_gt * h1 * w1 * 5 / 1e6, "target_pixels": n_img * n_pos * m_res * m_res,
+                    "target_pixels_that_differ_from_the_dense_route": differ})
     for r_ in res:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r_.items()}))
 
