@@ -2086,3 +2086,53 @@ def project_rle_masks(rle_masks, gt_index, boxes, resolution):
                                            int(m.flip_v), int(resolution), out.data_ptr(), _stream())
     _lib.check(rc, "project_rle_masks")
     return out
+
+
+# ---- box-proposal recall (evaluation/coco/coco_eval.py:199-312; csrc/proposal_recall.hip) ---------------------------------
+def proposal_gt_overlaps(proposals, gt_boxes, gt_areas, images, area_ranges, limits):
+    """The matching of the reference's ``evaluate_box_proposals`` (coco_eval.py:269-290 over ``boxlist_iou``) for a chunk of
+    images, every area range and every limit in one launch (``ovis_proposal_gt_overlaps``).  proposals [P, 4] and gt_boxes
+    [G, 4] fp32 xyxy in one frame, proposals best first inside an image; gt_areas [G] fp32; area_ranges [A, 2] fp32 -- all on
+    the device.  images: a HOST int64 [N, 4] table (prop_start, prop_count, gt_start, gt_count), checked here row by row
+    against the buffers (the kernel trusts it) and uploaded; limits: a sequence of L positive ints.  -> fp32 [A, L, G]: per
+    ground truth the IoU of the round that consumed it, 0 when it is inside the area range (both ends inclusive) but was
+    never consumed, -1 when it is outside; rows of no image stay -1.  ValueError: a reversed box, x2 - x1 + 1 <= 0 or
+    y2 - y1 + 1 <= 0 (its union with another box could be <= 0; x2 < x1 by less than a pixel is a decoded box narrower than
+    a pixel, which the reference scores).  More ground truths in an image than ``_lib.OVIS_PROPOSAL_RECALL_MAX_GTS`` or a limit
+    above ``_lib.OVIS_PROPOSAL_RECALL_MAX_LIMIT``: OVIS_ERANGE."""
+    proposals, gt_boxes = _dev(proposals, "proposals"), _dev(gt_boxes, "gt_boxes")
+    gt_areas, area_ranges = _dev(gt_areas, "gt_areas"), _dev(area_ranges, "area_ranges")
+    if proposals.dim() != 2 or proposals.shape[1] != 4 or gt_boxes.dim() != 2 or gt_boxes.shape[1] != 4 \
+            or gt_areas.shape != (gt_boxes.shape[0],) or area_ranges.dim() != 2 or area_ranges.shape[1] != 2 \
+            or not area_ranges.shape[0]:
+        raise RuntimeError("proposal_gt_overlaps: expected proposals [P,4], gt_boxes [G,4], gt_areas [G] and area_ranges [A,2]")
+    table = torch.as_tensor(images, dtype=torch.int64).reshape(-1, 4).contiguous()
+    if table.is_cuda or bool((table < 0).any()):
+        raise RuntimeError("proposal_gt_overlaps: a host table of non-negative int64 [N, 4] expected")
+    limits = torch.as_tensor(limits, dtype=torch.int32).reshape(-1)
+    if limits.is_cuda or not limits.numel() or bool((limits < 1).any()):
+        raise RuntimeError("proposal_gt_overlaps: limits is a host sequence of positive ints")
+    p, g, a, n_limits = proposals.shape[0], gt_boxes.shape[0], area_ranges.shape[0], limits.numel()
+    bad = (table[:, 0] + table[:, 1] > p) | (table[:, 2] + table[:, 3] > g)
+    if bool(bad.any()):
+        raise RuntimeError(f"proposal_gt_overlaps: image {int(torch.nonzero(bad)[0])} of the table points outside its buffers")
+    for name, boxes in (("proposals", proposals), ("gt_boxes", gt_boxes)):
+        # a decoded box narrower than a pixel has x2 < x1 by less than 1 and a positive width x2 - x1 + 1: the reference
+        # scores it, and so does the kernel; a width or height that is not positive could make the union <= 0
+        if boxes.numel() and bool(((boxes[:, 2] - boxes[:, 0] + 1 <= 0) | (boxes[:, 3] - boxes[:, 1] + 1 <= 0)).any()):
+            raise ValueError(f"proposal_gt_overlaps: {name} holds a reversed box: x2 - x1 + 1 <= 0 or y2 - y1 + 1 <= 0")
+    out = torch.full((a, n_limits, g), -1.0, dtype=torch.float32, device=gt_boxes.device)
+    n = table.shape[0]
+    if n == 0:
+        return out
+    # the uploads are held in names until the launch is enqueued: a temporary's block would go back to the caching
+    # allocator at once and be handed to the next upload
+    table_dev, limits_dev = table.to(gt_boxes.device), limits.to(gt_boxes.device)
+    with _on(gt_boxes.device):
+        rc = _L.ovis_proposal_gt_overlaps(proposals.data_ptr() if p else 0, gt_boxes.data_ptr() if g else 0,
+                                          gt_areas.data_ptr() if g else 0, table_dev.data_ptr(), n,
+                                          int(table[:, 3].max()), area_ranges.data_ptr(), a,
+                                          limits_dev.data_ptr(), n_limits, int(limits.max()), g,
+                                          out.data_ptr() if g else 0, _stream())
+    _lib.check(rc, "proposal_gt_overlaps")
+    return out

@@ -27,8 +27,13 @@ group in one call straight to the packed words, and reports a malformed encoding
 Semantics beyond pycocotools' own: images and categories are all those of the annotation file, sorted by id; an image
 without a prediction counts with zero detections; every annotation is ground truth, crowds included (``ignore =
 iscrowd``); a ground truth's ``area`` is the annotation's ``area`` when present, else its box's w * h; an IoU whose union
-is 0 is 0 (pycocotools yields NaN for two zero-area boxes; clipped detections have w, h >= 1).  AR summaries, keypoints
-and ``box_proposal`` recall are not computed.
+is 0 is 0 (pycocotools yields NaN for two zero-area boxes; clipped detections have w, h >= 1).
+
+RECALL.  ``recall=True`` adds ``COCOeval.summarize``'s six AR numbers and AR100_split_<split> (``accumulate_recall`` /
+``summarize_recall``): host arithmetic over the SAME match tables, no further device work -- the matching walks a problem's
+detections in score order, so the first k columns of the maxDets = 100 tables are the maxDets = k matching, which is how
+pycocotools itself slices them.  The ``box_proposal`` task of the reference's table is a different, class-agnostic matching
+with a kernel of its own: engine/proposal_recall.py.  Keypoints are not scored.
 """
 import contextlib
 import json
@@ -122,6 +127,58 @@ def summarize(precision, category_names, class_splits, class_order=None):
         res[f"AP50_class_{category_names[k]}"] = _mean(s[:, :, [k]])
     for split, cats in class_splits.items():
         res[f"AP50_split_{split}"] = _mean(s[:, :, list(cats)])
+    return res
+
+
+RECALL_METRICS = ("AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
+
+
+def accumulate_recall(tables, num_categories):
+    """The ``recall`` array of ``COCOeval.accumulate`` -> fp64 [T, K, A, M] from the match tables ``accumulate`` takes: -1
+    where the category has no problem or no non-ignored ground truth in the area range, 0 where it has no detection, else
+    tp / npig after the last of the first ``maxDet`` detections of every image.  ``match_kernel`` walks a problem's
+    detections in score order, each choosing among what the earlier ones left, so the first k columns of the maxDets = 100
+    tables ARE the maxDets = k matching -- pycocotools slices ``dtMatches[:, 0:maxDet]`` in the same way."""
+    cat = np.asarray(tables["category"], dtype=np.int64)
+    det_start, gt_start = np.asarray(tables["det_start"], dtype=np.int64), np.asarray(tables["gt_start"], dtype=np.int64)
+    matched_all, dt_ignore_all = np.asarray(tables["dt_match"]) >= 0, np.asarray(tables["dt_ignore"], dtype=bool)
+    gt_ignore_all = np.asarray(tables["gt_ignore"], dtype=bool)
+    det_problem = np.repeat(np.arange(len(cat)), np.diff(det_start))
+    det_rank = np.arange(len(det_problem)) - det_start[:-1][det_problem]
+    det_cat, gt_cat = cat[det_problem], np.repeat(cat, np.diff(gt_start))
+    num_t, num_a, num_m = len(IOU_THRESHOLDS), len(AREA_RANGES), len(MAX_DETS)
+    recall = -np.ones((num_t, num_categories, num_a, num_m))
+    for k in range(num_categories):
+        if not np.any(cat == k):
+            continue
+        dets_k, gts_k = np.nonzero(det_cat == k)[0], gt_cat == k
+        for a in range(num_a):
+            npig = np.count_nonzero(~gt_ignore_all[a][gts_k])
+            if npig == 0:
+                continue
+            for m, max_det in enumerate(MAX_DETS):
+                sel = dets_k[det_rank[dets_k] < max_det]
+                # the last entry of a running sum: the order of the detections does not matter
+                tps = np.logical_and(matched_all[a][:, sel], np.logical_not(dt_ignore_all[a][:, sel]))
+                tp_sum = np.cumsum(tps, axis=1).astype(dtype=np.float64)
+                for t, tp in enumerate(tp_sum):
+                    recall[t, k, a, m] = (tp / npig)[-1] if len(tp) else 0
+    return recall
+
+
+def summarize_recall(recall, category_names, class_splits):
+    """``COCOeval.summarize``'s six AR numbers -- AR1, AR10, AR100 (all areas), ARs, ARm, ARl (maxDets = 100), each the
+    mean of the entries > -1 -- and AR100_split_<split> over the categories of every split -> OrderedDict."""
+    m100 = MAX_DETS.index(100)
+    res = OrderedDict()
+    for name, m in (("AR1", MAX_DETS.index(1)), ("AR10", MAX_DETS.index(10)), ("AR100", m100)):
+        res[name] = _mean(recall[:, :, 0, m])
+    for name, a in (("ARs", 1), ("ARm", 2), ("ARl", 3)):
+        res[name] = _mean(recall[:, :, a, m100])
+    if len(category_names) != recall.shape[1]:
+        raise ValueError(f"summarize_recall: {len(category_names)} category names for a recall array of {recall.shape[1]}")
+    for split, cats in class_splits.items():
+        res[f"AR100_split_{split}"] = _mean(recall[:, list(cats), 0, m100])
     return res
 
 
@@ -522,9 +579,9 @@ def _scoring_device(device, who):
     return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
 
 
-def _summaries(dataset, iou_types, device, tables_of):
+def _summaries(dataset, iou_types, device, tables_of, recall=False):
     """{iou_type: ``summarize`` of ``accumulate`` of ``tables_of(iou_type, ground truth)``} with the dataset's names,
-    splits and class order."""
+    splits and class order; ``recall``: followed by ``summarize_recall`` of ``accumulate_recall`` of the same tables."""
     results = OrderedDict()
     ground_truth = _ground_truth(dataset)
     cat_ids = ground_truth[0]
@@ -536,31 +593,37 @@ def _summaries(dataset, iou_types, device, tables_of):
             tables, _ = tables_of(iou_type, ground_truth)
             results[iou_type] = summarize(accumulate(tables, len(cat_ids)), [dataset.categories[c] for c in cat_ids], splits,
                                           class_order)
+            if recall:
+                results[iou_type].update(summarize_recall(accumulate_recall(tables, len(cat_ids)),
+                                                          [dataset.categories[c] for c in cat_ids], splits))
     return results
 
 
-def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda"):
+def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda", recall=False):
     """{iou_type: OrderedDict of AP, AP50, AP75, APs, APm, APl, AP50_class_<name> per category (in the order of
     ``dataset.categories``, as ``COCOResults.update`` iterates) and AP50_split_<split> per key of ``dataset.class_splits``}
     for ``predictions``: the list ``inference()`` returns or ``torch.load`` gives from ``predictions.pth`` (BoxLists in
-    dataset-index order, fields ``scores``, ``labels`` and -- for segm -- ``mask`` [K, 1, M, M]).  ``device``: the HIP
-    device that scores; there is no host-only scoring."""
+    dataset-index order, fields ``scores``, ``labels`` and -- for segm -- ``mask`` [K, 1, M, M]).  ``recall``: followed by
+    AR1, AR10, AR100, ARs, ARm, ARl and AR100_split_<split> (``summarize_recall``).  ``device``: the HIP device that scores;
+    there is no host-only scoring."""
     device = _scoring_device(device, "evaluate_coco")
     return _summaries(dataset, iou_types, device,
-                      lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt))
+                      lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt), recall)
 
 
-def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="cuda"):
+def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="cuda", recall=False):
     """``evaluate_coco``'s numbers, in the same structure, for detections that come from COCO results files: ``results`` is
     {iou_type: a path or the parsed list} (``load_coco_results``); an iou_type it does not have is skipped.  Whatever wrote
     the files -- ``export_coco_results``, the reference, another tool -- nothing but the annotation file is needed beside
-    them.  ``device``: the HIP device that decodes the masks and scores; there is no host-only scoring."""
+    them.  ``recall``: as in ``evaluate_coco``.  ``device``: the HIP device that decodes the masks and scores; there is no
+    host-only scoring."""
     device = _scoring_device(device, "evaluate_coco_results")
     for iou_type in results:
         if iou_type not in ("bbox", "segm"):
             raise ValueError(f"evaluate_coco_results: iou_type '{iou_type}' is not supported (bbox, segm)")
     return _summaries(dataset, [t for t in iou_types if t in results], device,
-                      lambda iou_type, gt: results_match_tables(dataset, results[iou_type], iou_type, device, ground_truth=gt))
+                      lambda iou_type, gt: results_match_tables(dataset, results[iou_type], iou_type, device, ground_truth=gt),
+                      recall)
 
 
 def annotation_dataset(ann_file):

@@ -25,8 +25,10 @@ from ..modeling.structures import BoxList
 
 
 @torch.no_grad()
-def compute_on_dataset(model, batches, device, timer=None):
-    """batches: iterable of (images, targets, image_ids) -> {image_id: BoxList on CPU} (inference.py:25-47).  A batch whose
+def compute_on_dataset(model, batches, device, timer=None, forward=None):
+    """batches: iterable of (images, targets, image_ids) -> {image_id: BoxList on CPU} (inference.py:25-47).  ``forward``:
+    a callable images -> [BoxList] that takes the place of the model's evaluation pass (``model.propose``: the RPN's
+    proposals instead of detections); it has no multi-view form, so a ``ViewBatch`` raises.  Without it: a batch whose
     images are a ``ViewBatch`` (TEST.BBOX_AUG: build_transforms(cfg, False) made every view) goes through
     ``im_detect_bbox_aug`` (inference.py:34-35).  A model configured with TEST.BBOX_AUG.ENABLED that is handed ready-made
     images instead raises: the views are made from raw bytes, which such a stream (``tools/test_net.py``'s float32 synthetic
@@ -37,7 +39,11 @@ def compute_on_dataset(model, batches, device, timer=None):
     cpu = torch.device("cpu")
     for images, targets, image_ids in batches:
         t0 = time.perf_counter()
-        if isinstance(images, ViewBatch):
+        if forward is not None:
+            if isinstance(images, ViewBatch):
+                raise ValueError("compute_on_dataset: forward= takes single-view batches (TEST.BBOX_AUG.ENABLED False)")
+            output = forward(images.to(device))
+        elif isinstance(images, ViewBatch):
             output = im_detect_bbox_aug(model, images.to(device))
         elif augmented:
             raise ValueError("TEST.BBOX_AUG.ENABLED, but the batch holds already-transformed images: the views are made from "
@@ -131,16 +137,18 @@ def accumulate_predictions(predictions, logger=None):
 
 
 def inference(model, batches, dataset_name="synthetic", device="cuda", output_folder=None, class_embeddings=None,
-              logger=None):
+              logger=None, forward=None, file_name="predictions.pth"):
     """Detections of every image of ``batches`` (this rank's shard), gathered on rank 0 in image-id order and saved
-    as ``predictions.pth`` (inference.py:104-170, without the dataset-specific ``evaluate`` call)."""
+    as ``predictions.pth`` (inference.py:104-170, without the dataset-specific ``evaluate`` call).  ``forward`` /
+    ``file_name``: what ``compute_on_dataset`` runs instead of the model's evaluation pass, and the file its BoxLists are
+    saved to (``model.propose`` and ``proposals.pth`` for the RPN's proposals)."""
     logger = logger or logging.getLogger("ovis.inference")
     device = torch.device(device)
     if class_embeddings is not None:  # zero-shot heads map predicted embeddings to classes (inference.py:124-131)
         model.set_class_embeddings(class_embeddings.to(device))
     times = []
     start = time.perf_counter()
-    predictions = compute_on_dataset(model, batches, device, times)
+    predictions = compute_on_dataset(model, batches, device, times, forward=forward)
     comm.synchronize()
     total = time.perf_counter() - start
     world = comm.get_world_size()
@@ -153,5 +161,5 @@ def inference(model, batches, dataset_name="synthetic", device="cuda", output_fo
         return None
     if output_folder:
         os.makedirs(output_folder, exist_ok=True)
-        torch.save(ordered, os.path.join(output_folder, "predictions.pth"))
+        torch.save(ordered, os.path.join(output_folder, file_name))
     return ordered

@@ -109,6 +109,19 @@ class GeneralizedRCNN(nn.Module):
         _require_eval(self)
         return self.roi_heads["mask"](features, detections)[1]
 
+    @torch.no_grad()
+    def propose(self, images):
+        """Backbone and RPN of the evaluation pass alone -> [BoxList with ``objectness``]: the MODEL.RPN.POST_NMS_TOP_N_TEST
+        proposals the box head would be given (what ``tools/infer_net.py --rpn-recall`` scores)."""
+        _require_eval(self)
+        return _propose(self, images)
+
+
+def _propose(model, images):
+    images = to_image_list(images)
+    proposals, _ = model.rpn(images, model.backbone(images.tensors), None)
+    return [p.copy_with_fields(["objectness"]) for p in proposals]
+
 
 def _require_eval(model):
     if model.training:
@@ -271,6 +284,12 @@ class STGeneralizedRCNN(nn.Module):
         """The student's mask head, evaluation pass, on given boxes (BoxLists with ``labels``) -> detections with ``mask``."""
         _require_eval(self)
         return self.roi_heads_student["mask"](features, detections)[1]
+
+    @torch.no_grad()
+    def propose(self, images):
+        """Backbone and RPN of the evaluation pass alone -> [BoxList with ``objectness``], as ``GeneralizedRCNN.propose``."""
+        _require_eval(self)
+        return _propose(self, images)
 
     @torch.no_grad()
     def forward_frozen(self, images, targets, features=None):

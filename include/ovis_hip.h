@@ -945,6 +945,35 @@ int ovis_project_rle_masks_f32(const uint64_t* words, const int64_t* word_offset
                                int num, int h0, int w0, int h1, int w1, int flip_h, int flip_v, int resolution, float* out,
                                void* stream);
 
+/* ovis_proposal_gt_overlaps (csrc/proposal_recall.hip): the matching of the reference's box-proposal recall,
+ * evaluate_box_proposals (mb/data/datasets/evaluation/coco/coco_eval.py:199-312; the greedy loop is :269-290, the area
+ * test :258, the limit :269-270) over boxlist_iou (mb/structures/boxlist_ops.py:53-89), for a chunk of images, num_areas
+ * area ranges and num_limits proposal limits in ONE launch.  images: device int64 [num_images, 4] = (prop_start,
+ * prop_count, gt_start, gt_count) over proposals [*, 4] (fp32 xyxy in the ground truth's frame, best objectness first
+ * inside an image), gt_boxes [num_gts, 4] (fp32 xyxy) and gt_areas [num_gts] (fp32).  area_ranges [num_areas, 2] fp32,
+ * limits [num_limits] int32.  A UNIT is one (image, area range [lo, hi], limit): its ground truths are those with
+ * area >= lo && area <= hi, its proposals the first P' = min(prop_count, limit).  min(P', valid ground truths) rounds; each
+ * takes the live ground truth whose best IoU over the live proposals is largest (ties: the lowest ground-truth index) and
+ * the live proposal that attains it (ties: the lowest proposal index) -- torch.max's first occurrence on both axes --
+ * records that IoU for the ground truth and removes both.  A ground truth that overlaps no live proposal still consumes the
+ * first live proposal and records 0.
+ *   out fp32 [num_areas, num_limits, num_gts]: per ground truth of an image of the table the recorded IoU, 0 when it is
+ *   inside the range but was never consumed, -1 when its area is outside the range.  Rows of no image are not written.
+ *   IoU: fp32, TO_REMOVE = 1: area = (x2 - x1 + 1) * (y2 - y1 + 1), w = max(min(x2, X2) - max(x1, X1) + 1, 0), h likewise,
+ *   iou = w * h / ((area_p + area_g) - w * h), in this operation order without contraction: bit-identical to boxlist_iou.
+ *   Boxes must have x2 - x1 + 1 > 0 and y2 - y1 + 1 > 0 (the intersection is then at most either area and the union
+ *   positive; a decoded box narrower than a pixel has x2 < x1 by less than 1 and passes); the caller checks.
+ * max_gts / max_limit: the largest gt_count of the table / the largest limit; more than OVIS_PROPOSAL_RECALL_MAX_GTS /
+ * OVIS_PROPOSAL_RECALL_MAX_LIMIT: OVIS_ERANGE.  The kernel does not check the table against the buffers: the caller does,
+ * on the host.  The IoU matrix is never stored; no atomics, no scratch, deterministic and independent of the launch
+ * geometry (one workgroup per unit).  num_images == 0: OVIS_OK without a launch.  proposals may be NULL when no image of
+ * the table has a proposal. */
+#define OVIS_PROPOSAL_RECALL_MAX_GTS 256
+#define OVIS_PROPOSAL_RECALL_MAX_LIMIT 1024
+int ovis_proposal_gt_overlaps(const float* proposals, const float* gt_boxes, const float* gt_areas, const int64_t* images,
+                              int num_images, int max_gts, const float* area_ranges, int num_areas, const int32_t* limits,
+                              int num_limits, int max_limit, long num_gts, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

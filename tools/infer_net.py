@@ -14,7 +14,12 @@ sizes.  ``--visualize N`` (rank 0) also renders the first N images of every test
 against its own annotation file on the device (engine/coco_eval.py: COCO box AP, and mask AP when MODEL.MASK_ON, plus AP50
 per class and per seen / unseen split), logs the reference's ``Task: ... / names / values`` table and writes
 ``<OUTPUT_DIR>/inference/<name>/coco_results.json``; it needs OUTPUT_DIR and MODEL.DEVICE cuda -- there is no host-only
-scoring.  ``--export-results`` (rank 0, after the gather, independent of ``--evaluate``) writes the detections as COCO results
+scoring.  ``--recall`` (with ``--evaluate``) completes the reference's table: a ``box_proposal`` task first -- AR@100, ARs@100,
+... ARl@1000 of the detections scored as class-agnostic proposals, and AR@<limit>_split_<split> (engine/proposal_recall.py, matched
+on the device) -- and COCO's AR1 / AR10 / AR100 / ARs / ARm / ARl plus AR100_split_<split> behind the AP keys.  ``--rpn-recall``
+is a run of its own: backbone + RPN alone (``model.propose``), the proposals gathered like detections into
+``<OUTPUT_DIR>/inference/<name>/proposals.pth`` and scored by ``objectness`` as an ``rpn_proposal`` task, written to
+``rpn_recall.json`` -- whether the RPN proposes the unseen classes at all.  ``--export-results`` (rank 0, after the gather, independent of ``--evaluate``) writes the detections as COCO results
 files next to ``predictions.pth`` (engine/coco_results.py): ``bbox.json``, and ``segm.json`` when MODEL.MASK_ON -- every
 detection, boxes as xywh and masks as compressed RLE at the ORIGINAL image sizes, the masks encoded on the device; it needs
 OUTPUT_DIR, and MODEL.DEVICE cuda when MODEL.MASK_ON.  ``TEST.BBOX_AUG.ENABLED True`` (with H_FLIP / SCALES / MAX_SIZE / SCALE_H_FLIP) turns on multi-scale / flip testing:
@@ -27,6 +32,7 @@ import json
 import logging
 import os
 import sys
+from collections import OrderedDict
 
 import torch
 import torch.distributed as dist
@@ -40,7 +46,7 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  
 from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem_bn, make_batch, make_embeddings  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, coco_results, comm, inference, visualize  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, coco_results, comm, inference, proposal_recall, visualize  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
@@ -59,18 +65,55 @@ def save_visualizations(dataset, predictions, folder, count, threshold, device):
         Image.fromarray(picture).save(os.path.join(folder, stem + ".png"))
 
 
-def save_evaluation(dataset, predictions, folder, iou_types, device, logger):
+def save_evaluation(dataset, predictions, folder, iou_types, device, logger, recall=False):
     """COCO scoring of one test set (engine/coco_eval.py): the table goes to the log, the numbers to
-    ``folder``/coco_results.json as {iou_type: {metric: value}}."""
-    results = coco_eval.evaluate_coco(dataset, predictions, iou_types, device)
+    ``folder``/coco_results.json as {iou_type: {metric: value}}.  ``recall``: the reference's whole table -- a
+    ``box_proposal`` task first (engine/proposal_recall.py: the detections scored as proposals by their ``scores``, which is
+    what the reference's table shows, its post-processor copying ``scores`` into ``objectness``), and the AR keys behind the
+    AP keys of every iou_type."""
+    if recall:
+        results = OrderedDict(box_proposal=proposal_recall.evaluate_box_proposals(dataset, predictions, device, "scores"))
+        results.update(coco_eval.evaluate_coco(dataset, predictions, iou_types, device, recall=True))
+    else:
+        results = coco_eval.evaluate_coco(dataset, predictions, iou_types, device)
     logger.info(coco_eval.format_results(results))
     with open(os.path.join(folder, "coco_results.json"), "w") as f:
         json.dump(results, f, indent=1)
     return results
 
 
+def run_rpn_recall(cfg, model, catalog, device, logger=None):
+    """Backbone + RPN alone over every DATASETS.TEST name (``model.propose``): the MODEL.RPN.POST_NMS_TOP_N_TEST proposals
+    of every image, gathered like detections and saved as ``<OUTPUT_DIR>/inference/<name>/proposals.pth``, and on rank 0
+    their box-proposal recall by ``objectness`` (engine/proposal_recall.py) as a ``rpn_proposal`` task in the log and in
+    ``rpn_recall.json`` -> {name: the numbers (rank 0) or None}."""
+    if not cfg.OUTPUT_DIR:
+        raise ValueError("run_rpn_recall writes OUTPUT_DIR/inference/<name>/proposals.pth and rpn_recall.json: set OUTPUT_DIR")
+    logger = logger or logging.getLogger("ovis.inference")
+    transform = build_transforms(cfg, is_train=False)
+    results = {}
+    for name in cfg.DATASETS.TEST:
+        dataset = build_dataset(cfg, name, catalog)
+        loader = make_data_loader(cfg, dataset, transform, False, comm.get_rank(), comm.get_world_size())
+        batches = DevicePrefetcher(loader, device, depth=2, transform=transform)
+        out = os.path.join(cfg.OUTPUT_DIR, "inference", name)
+        try:
+            proposals = inference.inference(model, batches, name, device, out, logger=logger, forward=model.propose,
+                                            file_name="proposals.pth")
+        finally:
+            batches.close()
+        results[name] = None
+        if proposals is not None:
+            results[name] = OrderedDict(rpn_proposal=proposal_recall.evaluate_box_proposals(dataset, proposals, device,
+                                                                                            "objectness"))
+            logger.info(coco_eval.format_results(results[name]))
+            with open(os.path.join(out, "rpn_recall.json"), "w") as f:
+                json.dump(results[name], f, indent=1)
+    return results
+
+
 def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
-                 export_results=False):
+                 export_results=False, recall=False):
     """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}."""
     transform = build_transforms(cfg, is_train=False)
     results = {}
@@ -93,7 +136,7 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
                              "set OUTPUT_DIR")
         if evaluate and results[name] is not None:
             save_evaluation(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",), device,
-                            logger or logging.getLogger("ovis.inference"))
+                            logger or logging.getLogger("ovis.inference"), recall)
         if export_results and results[name] is not None:
             coco_results.export_coco_results(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",),
                                              device)
@@ -117,6 +160,14 @@ def main(argv=None):
     parser.add_argument("--export-results", action="store_true",
                         help="write every test set's detections as COCO results files, OUTPUT_DIR/inference/<name>/bbox.json "
                              "and (MODEL.MASK_ON) segm.json with the masks RLE-encoded on the device (rank 0)")
+    parser.add_argument("--recall", action="store_true",
+                        help="with --evaluate: the reference's whole table -- a box_proposal task first (AR@100 ... ARl@1000 of "
+                             "the detections scored as proposals, and per split) and COCO AR1 / AR10 / AR100 / ARs / ARm / ARl "
+                             "and AR100 per split behind the AP keys")
+    parser.add_argument("--rpn-recall", action="store_true",
+                        help="run backbone + RPN alone over every test set, save the proposals as "
+                             "OUTPUT_DIR/inference/<name>/proposals.pth and score their recall by objectness on the device: an "
+                             "rpn_proposal task in the log and in rpn_recall.json (rank 0); no detections are made")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args(argv)
 
@@ -133,6 +184,17 @@ def main(argv=None):
     if args.evaluate and cfg.MODEL.DEVICE != "cuda":
         parser.error("--evaluate scores on the HIP device (mask IoU and matching have no host implementation): "
                      "set MODEL.DEVICE cuda")
+    if args.recall and not args.evaluate:
+        parser.error("--recall adds the recall numbers to what --evaluate scores: give --evaluate too")
+    if args.rpn_recall and not cfg.OUTPUT_DIR:
+        parser.error("--rpn-recall writes OUTPUT_DIR/inference/<name>/proposals.pth and rpn_recall.json: set OUTPUT_DIR")
+    if args.rpn_recall and cfg.MODEL.DEVICE != "cuda":
+        parser.error("--rpn-recall matches proposals and ground truth on the HIP device (no host implementation): "
+                     "set MODEL.DEVICE cuda")
+    if args.rpn_recall and (args.evaluate or args.export_results or args.visualize > 0):
+        parser.error("--rpn-recall makes no detections: it does not go with --evaluate, --export-results or --visualize")
+    if args.rpn_recall and cfg.TEST.BBOX_AUG.ENABLED:
+        parser.error("--rpn-recall scores the proposals of one view: set TEST.BBOX_AUG.ENABLED False")
     if args.export_results and not cfg.OUTPUT_DIR:
         parser.error("--export-results writes OUTPUT_DIR/inference/<name>/bbox.json and segm.json: set OUTPUT_DIR")
     if args.export_results and cfg.MODEL.MASK_ON and cfg.MODEL.DEVICE != "cuda":
@@ -160,10 +222,13 @@ def main(argv=None):
         calibrate_stem_bn(model, images)  # random init only: give the frozen BN usable statistics
     _, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
     model.set_class_embeddings(e_seen)  # stands until a dataset brings its own (DATASETS.DATASET_ARGS.LOAD_EMBEDDINGS)
-    for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
-                                    args.evaluate, args.export_results).items():
-        if preds is not None:
-            logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
+    if args.rpn_recall:
+        run_rpn_recall(cfg, model, catalog, device, logger)
+    else:
+        for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
+                                        args.evaluate, args.export_results, args.recall).items():
+            if preds is not None:
+                logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:
         dist.destroy_process_group()
 

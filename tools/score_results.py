@@ -8,7 +8,7 @@ without a model, a configuration or the images (engine/coco_eval.py: ``evaluate_
   python tools/score_results.py --ann-file instances_val.json --segm segm.json --output scores.json
 
 Prints the ``Task: ... / names / values`` table ``--evaluate`` logs; ``--output`` writes the numbers as
-``coco_results.json`` has them.  There is no host-only scoring: the device must be a HIP device.
+``coco_results.json`` has them.  ``--recall`` adds COCO's AR numbers behind the AP keys, from the same match tables.  There is no host-only scoring: the device must be a HIP device.
 """
 import argparse
 import json
@@ -30,6 +30,9 @@ def main(argv=None):
     parser.add_argument("--segm", default=None, metavar="PATH", help="a segm results file (RLE masks)")
     parser.add_argument("--results-dir", default=None, metavar="DIR", help="DIR/bbox.json and DIR/segm.json, whichever exist")
     parser.add_argument("--output", default=None, metavar="PATH", help="write {iou_type: {metric: value}} as JSON")
+    parser.add_argument("--recall", action="store_true",
+                        help="add COCO's AR1 / AR10 / AR100 / ARs / ARm / ARl and AR100 per split behind the AP keys (results "
+                             "files are capped per category, so they are not proposal lists: no box_proposal task)")
     parser.add_argument("--device", default="cuda", help="the HIP device that scores (cuda, cuda:1, ...)")
     args = parser.parse_args(argv)
     files = {}
@@ -55,7 +58,7 @@ def main(argv=None):
     from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval
 
     dataset = coco_eval.annotation_dataset(args.ann_file)
-    results = coco_eval.evaluate_coco_results(dataset, files, IOU_TYPES, device)
+    results = coco_eval.evaluate_coco_results(dataset, files, IOU_TYPES, device, recall=args.recall)
     print(coco_eval.format_results(results))
     if args.output:
         with open(args.output, "w") as f:
