@@ -34,6 +34,11 @@ RECALL.  ``recall=True`` adds ``COCOeval.summarize``'s six AR numbers and AR100_
 detections in score order, so the first k columns of the maxDets = 100 tables are the maxDets = k matching, which is how
 pycocotools itself slices them.  The ``box_proposal`` task of the reference's table is a different, class-agnostic matching
 with a kernel of its own: engine/proposal_recall.py.  Keypoints are not scored.
+
+SHARDED.  ``evaluate_coco_sharded`` is ``evaluate_coco`` for a caller that holds one rank's {dataset index: BoxList} instead of
+the gathered list (a training run's periodic evaluation, engine/evaluation.py): an image's matching does not depend on any
+other image, so every rank scores the images it predicted on its own device and only the match tables go to rank 0, where
+``merge_shard_tables`` puts the whole-image blocks into image-id order -- the tables ``match_tables`` gives, array for array.
 """
 import contextlib
 import json
@@ -42,7 +47,9 @@ from collections import OrderedDict
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
+from . import comm
 from .. import _C
 from ..modeling.structures import BoxList, PolygonMasks
 
@@ -579,11 +586,11 @@ def _scoring_device(device, who):
     return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
 
 
-def _summaries(dataset, iou_types, device, tables_of, recall=False):
+def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth=None):
     """{iou_type: ``summarize`` of ``accumulate`` of ``tables_of(iou_type, ground truth)``} with the dataset's names,
     splits and class order; ``recall``: followed by ``summarize_recall`` of ``accumulate_recall`` of the same tables."""
     results = OrderedDict()
-    ground_truth = _ground_truth(dataset)
+    ground_truth = ground_truth if ground_truth is not None else _ground_truth(dataset)
     cat_ids = ground_truth[0]
     cat_index = {c: i for i, c in enumerate(cat_ids)}
     splits = OrderedDict((split, [cat_index[c] for c in ids]) for split, ids in dataset.class_splits.items())
@@ -624,6 +631,98 @@ def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="
     return _summaries(dataset, [t for t in iou_types if t in results], device,
                       lambda iou_type, gt: results_match_tables(dataset, results[iou_type], iou_type, device, ground_truth=gt),
                       recall)
+
+
+# ---- every rank scores what it predicted: only match tables travel --------------------------------------------------------
+def shard_owners(index_lists):
+    """{dataset index: the rank that scores it} for ``index_lists[rank]`` = the dataset indices rank ``rank`` predicted: the
+    LOWEST rank that holds an index owns it (the test sampler's last slice may wrap around to index 0, so an image can sit
+    on two ranks).  A function of the exchanged lists alone: every rank evaluates it to the same answer."""
+    owner = {}
+    for rank, indices in enumerate(index_lists):
+        for idx in indices:
+            owner.setdefault(int(idx), rank)
+    return owner
+
+
+def merge_shard_tables(parts):
+    """The match tables of several shards as the one table ``match_tables`` gives for all their images.  ``parts[rank]``:
+    the tables of that rank's images plus ``image`` int [P], the image id of every problem; the problems of an image are
+    consecutive (a whole-image block), the blocks of a part in any order.  Blocks are put into image-id order and
+    concatenated; of an image that several parts hold, the lowest rank's block is kept (``shard_owners``' rule).  An image
+    scores the same whatever else is scored beside it, so this is array for array the unsharded result -- and with it the
+    tie order of ``accumulate``, whose stable sort leaves equal scores in image order.  Host only, NumPy only."""
+    blocks = {}
+    for part in parts:
+        image = np.asarray(part["image"], dtype=np.int64)
+        if len(image) != len(part["category"]):
+            raise ValueError(f"merge_shard_tables: {len(image)} image ids for {len(part['category'])} problems")
+        if not len(image):
+            continue
+        cuts = np.flatnonzero(np.diff(image)) + 1
+        seen = set()
+        for p0, p1 in zip(np.concatenate([[0], cuts]).tolist(), np.concatenate([cuts, [len(image)]]).tolist()):
+            img_id = int(image[p0])
+            if img_id in seen:
+                raise ValueError(f"merge_shard_tables: the problems of image {img_id} are not one block")
+            seen.add(img_id)
+            blocks.setdefault(img_id, (part, p0, p1))  # parts come in rank order: the first holder is the lowest rank
+    ordered = []
+    for img_id in sorted(blocks):
+        part, p0, p1 = blocks[img_id]
+        d0, d1, g0, g1 = part["det_start"][p0], part["det_start"][p1], part["gt_start"][p0], part["gt_start"][p1]
+        ordered.append({"category": part["category"][p0:p1], "det_start": part["det_start"][p0:p1 + 1] - d0,
+                        "gt_start": part["gt_start"][p0:p1 + 1] - g0, "scores": part["scores"][d0:d1],
+                        "dt_match": part["dt_match"][:, :, d0:d1], "dt_ignore": part["dt_ignore"][:, :, d0:d1],
+                        "gt_ignore": part["gt_ignore"][:, g0:g1]})
+    return concatenate_tables(ordered)
+
+
+def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm"), device="cuda", recall=False):
+    """``evaluate_coco``'s numbers without gathering the predictions: ``local_predictions`` is THIS rank's {dataset index:
+    BoxList} (what ``engine.inference.compute_on_dataset`` returns), every rank calls this, rank 0 gets the OrderedDict and
+    the others None.  The ranks exchange their index lists; ``shard_owners`` says who scores an image that sits on two of
+    them, and the images of the annotation file that nobody predicted (those ``COCODataset`` drops are still scored) go
+    to rank 0 with zero detections.  Every rank then makes the detection rows of its images and scores them against their
+    ground truth on its own device (``_detections``, ``_score_rows``), and its match tables -- about 208 B per detection, not
+    the M x M maps -- go to rank 0 with the image id of every problem, where ``merge_shard_tables`` puts them into the order
+    ``match_tables`` has.  One process: the same code with one shard."""
+    device = _scoring_device(device, "evaluate_coco_sharded")
+    for iou_type in iou_types:
+        if iou_type not in ("bbox", "segm"):
+            raise ValueError(f"evaluate_coco_sharded: iou_type '{iou_type}' is not supported (bbox, segm)")
+    world, rank = comm.get_world_size(), comm.get_rank()
+    index_lists = [sorted(int(i) for i in local_predictions)]
+    if index_lists[0] and not 0 <= index_lists[0][0] <= index_lists[0][-1] < len(dataset):
+        raise ValueError(f"evaluate_coco_sharded: prediction indices {index_lists[0][0]} .. {index_lists[0][-1]} for a dataset "
+                         f"of {len(dataset)} images")
+    if world > 1:
+        mine, index_lists = index_lists[0], [None] * world
+        dist.all_gather_object(index_lists, mine)
+    owner_of_image = {dataset.id_to_img_map[idx]: r for idx, r in shard_owners(index_lists).items()}
+    ground_truth = _ground_truth(dataset)
+    cat_ids, images = ground_truth
+    cat_index = {c: i for i, c in enumerate(cat_ids)}
+    label_to_cat = {label: cat_index[json_id] for label, json_id in dataset.contiguous_category_id_to_json_id.items()}
+    images = [image for image in images if owner_of_image.get(image["id"], 0) == rank]  # in image-id order
+    by_image = {dataset.id_to_img_map[idx]: local_predictions[idx] for idx in index_lists[rank]}
+    merged = {}
+    with torch.cuda.device(device):
+        for iou_type in iou_types:
+            dets = [_detections(by_image.get(image["id"]), image, label_to_cat, iou_type == "segm") for image in images]
+            tables = _score_rows(images, dets, iou_type, device, None, None, None)
+            problems = np.asarray([len(np.union1d(det["cats"], image["cats"])) for image, det in zip(images, dets)],
+                                  dtype=np.int64)
+            tables["image"] = np.repeat(np.asarray([image["id"] for image in images], dtype=np.int64), problems)
+            parts = [tables]
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, tables)
+            if rank == 0:
+                merged[iou_type] = merge_shard_tables(parts)
+    if rank != 0:
+        return None
+    return _summaries(dataset, iou_types, device, lambda iou_type, gt: (merged[iou_type], cat_ids), recall, ground_truth)
 
 
 def annotation_dataset(ann_file):

@@ -3,8 +3,8 @@ DDP set-up of tools/train_net.py:43-126, rebuilt around ``BucketedGradReducer``.
 
 Only the step itself is here (forward -> sum of losses -> backward with overlapped all-reduce -> SGD ->
 LR schedule) plus rank-0 logging at LOG_PERIOD and the reference's checkpoint cadence (``model_<iter>.pth`` every
-CHECKPOINT_PERIOD, ``model_final.pth`` at the end: trainer.py:172-173, 252-253); periodic evaluation is outside the
-hot-path scope.
+CHECKPOINT_PERIOD, ``model_final.pth`` at the end: trainer.py:172-173, 252-253) and the call of an ``evaluator`` every
+TEST_PERIOD iterations (trainer.py:174-203; what it does is engine/evaluation.py's).
 """
 import logging
 import time
@@ -240,7 +240,12 @@ class PipelinedTrainer:
 
 
 def do_train(cfg, model, data_iter, optimizer, scheduler, max_iter, start_iter=0, log_period=None, logger=None,
-             checkpointer=None, checkpoint_period=None):
+             checkpointer=None, checkpoint_period=None, evaluator=None, test_period=0):
+    """``evaluator`` / ``test_period`` (SOLVER.TEST_PERIOD, trainer.py:174-203): ``evaluator(iteration)`` is called behind every
+    iteration whose number -- counted over the whole run, so a resumed run evaluates where the first would have -- is a multiple
+    of ``test_period``, after that iteration's checkpoint.  Any callable: the loop knows nothing about datasets.  It may put the
+    model into evaluation mode and give it other class embeddings as long as it puts both back
+    (engine/evaluation.py::evaluate_in_training)."""
     logger = logger or logging.getLogger("ovis.trainer")
     log_period = log_period or cfg.SOLVER.LOG_PERIOD
     model.train()
@@ -287,6 +292,13 @@ def do_train(cfg, model, data_iter, optimizer, scheduler, max_iter, start_iter=0
         if checkpointer is not None and checkpoint_period and (iteration + 1) % checkpoint_period == 0:
             pipe.drain()  # the look-ahead half holds no state, but the weights must be quiescent while they are read
             checkpointer.save("model_{:07d}".format(iteration + 1), iteration=iteration + 1)
+        if evaluator is not None and test_period > 0 and (iteration + 1) % test_period == 0:
+            # the look-ahead thread runs ``forward_frozen`` on this very model object: it has joined before the evaluator
+            # changes module modes and class embeddings.  Its outputs depend on frozen weights only and are kept.
+            pipe.drain()
+            began = time.time()
+            evaluator(iteration + 1)
+            last += time.time() - began  # the logged s/it stays the training loop's
     pipe.drain(discard=True)
     reducer.remove()
     if checkpointer is not None and completed > start_iter:

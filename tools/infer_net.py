@@ -28,11 +28,11 @@ views' detections; the saved BoxLists are in the first view's frame and keep the
 synthetic-stream tool; LVIS scoring is outside this build.
 """
 import argparse
-import json
+import json  # noqa: F401  (the module's names stay what they were before engine/evaluation.py took the functions)
 import logging
 import os
 import sys
-from collections import OrderedDict
+from collections import OrderedDict  # noqa: F401
 
 import torch
 import torch.distributed as dist
@@ -41,106 +41,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.data.build import build_dataset, make_data_loader  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.build import build_dataset, make_data_loader  # noqa: E402,F401
 from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402,F401
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem_bn, make_batch, make_embeddings  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, coco_results, comm, inference, proposal_recall, visualize  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402,F401
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, coco_results, comm, inference, proposal_recall, visualize  # noqa: E402,F401
+from cvpr22_cross_modal_pseudo_labeling_amd.engine.evaluation import (run_datasets, run_rpn_recall, save_evaluation,  # noqa: E402,F401
+                                                                       save_visualizations)
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
-
-
-def save_visualizations(dataset, predictions, folder, count, threshold, device):
-    """The first ``count`` images of ``dataset`` with their detections drawn (engine/visualize.py) -> ``folder``/<stem>.png."""
-    from PIL import Image
-
-    os.makedirs(folder, exist_ok=True)
-    unseen = [dataset.json_category_id_to_contiguous_id[c] for c in dataset.class_splits.get("unseen", [])]
-    for idx in range(min(count, len(predictions), len(dataset))):
-        image = dataset.original_image(idx)  # RGB, at its own size, before any transform
-        picture = visualize.render_predictions(image, predictions[idx].to(device), dataset.class_names, threshold=threshold,
-                                               unseen_labels=unseen)
-        stem = os.path.splitext(os.path.basename(dataset.get_img_info(idx)["file_name"]))[0]
-        Image.fromarray(picture).save(os.path.join(folder, stem + ".png"))
-
-
-def save_evaluation(dataset, predictions, folder, iou_types, device, logger, recall=False):
-    """COCO scoring of one test set (engine/coco_eval.py): the table goes to the log, the numbers to
-    ``folder``/coco_results.json as {iou_type: {metric: value}}.  ``recall``: the reference's whole table -- a
-    ``box_proposal`` task first (engine/proposal_recall.py: the detections scored as proposals by their ``scores``, which is
-    what the reference's table shows, its post-processor copying ``scores`` into ``objectness``), and the AR keys behind the
-    AP keys of every iou_type."""
-    if recall:
-        results = OrderedDict(box_proposal=proposal_recall.evaluate_box_proposals(dataset, predictions, device, "scores"))
-        results.update(coco_eval.evaluate_coco(dataset, predictions, iou_types, device, recall=True))
-    else:
-        results = coco_eval.evaluate_coco(dataset, predictions, iou_types, device)
-    logger.info(coco_eval.format_results(results))
-    with open(os.path.join(folder, "coco_results.json"), "w") as f:
-        json.dump(results, f, indent=1)
-    return results
-
-
-def run_rpn_recall(cfg, model, catalog, device, logger=None):
-    """Backbone + RPN alone over every DATASETS.TEST name (``model.propose``): the MODEL.RPN.POST_NMS_TOP_N_TEST proposals
-    of every image, gathered like detections and saved as ``<OUTPUT_DIR>/inference/<name>/proposals.pth``, and on rank 0
-    their box-proposal recall by ``objectness`` (engine/proposal_recall.py) as a ``rpn_proposal`` task in the log and in
-    ``rpn_recall.json`` -> {name: the numbers (rank 0) or None}."""
-    if not cfg.OUTPUT_DIR:
-        raise ValueError("run_rpn_recall writes OUTPUT_DIR/inference/<name>/proposals.pth and rpn_recall.json: set OUTPUT_DIR")
-    logger = logger or logging.getLogger("ovis.inference")
-    transform = build_transforms(cfg, is_train=False)
-    results = {}
-    for name in cfg.DATASETS.TEST:
-        dataset = build_dataset(cfg, name, catalog)
-        loader = make_data_loader(cfg, dataset, transform, False, comm.get_rank(), comm.get_world_size())
-        batches = DevicePrefetcher(loader, device, depth=2, transform=transform)
-        out = os.path.join(cfg.OUTPUT_DIR, "inference", name)
-        try:
-            proposals = inference.inference(model, batches, name, device, out, logger=logger, forward=model.propose,
-                                            file_name="proposals.pth")
-        finally:
-            batches.close()
-        results[name] = None
-        if proposals is not None:
-            results[name] = OrderedDict(rpn_proposal=proposal_recall.evaluate_box_proposals(dataset, proposals, device,
-                                                                                            "objectness"))
-            logger.info(coco_eval.format_results(results[name]))
-            with open(os.path.join(out, "rpn_recall.json"), "w") as f:
-                json.dump(results[name], f, indent=1)
-    return results
-
-
-def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
-                 export_results=False, recall=False):
-    """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}."""
-    transform = build_transforms(cfg, is_train=False)
-    results = {}
-    for name in cfg.DATASETS.TEST:
-        dataset = build_dataset(cfg, name, catalog)
-        loader = make_data_loader(cfg, dataset, transform, False, comm.get_rank(), comm.get_world_size())
-        batches = DevicePrefetcher(loader, device, depth=2, transform=transform)
-        out = os.path.join(cfg.OUTPUT_DIR, "inference", name) if cfg.OUTPUT_DIR else None
-        try:  # the zero-shot heads classify against THIS dataset's class embeddings
-            results[name] = inference.inference(model, batches, name, device, out,
-                                                class_embeddings=getattr(dataset, "class_emb_mtx", None), logger=logger)
-        finally:
-            batches.close()
-        if visualize_count > 0 and out and results[name] is not None:  # rank 0 only: the others got None
-            save_visualizations(dataset, results[name], os.path.join(out, "vis"), visualize_count, vis_threshold, device)
-        if evaluate and not out:
-            raise ValueError("run_datasets: evaluate=True writes OUTPUT_DIR/inference/<name>/coco_results.json: set OUTPUT_DIR")
-        if export_results and not out:
-            raise ValueError("run_datasets: export_results=True writes OUTPUT_DIR/inference/<name>/bbox.json and segm.json: "
-                             "set OUTPUT_DIR")
-        if evaluate and results[name] is not None:
-            save_evaluation(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",), device,
-                            logger or logging.getLogger("ovis.inference"), recall)
-        if export_results and results[name] is not None:
-            coco_results.export_coco_results(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",),
-                                             device)
-    return results
 
 
 def main(argv=None):

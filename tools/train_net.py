@@ -1,16 +1,31 @@
 """Training entry point with the reference's command line (tools/train_net.py:162-234):
 
-    python -m torch.distributed.run --nproc-per-node N tools/train_net.py --config-file CFG [--skip-test] KEY VALUE ...
+    python -m torch.distributed.run --nproc-per-node N tools/train_net.py --config-file CFG [--dataset-catalog FILE]
+        [--evaluate] [--skip-test] KEY VALUE ...
 
 One process per GPU (RCCL via torch.distributed, env:// rendezvous), config = defaults <- yaml <- trailing overrides,
 frozen before use.  Without ``--dataset-catalog`` the data stream is the synthetic COCO-shaped generator
 (cvpr22_cross_modal_pseudo_labeling_amd/data/synthetic.py); with it, DATASETS.TRAIN is read from the user's COCO-format
 files (data/catalog.py, data/datasets.py, data/build.py) through the raw input path.  MODEL.WEIGHT (a ``.pth`` in the reference's wire format),
 OUTPUT_DIR resume and SOLVER.CHECKPOINT_PERIOD behave as in the reference (utils/checkpoint.py: checkpoints are written and
-resumed from whenever OUTPUT_DIR is set; ``--no-checkpoints`` opts out); evaluation and
-TensorBoard are outside the hot-path scope.
+resumed from whenever OUTPUT_DIR is set; ``--no-checkpoints`` opts out).
+
+``--evaluate`` (with ``--dataset-catalog``, OUTPUT_DIR and MODEL.DEVICE cuda) is the reference's evaluation while training:
+behind every SOLVER.TEST_PERIOD-th iteration -- counted over the whole run, after that iteration's checkpoint -- every
+DATASETS.TEST set goes through the model as it stands and its COCO box AP (mask AP when MODEL.MASK_ON, AP50 per class and
+per seen / unseen split) is logged under the iteration and written to
+``OUTPUT_DIR/inference/<name>/coco_results_<iteration:07d>.json`` (engine/evaluation.py::evaluate_in_training,
+maskrcnn_benchmark/engine/trainer.py:174-203: every rank scores the images it predicted, nothing is saved but the numbers);
+and after the last iteration the final test (tools/train_net.py:129-159 of the reference), which is what
+``tools/infer_net.py --evaluate`` does with the final weights -- ``predictions.pth`` and ``coco_results.json`` under
+``OUTPUT_DIR/inference/<name>/`` -- unless ``--skip-test``.  Without ``--evaluate`` neither runs and ``--skip-test`` has
+nothing to skip.  The validation loss of the reference's loop is not computed (every shipped yaml sets
+SOLVER.SKIP_VAL_LOSS True; the reference's version runs the training forward, which moves the student-teacher model's
+iteration count), TEST.BBOX_AUG belongs to ``tools/infer_net.py``, and TensorBoard and best-checkpoint tracking are outside
+this build.
 """
 import argparse
+import functools
 import logging
 import os
 import sys
@@ -36,7 +51,7 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (LVIS_VOCAB, R
                                                                        SyntheticBatches, calibrate_stem_bn, make_batch,
                                                                        make_embeddings)
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, solver, trainer  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, evaluation, solver, trainer  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
@@ -59,10 +74,18 @@ def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter
 
 
 def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False, dataset_catalog=None,
-          data_dir="", seed=0):
+          data_dir="", seed=0, evaluate=False, skip_test=False):
+    """``evaluate``: score every DATASETS.TEST set behind every SOLVER.TEST_PERIOD-th iteration
+    (engine/evaluation.py::evaluate_in_training) and, unless ``skip_test``, run the final test behind the last one
+    (``evaluation.run_datasets``: predictions.pth and coco_results.json under OUTPUT_DIR/inference/<name>/)."""
+    if evaluate and not (dataset_catalog and cfg.OUTPUT_DIR and cfg.MODEL.DEVICE == "cuda"):
+        raise ValueError("train(evaluate=True) needs a dataset catalog (DATASETS.TEST), OUTPUT_DIR and MODEL.DEVICE cuda")
+    if evaluate and cfg.TEST.BBOX_AUG.ENABLED:
+        raise ValueError("train(evaluate=True) scores one view per image: set TEST.BBOX_AUG.ENABLED False")
     device = torch.device(cfg.MODEL.DEVICE, local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
     model = build_detection_model(cfg).to(device)
-    dataset = build_train_dataset(cfg, DatasetCatalog(dataset_catalog, data_dir)) if dataset_catalog else None
+    catalog = DatasetCatalog(dataset_catalog, data_dir) if dataset_catalog else None
+    dataset = build_train_dataset(cfg, catalog) if catalog is not None else None
     # the caption-vocabulary matrix stays the seeded stand-in: as many rows as the dataset's vocabulary when that is larger
     n_vocab = max(LVIS_VOCAB, len(dataset.parser.class_names) if getattr(dataset, "parser", None) else 0)
     e_vocab, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device, n_vocab=n_vocab)
@@ -99,19 +122,38 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
     if not cfg.MODEL.WEIGHT and not checkpointer.has_checkpoint():  # random init only: give the frozen BN usable statistics
         images, _ = make_batch(1, device=device, seed=7)
         calibrate_stem_bn(model, images)
+    evaluator = None
+    if evaluate:
+        logger = logging.getLogger("ovis.trainer")
+        if not cfg.SOLVER.SKIP_VAL_LOSS:
+            logger.info("SOLVER.SKIP_VAL_LOSS False: the validation loss is not computed, --evaluate scores AP only")
+        evaluator = functools.partial(evaluation.evaluate_in_training, cfg, model, catalog, device,
+                                      train_class_embeddings=e_seen, logger=logger)
     try:
-        return trainer.do_train(cfg, model, data, optimizer, scheduler, max_iter, start_iter=start_iter,
-                                checkpointer=checkpointer if save_checkpoints else None,
-                                checkpoint_period=cfg.SOLVER.CHECKPOINT_PERIOD)
+        history = trainer.do_train(cfg, model, data, optimizer, scheduler, max_iter, start_iter=start_iter,
+                                   checkpointer=checkpointer if save_checkpoints else None,
+                                   checkpoint_period=cfg.SOLVER.CHECKPOINT_PERIOD, evaluator=evaluator,
+                                   test_period=cfg.SOLVER.TEST_PERIOD if evaluate else 0)
     finally:
         data.close()
+    if evaluate and not skip_test:  # tools/train_net.py:129-159: the final test, the route of tools/infer_net.py --evaluate
+        comm.synchronize()
+        evaluation.run_datasets(cfg, model, catalog, device, logging.getLogger("ovis.inference"), evaluate=True)
+        comm.synchronize()
+    return history
 
 
-def main():
+def main(argv=None):
     parser = argparse.ArgumentParser(description="MI355X-native detection training (synthetic data)")
     parser.add_argument("--config-file", default="", metavar="FILE", help="path to config file")
     parser.add_argument("--local_rank", type=int, default=int(os.environ.get("LOCAL_RANK", 0)))
-    parser.add_argument("--skip-test", dest="skip_test", action="store_true", help="accepted for compatibility")
+    parser.add_argument("--skip-test", dest="skip_test", action="store_true",
+                        help="with --evaluate: do not run the final test behind the last iteration")
+    parser.add_argument("--evaluate", action="store_true",
+                        help="score every DATASETS.TEST set on the device behind every SOLVER.TEST_PERIOD-th iteration (COCO box / "
+                             "mask AP, AP50 per class and split -> OUTPUT_DIR/inference/<name>/coco_results_<iteration>.json) and "
+                             "run the final test behind the last one (predictions.pth, coco_results.json); needs "
+                             "--dataset-catalog, OUTPUT_DIR and MODEL.DEVICE cuda")
     parser.add_argument("--max-iter", type=int, default=None, help="override SOLVER.MAX_ITER for a short run")
     parser.add_argument("--no-checkpoints", action="store_true",
                         help="do not write model_<iter>.pth / model_final.pth / last_checkpoint under OUTPUT_DIR and do not "
@@ -128,7 +170,7 @@ def main():
     parser.add_argument("--seed", type=int, default=0,
                         help="with --dataset-catalog: the run's seed of the input transform's random draws (sizes, flips)")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
-    args = parser.parse_args()
+    args = parser.parse_args(argv)
 
     num_gpus = int(os.environ.get("WORLD_SIZE", 1))
     distributed = num_gpus > 1
@@ -137,6 +179,16 @@ def main():
         cfg.merge_from_file(args.config_file)
     cfg.merge_from_list(args.opts or [])
     cfg.freeze()
+    if args.evaluate and not args.dataset_catalog:
+        parser.error("--evaluate runs the DATASETS.TEST sets of the catalog through the model: give --dataset-catalog")
+    if args.evaluate and not cfg.OUTPUT_DIR:
+        parser.error("--evaluate writes OUTPUT_DIR/inference/<name>/coco_results_<iteration>.json: set OUTPUT_DIR")
+    if args.evaluate and cfg.MODEL.DEVICE != "cuda":
+        parser.error("--evaluate scores on the HIP device (mask IoU and matching have no host implementation): "
+                     "set MODEL.DEVICE cuda")
+    if args.evaluate and cfg.TEST.BBOX_AUG.ENABLED:
+        parser.error("--evaluate scores one view per image while training: set TEST.BBOX_AUG.ENABLED False "
+                     "(tools/infer_net.py runs multi-scale / flip testing on a checkpoint)")
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
         # The training process does almost no CPU math, but every multi-threaded host op (a staging memcpy, a reduction over a
@@ -158,7 +210,8 @@ def main():
                                            cfg.SOLVER.IMS_PER_BATCH, num_gpus)
     train(cfg, args.local_rank, distributed, args.max_iter or cfg.SOLVER.MAX_ITER, ims_per_gpu,
           save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input,
-          dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed)
+          dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed, evaluate=args.evaluate,
+          skip_test=args.skip_test)
     if distributed:
         dist.destroy_process_group()
 
