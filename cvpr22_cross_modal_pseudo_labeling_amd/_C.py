@@ -786,6 +786,53 @@ def sample_fg_bg(labels, batch_size, max_positives, seed):
     return sel, slots, counts
 
 
+BRANCH_ROI_UNION_MAX_IMAGES = _lib.OVIS_BOX_DECODE_MAX_IMAGES  # the per-image pointers travel as kernel arguments
+
+
+def branch_roi_union(branch0, branch1, image_ids=None):
+    """Union of the RoIs two branches sampled from proposal lists of the same images (``ovis_branch_roi_union``), one
+    launch, nothing read back.  ``branch0`` / ``branch1``: per image a tuple (boxes [P, 4] float32, selected, positive_slots,
+    counts) -- the image's proposals and what ``sample_fg_bg`` returned for them.  A branch-1 row whose four box words equal
+    a branch-0 row's of the same image (bit patterns) shares that row; the others follow all branch-0 rows.
+    -> (rois [R, 5]: the union rows' RoIs, R = images * (batch0 + batch1) rounded up to 32, rows behind the union copies of
+    its last row; map1 [images * batch1] int64: union row of every branch-1 row, dense; positive_rows int64: ascending union
+    rows positive in either branch; slots0, slots1: each branch's positives as positions in ``positive_rows``;
+    counts [images, 2] int32: (new rows, entries of positive_rows) per image)."""
+    n = len(branch0)
+    if n == 0 or len(branch1) != n:
+        raise RuntimeError("branch_roi_union: the same, non-zero number of images expected in both branches")
+    cols = []
+    for name, branch in (("branch0", branch0), ("branch1", branch1)):
+        boxes = [_dev(b[0], f"{name} boxes") for b in branch]
+        sel = [_dev(b[1], f"{name} selected", torch.int64) for b in branch]
+        slots = [_dev(b[2], f"{name} positive_slots", torch.int64) for b in branch]
+        counts = [_dev(b[3], f"{name} counts", torch.int32) for b in branch]
+        batch = sel[0].numel()
+        if any(b.dim() != 2 or b.shape[1] != 4 for b in boxes) or any(c.numel() != 2 for c in counts) \
+                or any(s.numel() != batch for s in sel + slots) or batch == 0:
+            raise RuntimeError(f"branch_roi_union: {name}: [P, 4] boxes, equally long selected / positive_slots and [2] counts expected")
+        cols.append((boxes, sel, slots, counts, batch))
+    dev = cols[0][0][0].device
+    b0, b1 = cols[0][4], cols[1][4]
+    rows = -(-n * (b0 + b1) // 32) * 32
+    rois = torch.empty((rows, 5), dtype=torch.float32, device=dev)
+    i64 = torch.empty((n * (2 * b0 + 3 * b1),), dtype=torch.int64, device=dev)
+    map1, positive_rows, slots0, slots1 = i64.split([n * b1, n * (b0 + b1), n * b0, n * b1])
+    i32 = torch.empty((b0 + 2 * n,), dtype=torch.int32, device=dev)
+
+    def table(tensors, ctype=ctypes.c_void_p):
+        return (ctype * n)(*[t.data_ptr() if t.numel() else None for t in tensors])
+    args = []
+    for boxes, sel, slots, counts, _ in cols:
+        args += [table(boxes), (ctypes.c_int32 * n)(*[b.shape[0] for b in boxes]), table(sel), table(slots), table(counts)]
+    ids = None if image_ids is None else (ctypes.c_int32 * n)(*[int(i) for i in image_ids])
+    with _on(dev):
+        rc = _L.ovis_branch_roi_union(*args, ids, n, b0, b1, rois.data_ptr(), rows, map1.data_ptr(), positive_rows.data_ptr(),
+                                      slots0.data_ptr(), slots1.data_ptr(), i32.data_ptr(), i32[b0:].data_ptr(), _stream())
+    _lib.check(rc, "branch_roi_union")
+    return rois, map1, positive_rows, slots0, slots1, i32[b0:].view(n, 2)
+
+
 def gather_rows(index, boxes_a=None, boxes_b=None, ints_a=None, ints_b=None):
     """``x.index_select(0, index)`` for up to two [P, 4] float32 and two [P] int64 tensors in one launch
     (``ovis_gather_rows``) -> tuple of the gathered tensors (None where the source is None)."""

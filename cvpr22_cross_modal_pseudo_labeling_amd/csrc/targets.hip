@@ -19,6 +19,9 @@
 //                  labels' masks (st_generalized_rcnn.py:266-271).  A pixel of the full-resolution binary mask the
 //                  reference builds with Masker (mask_head/inference.py:100-160: pad by 1, expand the box, bilinear
 //                  resize to the integer box, > 0.5, paste) is evaluated on the fly, so the H x W canvases never exist.
+//   branch_roi_union: the RoIs two branches sampled from lists of the same images, each distinct box once (the student's
+//                  pseudo-label and ground-truth branches, st_generalized_rcnn.py:284-408, share one pooler + res5 pass):
+//                  row maps, RoI rows and the positives' list in ONE launch in front of the sampler's one host read.
 #include "ovis_common.h"
 #define OVIS_HD __device__ __forceinline__
 #include "mask_crop_geom.h"
@@ -469,7 +472,272 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const long long* __res
   if (ib) ib_out[i] = ib[r];
 }
 
+// ---- union of two branches' sampled RoIs ----------------------------------------------------------------------------------
+// The student's two branches sample their RoIs from proposal lists that come out of one decode + NMS pass, so many rows
+// are the same box in both.  The union lists every branch-0 row (today's order) and behind them the branch-1 rows that no
+// branch-0 row of the same image equals bit for bit; the pooler and the res5 head then run once per union row.
+constexpr int kUnionStage = 512;  // rows of a sampled list staged in LDS at a time (longer lists: a loop of stages)
+
+struct UnionImages {  // per image: the two branches' proposals and sampler outputs (device pointers; counts stay on the device)
+  int count;
+  int image_id[OVIS_BOX_DECODE_MAX_IMAGES];
+  int num[2][OVIS_BOX_DECODE_MAX_IMAGES];  // proposals of the branch
+  const float* boxes[2][OVIS_BOX_DECODE_MAX_IMAGES];
+  const long* selected[2][OVIS_BOX_DECODE_MAX_IMAGES];
+  const long* slots[2][OVIS_BOX_DECODE_MAX_IMAGES];
+  const int* counts[2][OVIS_BOX_DECODE_MAX_IMAGES];
+};
+
+__device__ __forceinline__ unsigned union_hash(uint4 b) {
+  return b.x ^ ((b.y << 8) | (b.y >> 24)) ^ ((b.z << 16) | (b.z >> 16)) ^ ((b.w << 24) | (b.w >> 8));
+}
+
+// box of sampled row r: boxes[selected[r]], the index clamped into the P proposals (P >= 1)
+__device__ __forceinline__ uint4 union_box(const float* __restrict__ boxes, const long* __restrict__ selected, int r, int P) {
+  long s = selected[r];
+  s = s < 0 ? 0 : (s >= P ? P - 1 : s);
+  return *(const uint4*)(boxes + 4 * s);
+}
+
+__device__ __forceinline__ void union_write_roi(float* __restrict__ rois, long row, int id, uint4 b) {
+  float* o = rois + 5 * row;
+  o[0] = (float)id;
+  o[1] = __uint_as_float(b.x);
+  o[2] = __uint_as_float(b.y);
+  o[3] = __uint_as_float(b.z);
+  o[4] = __uint_as_float(b.w);
+}
+
+// Lowest r in [0, n) whose sampled box has the four words of `mine` (n: none).  EVERY thread of the workgroup calls it with
+// the same list (it stages the list through LDS between barriers); threads with active == false only help staging.  A 32-bit
+// hash per row is compared first, four rows per LDS read; the boxes themselves only where it hits.
+__device__ int union_first_equal(const float* __restrict__ boxes, const long* __restrict__ selected, int n, int P, uint4 mine,
+                                 bool active, uint4* sbox, unsigned* shash) {
+  const unsigned mh = union_hash(mine);
+  int first = n;
+  for (int s = 0; s < n; s += kUnionStage) {
+    const int cnt = min(kUnionStage, n - s);
+    __syncthreads();  // the previous stage (of this or an earlier call) has been read
+    for (int r = threadIdx.x; r < kUnionStage; r += kSampThreads) {
+      if (r < cnt) {
+        const uint4 b = union_box(boxes, selected, s + r, P);
+        sbox[r] = b;
+        shash[r] = union_hash(b);
+      } else {
+        shash[r] = 0u;  // read in groups of four; a hit behind cnt is refused below
+      }
+    }
+    __syncthreads();
+    if (active && first == n) {
+      for (int g = 0; g < cnt && first == n; g += 4) {
+        const uint4 h = *(const uint4*)(shash + g);
+        if (h.x == mh || h.y == mh || h.z == mh || h.w == mh) {
+          const unsigned hh[4] = {h.x, h.y, h.z, h.w};
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int r = g + u;
+            if (first == n && r < cnt && hh[u] == mh) {
+              const uint4 b = sbox[r];
+              if (b.x == mine.x && b.y == mine.y && b.z == mine.z && b.w == mine.w) first = s + r;
+            }
+          }
+        }
+      }
+    }
+  }
+  return first;
+}
+
+// ONE workgroup, the images in turn (the union's row numbers run across images).  Order of every output = order of the
+// inputs, fixed by block scans: no atomics, the same words on every call.  n / npos are the device counts clipped to the
+// buffer lengths, slots outside [0, n) are skipped, proposal indices are clamped: no access leaves a buffer.
+__global__ __launch_bounds__(kSampThreads) void branch_roi_union_kernel(UnionImages in, int batch0, int batch1,
+                                                                        float* __restrict__ rois, int rois_rows,
+                                                                        long* __restrict__ map1, long* __restrict__ pos_rows,
+                                                                        long* __restrict__ slots0_out,
+                                                                        long* __restrict__ slots1_out, int* __restrict__ mark,
+                                                                        int* __restrict__ out_counts) {
+  __shared__ uint4 sbox[kUnionStage];
+  __shared__ __attribute__((aligned(16))) unsigned shash[kUnionStage];
+  __shared__ int sh[kSampThreads / 64];
+  __shared__ int ns[2][OVIS_BOX_DECODE_MAX_IMAGES], ps[2][OVIS_BOX_DECODE_MAX_IMAGES];
+  __shared__ int new_rows[OVIS_BOX_DECODE_MAX_IMAGES], len_a[OVIS_BOX_DECODE_MAX_IMAGES];
+  const int tid = threadIdx.x;
+  if (tid < 2 * in.count) {
+    const int b = tid & 1, img = tid >> 1;
+    const int cap = b ? batch1 : batch0;
+    int n = in.counts[b][img][0], p = in.counts[b][img][1];
+    n = in.num[b][img] > 0 ? max(0, min(n, cap)) : 0;
+    ns[b][img] = n;
+    ps[b][img] = max(0, min(p, n));
+  }
+  __syncthreads();
+  int total0 = 0;
+  for (int img = 0; img < in.count; ++img) total0 += ns[0][img];
+  int base0 = 0, base1 = 0, new_base = 0, a_base = 0, ps0 = 0, ps1 = 0;
+  for (int img = 0; img < in.count; ++img) {
+    const int n0 = ns[0][img], n1 = ns[1][img], p0 = ps[0][img], p1 = ps[1][img], id = in.image_id[img];
+    const int P0 = in.num[0][img], P1 = in.num[1][img];
+    const float* boxes0 = in.boxes[0][img];
+    const float* boxes1 = in.boxes[1][img];
+    const long *sel0 = in.selected[0][img], *sel1 = in.selected[1][img];
+    const long *slots0 = in.slots[0][img], *slots1 = in.slots[1][img];
+    for (int r = tid; r < n0; r += kSampThreads) union_write_roi(rois, base0 + r, id, union_box(boxes0, sel0, r, P0));
+    // branch-1 row j is the branch-0 row i when i is the lowest row with its box and no earlier branch-1 row has that box
+    int img_new = 0;
+    for (int jb = 0; jb < n1; jb += kSampThreads) {
+      const int j = jb + tid;
+      const bool active = j < n1;
+      const uint4 mine = active ? union_box(boxes1, sel1, j, P1) : make_uint4(0u, 0u, 0u, 0u);
+      const int i = union_first_equal(boxes0, sel0, n0, P0, mine, active, sbox, shash);
+      const int upto = min(n1, jb + kSampThreads);
+      const int j_first = union_first_equal(boxes1, sel1, upto, P1, mine, active, sbox, shash);  // <= j: the row finds itself
+      const bool matched = active && i < n0 && j_first == j;
+      int tot;
+      const int k = block_exscan(active && !matched ? 1 : 0, sh, &tot);
+      if (active) {
+        const long u = matched ? (long)(base0 + i) : (long)(total0 + new_base + img_new + k);
+        map1[base1 + j] = u;
+        if (!matched) union_write_roi(rois, u, id, mine);
+      }
+      img_new += tot;
+    }
+    // union rows below total0 that are positive in either branch: ascending into pos_rows, their list position into mark
+    for (int r = tid; r < n0; r += kSampThreads) mark[r] = 0;
+    __syncthreads();  // mark cleared; map1 of this image written
+    for (int t = tid; t < p0; t += kSampThreads) {
+      const long s = slots0[t];
+      if (s >= 0 && s < n0) mark[s] = 1;
+    }
+    for (int t = tid; t < p1; t += kSampThreads) {
+      const long j = slots1[t];
+      if (j >= 0 && j < n1) {
+        const long u = map1[base1 + j];
+        if (u < total0) mark[u - base0] = 1;
+      }
+    }
+    __syncthreads();
+    int la = 0;
+    for (int rb = 0; rb < n0; rb += kSampThreads) {
+      const int r = rb + tid;
+      const bool f = r < n0 && mark[r] != 0;
+      int tot;
+      const int k = block_exscan(f ? 1 : 0, sh, &tot);
+      if (f) {
+        pos_rows[a_base + la + k] = base0 + r;
+        mark[r] = a_base + la + k + 1;
+      }
+      la += tot;
+    }
+    __syncthreads();
+    for (int t = tid; t < p0; t += kSampThreads) {
+      const long s = slots0[t];
+      slots0_out[ps0 + t] = (s >= 0 && s < n0) ? mark[s] - 1 : 0;
+    }
+    for (int t = tid; t < p1; t += kSampThreads) {
+      const long j = slots1[t];
+      long at = 0;
+      if (j >= 0 && j < n1) {
+        const long u = map1[base1 + j];
+        if (u < total0) at = mark[u - base0] - 1;
+      }
+      slots1_out[ps1 + t] = at;  // positives on new rows: second pass
+    }
+    if (tid == 0) {
+      new_rows[img] = img_new;
+      len_a[img] = la;
+    }
+    __syncthreads();  // mark is cleared again for the next image
+    base0 += n0;
+    base1 += n1;
+    new_base += img_new;
+    a_base += la;
+    ps0 += p0;
+    ps1 += p1;
+  }
+  // positives of branch 1 on new rows follow every row below total0, in their order
+  int b_base = a_base;
+  base1 = 0;
+  ps1 = 0;
+  for (int img = 0; img < in.count; ++img) {
+    const int n1 = ns[1][img], p1 = ps[1][img];
+    const long* slots1 = in.slots[1][img];
+    int lb = 0;
+    for (int tb = 0; tb < p1; tb += kSampThreads) {
+      const int t = tb + tid;
+      long u = 0;
+      bool f = false;
+      if (t < p1) {
+        const long j = slots1[t];
+        if (j >= 0 && j < n1) {
+          u = map1[base1 + j];
+          f = u >= total0;
+        }
+      }
+      int tot;
+      const int k = block_exscan(f ? 1 : 0, sh, &tot);
+      if (f) {
+        pos_rows[b_base + lb + k] = u;
+        slots1_out[ps1 + t] = b_base + lb + k;
+      }
+      lb += tot;
+    }
+    if (tid == 0) {
+      out_counts[2 * img] = new_rows[img];
+      out_counts[2 * img + 1] = len_a[img] + lb;
+    }
+    b_base += lb;
+    base1 += n1;
+    ps1 += p1;
+  }
+  // rows behind the union: copies of its last row (the caller rounds the RoI count up; nothing indexes them)
+  const int rows = total0 + new_base;
+  __syncthreads();
+  for (int r = rows + tid; r < rois_rows; r += kSampThreads) {
+#pragma unroll
+    for (int c = 0; c < 5; ++c) rois[5 * (long)r + c] = rows > 0 ? rois[5 * (long)(rows - 1) + c] : (c == 0 ? (float)in.image_id[0] : 0.f);
+  }
+}
+
 }  // namespace
+
+extern "C" int ovis_branch_roi_union(const float* const* boxes0, const int32_t* num0, const int64_t* const* selected0,
+                                     const int64_t* const* positive_slots0, const int32_t* const* counts0,
+                                     const float* const* boxes1, const int32_t* num1, const int64_t* const* selected1,
+                                     const int64_t* const* positive_slots1, const int32_t* const* counts1,
+                                     const int32_t* image_ids, int num_images, int batch0, int batch1, float* rois,
+                                     int rois_rows, int64_t* map1, int64_t* positive_rows, int64_t* slots0, int64_t* slots1,
+                                     int32_t* workspace, int32_t* out_counts, void* stream) {
+  if (num_images <= 0 || batch0 <= 0 || batch1 <= 0) return OVIS_EINVAL;
+  if (num_images > OVIS_BOX_DECODE_MAX_IMAGES || (long)num_images * ((long)batch0 + batch1) > (1L << 26)) return OVIS_ERANGE;
+  if (rois_rows < (long)num_images * ((long)batch0 + batch1)) return OVIS_ENOSPC;
+  if (!boxes0 || !num0 || !selected0 || !positive_slots0 || !counts0 || !boxes1 || !num1 || !selected1 || !positive_slots1 ||
+      !counts1 || !rois || !map1 || !positive_rows || !slots0 || !slots1 || !workspace || !out_counts)
+    return OVIS_EINVAL;
+  UnionImages in;
+  in.count = num_images;
+  for (int i = 0; i < num_images; ++i) {
+    const float* bx[2] = {boxes0[i], boxes1[i]};
+    const int nb[2] = {num0[i], num1[i]};
+    const int64_t* se[2] = {selected0[i], selected1[i]};
+    const int64_t* sl[2] = {positive_slots0[i], positive_slots1[i]};
+    const int32_t* ct[2] = {counts0[i], counts1[i]};
+    for (int b = 0; b < 2; ++b) {
+      if (nb[b] < 0 || (nb[b] > 0 && !bx[b]) || !se[b] || !sl[b] || !ct[b]) return OVIS_EINVAL;
+      if ((uintptr_t)bx[b] & 15) return OVIS_ERANGE;
+      in.num[b][i] = nb[b];
+      in.boxes[b][i] = bx[b];
+      in.selected[b][i] = (const long*)se[b];
+      in.slots[b][i] = (const long*)sl[b];
+      in.counts[b][i] = ct[b];
+    }
+    in.image_id[i] = image_ids ? image_ids[i] : i;
+  }
+  hipLaunchKernelGGL(branch_roi_union_kernel, dim3(1), dim3(kSampThreads), 0, (hipStream_t)stream, in, batch0, batch1, rois,
+                     rois_rows, (long*)map1, (long*)positive_rows, (long*)slots0, (long*)slots1, workspace, out_counts);
+  OVIS_LAUNCH_CHECK();
+  return OVIS_OK;
+}
 
 extern "C" int ovis_sample_fg_bg(const int64_t* labels, int num, int batch_size, int max_positives, uint64_t seed,
                                  int64_t* selected, int64_t* positive_slots, int32_t* counts, void* stream) {

@@ -152,6 +152,11 @@ class PipelinedTrainer:
         self.model, self.optimizer, self.reducer, self.scheduler = model, optimizer, reducer, scheduler
         self.policy = policy or StepPolicy()
         self.enabled = hasattr(model, "forward_frozen") and torch.cuda.is_available()
+        # training pools the RoIs that both student branches drew once (roi_heads.py::CombinedROIHeads.share_branch_rois:
+        # about 13 % of the res5 head's rows at the shipped sizes); pipelined or not, this object drives every training loop
+        student_heads = getattr(model, "roi_heads_student", None)
+        if hasattr(student_heads, "share_branch_rois"):
+            student_heads.share_branch_rois = True
         # The look-ahead half must not read anything the optimizer writes: with MODEL.LANGUAGE_BACKBONE.FT_EMB the BERT
         # table is trained AND read by the frozen half's noun embeddings (st_generalized_rcnn.py:242) -- the side stream
         # would read it while optimizer.step() writes it.  Run such models un-pipelined.

@@ -19,6 +19,7 @@ device instead of a hard-coded ``.cuda()``, and the mask head handle
 images per process.
 """
 import bisect
+from collections import namedtuple
 
 import torch
 import torch.nn.functional as F
@@ -36,6 +37,13 @@ from .structures import BoxList, PastedMasks, PolygonMasks, RleMasks, SampledBox
 
 def _cat(tensors, dim=0):
     return tensors[0] if len(tensors) == 1 else torch.cat(tensors, dim)
+
+
+# The sampled RoIs of two branches over the same images, each distinct box once (``_C.branch_roi_union``): ``rois`` [R, 5]
+# (R a multiple of 32; rows behind the union repeat its last RoI), branch 0 = union rows [0, rows0), branch 1 = rows
+# ``map1``; ``positive_rows``: ascending union rows positive in either branch, ``slots0`` / ``slots1``: each branch's
+# positives as positions in it.
+BranchRoiUnion = namedtuple("BranchRoiUnion", "rois rows0 map1 positive_rows slots0 slots1")
 
 
 class Pooler(nn.Module):
@@ -202,9 +210,15 @@ class FastRCNNLossComputation:
         ONE copy; the sampled lists (``SampledBoxList``) carry ``pos_index`` (where the positives sit), so neither the box
         loss nor the mask head runs a ``nonzero``.  The reference's sequence (box_head/loss.py:89-123: IoU matrix, Matcher, randperm
         sampler, boolean indexing: ~60 launches and 3 host syncs per image) serves CPU tensors."""
+        return self.subsample_branches(groups)[0]
+
+    def subsample_branches(self, groups, union_image_ids=None):
+        """``subsample_many`` -> (sampled lists per group, union).  ``union_image_ids`` (two groups over the same images,
+        on the device): the union of the two groups' sampled RoIs (``_C.branch_roi_union``) is built in front of the one
+        host read, which then also brings its sizes -> ``BranchRoiUnion``; None otherwise."""
         if not all(p.bbox.is_cuda for props, _ in groups for p in props) or self.matcher.allow_low_quality_matches \
                 or not self.device_sampler:
-            return [self._subsample_tensor_ops(props, tgts) for props, tgts in groups]
+            return [self._subsample_tensor_ops(props, tgts) for props, tgts in groups], None
         pending = []
         for props, tgts in groups:
             for prop, tgt in zip(props, tgts):
@@ -212,7 +226,24 @@ class FastRCNNLossComputation:
                                                    self.matcher.low_threshold, self.box_coder.weights)
                 sel, slots, counts = self.sampler.sample_device(labels, self.generator)
                 pending.append((prop, idx, labels, reg, sel, slots, counts))
-        cnt = torch.stack([p[-1] for p in pending]).tolist() if pending else []  # the one host read
+        union, count_rows = None, [p[-1] for p in pending]
+        n_img = len(groups[0][0]) if groups else 0
+        if union_image_ids is not None and len(groups) == 2 and len(groups[1][0]) == n_img == len(union_image_ids) \
+                and 0 < n_img <= _C.BRANCH_ROI_UNION_MAX_IMAGES:
+            union = _C.branch_roi_union(*([(p[0].bbox, p[4], p[5], p[6]) for p in pending[b * n_img:(b + 1) * n_img]]
+                                          for b in (0, 1)), union_image_ids)
+            count_rows = count_rows + list(union[5].unbind(0))
+        cnt = torch.stack(count_rows).tolist() if pending else []  # the one host read
+        if union is not None:
+            rois, map1, positive_rows, slots0, slots1, _ = union
+            own, extra = cnt[:len(pending)], cnt[len(pending):]
+            rows0 = sum(c[0] for c in own[:n_img])
+            rows = rows0 + sum(e[0] for e in extra)
+            # a multiple of 32 RoIs, so that the head's buffers do not change size with every draw; the rows behind the
+            # union repeat its last RoI and nothing indexes them
+            union = BranchRoiUnion(rois[:-(-rows // 32) * 32], rows0, map1[:sum(c[0] for c in own[n_img:])],
+                                   positive_rows[:sum(e[1] for e in extra)], slots0[:sum(c[1] for c in own[:n_img])],
+                                   slots1[:sum(c[1] for c in own[n_img:])])
         out, k = [], 0
         for props, _ in groups:
             group = []
@@ -228,7 +259,7 @@ class FastRCNNLossComputation:
                 group.append(SampledBoxList(b, slots[:npos]))
             out.append(group)
         self._proposals = out[-1]
-        return out
+        return out, union
 
     def _subsample_tensor_ops(self, proposals, targets):
         out = []
@@ -895,6 +926,10 @@ class ROIMaskHead(nn.Module):
 
 class CombinedROIHeads(nn.ModuleDict):
     batch_branches = True  # False = one head pass per branch, the reference's order (cross-check in tests/test_model_gpu.py)
+    # True = the batched pass pools a RoI that both branches drew once (``_C.branch_roi_union``).  The training loops turn it
+    # on (engine/trainer.py::PipelinedTrainer); a bare ``forward_student`` keeps a row per branch, branch after branch -- the
+    # row layout that replays of the batched pass (tests/gate_forcing.py) and the cross-checks read
+    share_branch_rois = False
 
     def __init__(self, cfg, in_channels, is_teacher=False):
         heads = [("box", ROIBoxHead(cfg, in_channels, is_teacher))]
@@ -919,20 +954,33 @@ class CombinedROIHeads(nn.ModuleDict):
         branch -- the values the sequential calls give (same sampling order), with half the launches and GEMMs of twice
         the height."""
         box = self.box
+        # two branches over the same images draw many of their RoIs from the same boxes (the student's proposal lists come
+        # out of one decode + NMS pass): the pooler and res5 run once per distinct RoI, each branch indexes its rows
+        share = (self.share_branch_rois and len(branches) == 2
+                 and list(branches[0]["image_ids"]) == list(branches[1]["image_ids"]))
         with torch.no_grad():
-            sampled = box.loss_evaluator.subsample_many([(br["proposals"], br["targets"]) for br in branches])
-        rois = _C.rois_from_boxes([p.bbox for props in sampled for p in props],
-                                  [img for br in branches for img in br["image_ids"]])  # RoIs of every branch, one launch
-        # the mask head reads the res5 features of the positive RoIs only: their indices are known from the sampled lists,
-        # so the last res5 block hands those maps out itself (their gradient then enters its backward as dense maps
-        # instead of being scattered into a zero tensor of all RoIs first)
-        sel_pos = positives_index([p for props in sampled for p in props]) if self.mask_on else None
+            sampled, union = box.loss_evaluator.subsample_branches([(br["proposals"], br["targets"]) for br in branches],
+                                                                   list(branches[0]["image_ids"]) if share else None)
+        if union is not None:
+            rois = union.rois
+            sel_pos = union.positive_rows if self.mask_on else None
+        else:
+            rois = _C.rois_from_boxes([p.bbox for props in sampled for p in props],
+                                      [img for br in branches for img in br["image_ids"]])  # RoIs of every branch, one launch
+            # the mask head reads the res5 features of the positive RoIs only: their indices are known from the sampled
+            # lists, so the last res5 block hands those maps out itself (their gradient then enters its backward as dense
+            # maps instead of being scattered into a zero tensor of all RoIs first)
+            sel_pos = positives_index([p for props in sampled for p in props]) if self.mask_on else None
         x, pooled, handed = box.feature_extractor.forward_rois([feat], rois, select=sel_pos)
         pooled = box.predictor.pooled(pooled if pooled is not None else x)
         counts = [sum(len(p) for p in props) for props in sampled]
         out, off = [], 0
-        for br, props, cnt in zip(branches, sampled, counts):
-            class_logits, box_regression = box.predictor(pooled[off:off + cnt], br["cls_embs"])
+        for b, (br, props, cnt) in enumerate(zip(branches, sampled, counts)):
+            if union is None:
+                rows = pooled[off:off + cnt]
+            else:  # unique indices: the backward of the gather is an assignment, autograd adds the two branches' gradients
+                rows = pooled[:cnt] if b == 0 else pooled.index_select(0, union.map1)
+            class_logits, box_regression = box.predictor(rows, br["cls_embs"])
             lc, lb = box.loss_evaluator(class_logits, box_regression, props)
             out.append(dict(loss_classifier=lc, loss_box_reg=lb))
             off += cnt
@@ -951,9 +999,11 @@ class CombinedROIHeads(nn.ModuleDict):
             else:
                 xs = fl[sel].permute(0, 3, 1, 2) if (fl.is_contiguous() and not x.is_contiguous()) else x[sel]  # ONE index op
             off = 0
-            for br, pos_props, losses in zip(branches, pos_all, out):
+            for b, (br, pos_props, losses) in enumerate(zip(branches, pos_all, out)):
                 k = sum(len(p) for p in pos_props)
-                losses["loss_mask"] = mask.fused_training_loss(xs[off:off + k], pos_props, br["targets"],
+                # union: ``xs`` holds each positive union row once, a branch takes its own (unique slots, in its order)
+                xb = xs[off:off + k] if union is None else xs.index_select(0, union.slots1 if b else union.slots0)
+                losses["loss_mask"] = mask.fused_training_loss(xb, pos_props, br["targets"],
                                                                br.get("compute_uncertain", False), br.get("eps"))
                 off += k
         return out

@@ -536,6 +536,35 @@ int ovis_sample_fg_bg(const int64_t* labels, int num, int batch_size, int max_po
 int ovis_project_pasted_masks_f32(const float* mask_probs, const float* gt_boxes, const int64_t* gt_index,
                                   const float* boxes, int num, int image_height, int image_width, int prob_resolution,
                                   int resolution, float threshold, float* out, void* stream);
+/* ovis_branch_roi_union: the union of the RoIs two branches sampled (ovis_sample_fg_bg) from proposal lists of the same
+ * images -- the student's pseudo-label and ground-truth branches (st_generalized_rcnn.py:284-408), whose lists come out of
+ * one decode + NMS pass, so that the pooler and the res5 head run once per distinct RoI.  One launch for all images, no
+ * host read: per image i and branch b the HOST arrays (at most OVIS_BOX_DECODE_MAX_IMAGES entries) give the DEVICE
+ * pointers boxes_b[i] [num_b[i], 4] f32 (16-byte aligned), selected_b[i] / positive_slots_b[i] [batch_b] int64 and
+ * counts_b[i] [2] int32 as ovis_sample_fg_bg wrote them; sampled row r of a branch is the box boxes[selected[r]].
+ *   match: branch-1 row j is branch-0 row i of the SAME image when the four box words are equal as 32-bit patterns
+ *          (-0.0 != 0.0, a NaN equals only its own bits), i is the lowest such row and no branch-1 row below j has
+ *          those words (further equal branch-1 rows stay rows of their own): both row maps are injective.
+ *   union: every branch-0 row, image-major in its order (rows [0, sum n0)), then the unmatched branch-1 rows,
+ *          image-major in their order.
+ *   rois [rois_rows >= num_images * (batch0 + batch1), 5]: (image_ids[i] or i, x1, y1, x2, y2) of the union rows; every
+ *          row behind them is a copy of the last one (the caller may round the RoI count up).
+ *   map1 [num_images * batch1] int64: the union row of every branch-1 row, image-major, dense.
+ *   positive_rows [num_images * (batch0 + batch1)] int64: ascending, the union rows that are positive in either branch;
+ *   slots0 [num_images * batch0] / slots1 [num_images * batch1]: each branch's positives (image-major, in the order of
+ *          positive_slots) as positions in positive_rows.
+ *   out_counts [num_images, 2] int32: (new rows, entries of positive_rows) the image contributed.
+ *   workspace [batch0] int32.
+ * Counts are clipped to the buffer lengths, proposal indices clamped into their list, slots outside the sampled rows
+ * skipped: no access leaves a buffer whatever lies behind the counts.  Orders come from workgroup scans, no atomics: the
+ * same words on every call. */
+int ovis_branch_roi_union(const float* const* boxes0, const int32_t* num0, const int64_t* const* selected0,
+                          const int64_t* const* positive_slots0, const int32_t* const* counts0,
+                          const float* const* boxes1, const int32_t* num1, const int64_t* const* selected1,
+                          const int64_t* const* positive_slots1, const int32_t* const* counts1, const int32_t* image_ids,
+                          int num_images, int batch0, int batch1, float* rois, int rois_rows, int64_t* map1,
+                          int64_t* positive_rows, int64_t* slots0, int64_t* slots1, int32_t* workspace,
+                          int32_t* out_counts, void* stream);
 /* ovis_paste_masks_u8: the image-size binary masks themselves -- Masker.forward_single_image / paste_mask_in_image
  * (mb/modeling/roi_heads/mask_head/inference.py:100-205, padding 1) for ALL masks of an image in one launch, with the
  * per-pixel arithmetic of ovis_project_pasted_masks_f32 (csrc/pasted_geom.h).  mask_probs [num, prob_resolution,
