@@ -12,24 +12,7 @@ import threading
 
 import torch
 
-
-def _map(obj, fn):
-    if torch.is_tensor(obj):
-        return fn(obj)
-    if isinstance(obj, (list, tuple)):
-        return type(obj)(_map(o, fn) for o in obj)
-    if isinstance(obj, dict):
-        return {k: _map(v, fn) for k, v in obj.items()}
-    if hasattr(obj, "bbox") and hasattr(obj, "extra_fields"):  # BoxList
-        out = type(obj)(fn(obj.bbox), obj.size)
-        for k, v in obj.extra_fields.items():
-            out.add_field(k, _map(v, fn))
-        return out
-    if hasattr(obj, "polygon_start") and hasattr(obj, "instance_start"):  # PolygonMasks
-        return type(obj)(None, obj.size, (fn(obj.coords), fn(obj.polygon_start), fn(obj.instance_start)))
-    if hasattr(obj, "map_tensors"):  # RleMasks
-        return obj.map_tensors(fn)
-    return obj
+from ..modeling.structures import map_tensors as _map
 
 
 _COPY_STREAMS = {}
@@ -47,10 +30,10 @@ def copy_stream(device):
 
 
 class DevicePrefetcher:
-    """Iterates ``source`` (host batches: tensors / BoxLists / PolygonMasks / RleMasks / nested lists, tuples, dicts of them; a
-    ``PolygonMasks`` or ``RleMasks`` field is staged and rebuilt on the device like a BoxList, whether or not ``transform`` is given) ``depth`` batches
-    ahead on a worker thread and yields the same structures on ``device``.  On a CPU device it is a plain look-ahead
-    queue.  Exceptions of the source are re-raised in the consumer.  ``transform`` (optional) is applied to every staged
+    """Iterates ``source`` (host batches: tensors / anything with ``map_tensors`` -- the ``TensorHolder``s of
+    modeling/structures.py -- / nested lists, tuples, dicts of them; a holder in a BoxList's field is staged and rebuilt on the
+    device like the BoxList, whether or not ``transform`` is given) ``depth`` batches ahead on a worker thread and yields
+    the same structures on ``device``.  On a CPU device it is a plain look-ahead queue.  Exceptions of the source are re-raised in the consumer.  ``transform`` (optional) is applied to every staged
     batch in the CONSUMER's thread, on its current stream, once that stream waits for the batch's copies -- the device half
     of ``data/transforms.py`` turns the staged raw uint8 images into the padded float batch there."""
 

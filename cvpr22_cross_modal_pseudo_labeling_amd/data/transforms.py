@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import _C
-from ..modeling.structures import ImageList, RleMasks, raise_on_bad_rle
+from ..modeling.structures import ImageList, RleMasks, TensorHolder, raise_on_bad_rle
 
 FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM = 0, 1
 
@@ -134,10 +134,12 @@ class InputTransform:
         return (self.device(batch[0]),) + tuple(batch[1:])
 
 
-class ViewBatch:
+class ViewBatch(TensorHolder):
     """The test-time-augmentation views of one batch (TEST.BBOX_AUG): ``views[v]`` is the ``ImageList`` of view v over the
     same images, ``flips[v]`` whether that view is mirrored left-right.  View 0 is the un-augmented one: detections are
     reported in its frame and size."""
+
+    _TENSORS = ("views",)
 
     def __init__(self, views, flips):
         self.views, self.flips = list(views), [bool(f) for f in flips]
@@ -146,12 +148,6 @@ class ViewBatch:
 
     def __len__(self):
         return len(self.views)
-
-    def to(self, *args, **kwargs):
-        return ViewBatch([v.to(*args, **kwargs) for v in self.views], self.flips)
-
-    def device_tensors(self):
-        return [v.tensors for v in self.views]
 
 
 class ViewTransform:

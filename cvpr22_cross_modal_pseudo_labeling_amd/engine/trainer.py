@@ -107,7 +107,7 @@ def _record_stream(obj, stream):
     elif isinstance(obj, (list, tuple)):
         for v in obj:
             _record_stream(v, stream)
-    elif hasattr(obj, "device_tensors"):  # BoxList, PolygonMasks, RleMasks, PastedMasks, ImageList (modeling/structures.py)
+    elif hasattr(obj, "device_tensors"):  # a TensorHolder (modeling/structures.py): what it declares, read-only
         _record_stream(obj.device_tensors(), stream)
 
 

@@ -32,7 +32,7 @@ from ..layers.derived import derived
 from .backbone import HeadFeatures, ResNetHead
 from .box_coder import BoxCoder
 from .matcher import BalancedPositiveNegativeSampler, Matcher
-from .structures import BoxList, PastedMasks, PolygonMasks, RleMasks, SampledBoxList, box_iou, boxlist_nms, cat_boxlist
+from .structures import BoxList, SampledBoxList, box_iou, boxlist_nms, cat_boxlist
 
 
 def _cat(tensors, dim=0):
@@ -685,6 +685,17 @@ def project_masks_on_boxes(masks, gt_index, boxes, M):
     return out.to(masks.dtype).float()
 
 
+def project_gt_masks(gt_masks, gt_index, boxes, M):
+    """float32 [P, M, M] mask targets of ``boxes`` from the ground truth in any of its forms: a dense [G, H, W] tensor -- bool
+    / uint8 on the device: crop + bilinear resize of every positive's mask in one launch (csrc/targets.hip), anything else:
+    the tensor-op formulation -- or a lazy form (structures.py: PolygonMasks, RleMasks, PastedMasks), which projects itself."""
+    if not torch.is_tensor(gt_masks):
+        return gt_masks.project(gt_index, boxes, M)
+    if gt_masks.is_cuda and gt_masks.dim() == 3 and gt_masks.dtype in (torch.bool, torch.uint8):
+        return _C.project_masks(gt_masks, gt_index, boxes, M)
+    return project_masks_on_boxes(gt_masks, gt_index, boxes, M)
+
+
 class MaskRCNNLossComputation:
     def __init__(self, cfg):
         rh = cfg.MODEL.ROI_HEADS
@@ -703,14 +714,9 @@ class MaskRCNNLossComputation:
             if _all_positive(prop) and prop.has_field("matched_gt") and prop.bbox.is_cuda:
                 # sampled positives of the box head: same thresholds, so the match is the one already made
                 labels.append(prop.get_field("labels"))
-                masks.append(self._project(gt_masks, prop.get_field("matched_gt"), prop.bbox))
+                masks.append(project_gt_masks(gt_masks, prop.get_field("matched_gt"), prop.bbox, self.discretization_size))
                 continue
-            if isinstance(gt_masks, PastedMasks):
-                gt_masks = gt_masks.materialize()
-            poly = isinstance(gt_masks, (PolygonMasks, RleMasks))  # lazy forms: projected per positive, one launch
-            fused = (prop.bbox.is_cuda and not self.matcher.allow_low_quality_matches
-                     and (poly or (gt_masks.dim() == 3 and gt_masks.dtype in (torch.bool, torch.uint8))))
-            if fused:
+            if prop.bbox.is_cuda and not self.matcher.allow_low_quality_matches:
                 idx, lab, _ = _C.match_encode(tgt.bbox, tgt.get_field("labels"), prop.bbox, self.matcher.high_threshold,
                                               self.matcher.low_threshold, None, between_keeps_label=True)
             else:
@@ -719,36 +725,9 @@ class MaskRCNNLossComputation:
                 lab = tgt.get_field("labels")[idx].to(torch.int64)
                 lab[matched == Matcher.BELOW_LOW_THRESHOLD] = 0
             pos = torch.nonzero(lab > 0).squeeze(1)
-            if poly:   # crop + resize + rasterise every positive's polygons (csrc/polygons.hip) / test its RLE ground
-                # truth's bits (csrc/rle_targets.hip) in one launch
-                masks.append(self._project(gt_masks, idx[pos], prop.bbox[pos]))
-            elif fused:  # crop + bilinear resize of every positive's mask in one launch (csrc/targets.hip)
-                masks.append(_C.project_masks(gt_masks, idx[pos], prop.bbox[pos], self.discretization_size))
-            else:
-                masks.append(project_masks_on_boxes(gt_masks, idx[pos], prop.bbox[pos], self.discretization_size))
+            masks.append(project_gt_masks(gt_masks, idx[pos], prop.bbox[pos], self.discretization_size))
             labels.append(lab)
         return labels, masks
-
-    def _project(self, gt_masks, gt_index, boxes):
-        m = self.discretization_size
-        if isinstance(gt_masks, PastedMasks):  # pseudo labels: targets straight from the probability maps
-            return _C.project_pasted_masks(gt_masks.probs, gt_masks.boxes, gt_index, boxes, gt_masks.image_size, m,
-                                           gt_masks.threshold)
-        if isinstance(gt_masks, PolygonMasks):  # COCO polygon ground truth (SegmentationMask mode 'poly')
-            if gt_masks.coords.device != boxes.device:
-                gt_masks = gt_masks.to(boxes.device)
-            return _C.project_polygon_masks(gt_masks.coords, gt_masks.polygon_start, gt_masks.instance_start, gt_index, boxes,
-                                            gt_masks.size, m)
-        if isinstance(gt_masks, RleMasks):  # bitmap ground truth (SegmentationMask mode 'mask'), from the decoded bit words
-            if not boxes.is_cuda:
-                raise NotImplementedError("RLE ground-truth masks under MODEL.DEVICE cpu are not supported: the decoder and "
-                                          "the target kernel are device code; train on the GPU or use polygon ground truth")
-            if gt_masks.instance.device != boxes.device:
-                gt_masks = gt_masks.to(boxes.device)
-            return _C.project_rle_masks(gt_masks, gt_index, boxes, m)
-        if gt_masks.dim() == 3 and gt_masks.dtype in (torch.bool, torch.uint8):
-            return _C.project_masks(gt_masks, gt_index, boxes, m)
-        return project_masks_on_boxes(gt_masks, gt_index, boxes, m)
 
     def fused(self, proposals, mu, sigma, eps, targets):
         """Same value as ``__call__`` on ``mu[None] + eps * sigma`` (one noise sample), through the fused HIP

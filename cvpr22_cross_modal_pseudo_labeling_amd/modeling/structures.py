@@ -3,8 +3,13 @@
 Behavioural counterpart of maskrcnn_benchmark/structures/bounding_box.py:9-255 (``BoxList``),
 structures/boxlist_ops.py:9-129 (``boxlist_nms / remove_small_boxes / boxlist_iou / cat_boxlist``)
 and structures/image_list.py:7-72, reduced to what the training hot path touches: boxes are always
-``xyxy`` float32 tensors on the device, fields are plain tensors (or python objects), and binary
-instance masks are a ``[G, H, W]`` tensor field instead of a ``SegmentationMask`` wrapper.
+``xyxy`` float32 tensors on the device, fields are plain tensors (or python objects), and instance
+masks are a field in one of four forms: a dense ``[G, H, W]`` tensor, or ``PolygonMasks`` / ``RleMasks`` /
+``PastedMasks``, which stay lazy and answer ``project`` for the mask head's targets.
+
+Every structure that carries tensors is a ``TensorHolder``: it declares the attributes that hold them, and
+``map_tensors`` / ``to`` / ``device_tensors`` follow from that declaration (input staging: data/prefetch.py, stream
+bookkeeping: engine/trainer.py::_record_stream).
 """
 import numpy as np
 import torch
@@ -14,8 +19,51 @@ from ..layers import nms as _nms
 TO_REMOVE = 1.0
 
 
-class BoxList:
+def map_tensors(obj, fn):
+    """``obj`` -- a tensor, a list / tuple / dict, a ``TensorHolder``, nested in any way -- with ``fn`` applied to every
+    tensor: the same nesting and types.  Anything else (None, strings, numbers) is carried over."""
+    if torch.is_tensor(obj):
+        return fn(obj)
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(map_tensors(o, fn) for o in obj)
+    if isinstance(obj, dict):
+        return {k: map_tensors(v, fn) for k, v in obj.items()}
+    if hasattr(obj, "map_tensors"):
+        return obj.map_tensors(fn)
+    return obj
+
+
+class TensorHolder:
+    """An object that holds tensors: ``_TENSORS`` names the attributes whose values are tensors, None, or lists / dicts /
+    holders of tensors; every other attribute is state that a copy shares."""
+
+    _TENSORS = ()
+
+    def _with(self, **changes):
+        """A shallow copy with the given attributes replaced."""
+        out = object.__new__(type(self))
+        out.__dict__ = {**self.__dict__, **changes}
+        return out
+
+    def map_tensors(self, fn):
+        """A copy of the same type with ``fn`` applied to every tensor held."""
+        held = self.__dict__
+        return self._with(**{k: map_tensors(held[k], fn) for k in self._TENSORS})
+
+    def to(self, *args, **kwargs):
+        return self.map_tensors(lambda t: t.to(*args, **kwargs))
+
+    def device_tensors(self):
+        """What a stream has to be told about (engine/trainer.py::_record_stream): the values held, as they are -- a
+        read-only walk, nothing is built."""
+        held = self.__dict__
+        return [held[k] for k in self._TENSORS if held[k] is not None]
+
+
+class BoxList(TensorHolder):
     """xyxy boxes of one image + named per-box fields.  ``size`` is (width, height)."""
+
+    _TENSORS = ("bbox", "extra_fields")  # a field that is a tensor or a holder is mapped, a string or other object carried over
 
     def __init__(self, bbox, image_size, mode="xyxy"):
         bbox = torch.as_tensor(bbox, dtype=torch.float32)
@@ -64,21 +112,11 @@ class BoxList:
         for k, v in self.extra_fields.items():
             if torch.is_tensor(v):
                 out.add_field(k, v[item] if v.dim() > 0 and v.shape[0] == len(self) else v)
-            elif isinstance(v, (PolygonMasks, RleMasks)):  # per-box masks follow the boxes (bounding_box.py:233-242)
-                out.add_field(k, v[item])
+            elif isinstance(v, TensorHolder) and hasattr(v, "__getitem__"):
+                out.add_field(k, v[item])  # per-box masks that can be indexed follow the boxes (bounding_box.py:233-242)
             else:
                 out.add_field(k, v)
         return out
-
-    def to(self, device):
-        out = BoxList(self.bbox.to(device), self.size)
-        for k, v in self.extra_fields.items():
-            out.add_field(k, v.to(device) if hasattr(v, "to") else v)
-        return out
-
-    def device_tensors(self):
-        """What a stream has to be told about (engine/trainer.py::_record_stream): tensors, or holders of tensors."""
-        return [self.bbox, *self.extra_fields.values()]
 
     def area(self):
         b = self.bbox
@@ -143,28 +181,25 @@ class SampledBoxList(BoxList):
     """A proposal list as the box head's sampler hands it out (roi_heads.py::FastRCNNLossComputation.subsample_many), with
     what the sampler knows about its positives: ``pos_index`` int64 [npos], the rows whose label is > 0 (None: the
     tensor-op sampler made the list, ask ``nonzero``), ``all_positive``: every row is a positive, matched to the ground-truth
-    box in its ``matched_gt`` field.  Takes bbox, size and fields from ``boxlist``.  Only ``to`` keeps the type: indexing,
-    ``copy_with_fields`` and ``cat_boxlist`` change the rows, so they yield a plain ``BoxList``."""
+    box in its ``matched_gt`` field.  Takes bbox, size and fields from ``boxlist``.  Only ``to`` and ``map_tensors`` keep the
+    type: indexing, ``copy_with_fields`` and ``cat_boxlist`` change the rows, so they yield a plain ``BoxList``."""
+
+    _TENSORS = BoxList._TENSORS + ("pos_index",)
 
     def __init__(self, boxlist, pos_index=None, all_positive=False):
         super().__init__(boxlist.bbox, boxlist.size)
         self.extra_fields = dict(boxlist.extra_fields)
         self.pos_index, self.all_positive = pos_index, all_positive
 
-    def to(self, device):
-        return SampledBoxList(super().to(device), None if self.pos_index is None else self.pos_index.to(device),
-                              self.all_positive)
 
-    def device_tensors(self):
-        return [*super().device_tensors(), self.pos_index]
-
-
-class PastedMasks:
+class PastedMasks(TensorHolder):
     """Binary instance masks of one image that are DEFINED by per-instance probability maps and boxes through the
     Masker paste (mask_head/inference.py:100-160) -- the pseudo labels' masks (st_generalized_rcnn.py:266-271) -- kept in
     that form: the student's mask targets are computed from the maps directly (``_C.project_pasted_masks``), so the
     H x W canvases are only built when something asks for them (``materialize``).  probs [G, M, M], boxes [G, 4],
     image_size = (height, width)."""
+
+    _TENSORS = ("probs", "boxes")
 
     def __init__(self, probs, boxes, image_size, threshold=0.5, padding=1):
         assert padding == 1, "the device kernel implements the reference's Masker(padding=1)"
@@ -173,11 +208,14 @@ class PastedMasks:
     def __len__(self):
         return self.probs.shape[0]
 
-    def to(self, device):
-        return PastedMasks(self.probs.to(device), self.boxes.to(device), self.image_size, self.threshold, self.padding)
-
-    def device_tensors(self):
-        return [self.probs, self.boxes]
+    def project(self, gt_index, boxes, resolution):
+        """float32 [P, M, M] mask targets of ``boxes``, straight from the probability maps; host boxes (a device step
+        replayed on the CPU): the pasted canvases through the tensor-op projection, the same bits."""
+        from .. import _C
+        if not boxes.is_cuda:
+            from .roi_heads import project_masks_on_boxes
+            return project_masks_on_boxes(self.materialize(), gt_index, boxes, resolution)
+        return _C.project_pasted_masks(self.probs, self.boxes, gt_index, boxes, self.image_size, resolution, self.threshold)
 
     def materialize(self):
         """bool [G, H, W]: what Masker(threshold, padding) pastes."""
@@ -186,7 +224,7 @@ class PastedMasks:
         return Masker(self.threshold, self.padding)(self.probs[:, None], BoxList(self.boxes, (w, h)))[:, 0]
 
 
-class PolygonMasks:
+class PolygonMasks(TensorHolder):
     """Polygon ground-truth masks of one image, the reference's ``SegmentationMask(polygons, size, mode='poly')``
     (structures/segmentation_mask.py:348-478 over PolygonInstance :208-347) in the flat form the device kernel reads:
     ``coords`` float32 [T] -- the (x, y) pairs of every polygon back to back --, ``polygon_start`` int32 [NP + 1] (offsets
@@ -196,11 +234,10 @@ class PolygonMasks:
     ``convert_to_binarymask`` rasterises whole-image masks at any image size (``_C.polygons_to_masks`` on the device,
     ``_cpu.polygons_to_masks`` on the host)."""
 
-    def __init__(self, instances, size, _flat=None):
+    _TENSORS = ("coords", "polygon_start", "instance_start")
+
+    def __init__(self, instances, size):
         self.size = tuple(size)
-        if _flat is not None:
-            self.coords, self.polygon_start, self.instance_start = _flat
-            return
         coords, pstart, istart = [], [0], [0]
         for polys in instances:
             for poly in polys:
@@ -216,12 +253,12 @@ class PolygonMasks:
     def __len__(self):
         return self.instance_start.numel() - 1
 
-    def to(self, device):
-        return PolygonMasks(None, self.size, (self.coords.to(device), self.polygon_start.to(device),
-                                              self.instance_start.to(device)))
-
-    def device_tensors(self):
-        return [self.coords, self.polygon_start, self.instance_start]
+    def project(self, gt_index, boxes, resolution):
+        """float32 [P, M, M] mask targets of ``boxes``: crop + resize + rasterise every positive's polygons in one launch
+        (csrc/polygons.hip), on the device ``boxes`` live on."""
+        from .. import _C
+        m = self if self.coords.device == boxes.device else self.to(boxes.device)
+        return _C.project_polygon_masks(m.coords, m.polygon_start, m.instance_start, gt_index, boxes, m.size, resolution)
 
     def instances(self):
         """Back to the nested-list form: per instance a list of flat float32 polygons (host tensors)."""
@@ -248,7 +285,7 @@ class PolygonMasks:
             raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
         c = self.coords.clone()
         c[method::2] = self.size[method] - self.coords[method::2] - TO_REMOVE
-        return PolygonMasks(None, self.size, (c, self.polygon_start, self.instance_start))
+        return self._with(coords=c)
 
     def resize(self, size):
         """Polygons scaled to ``size`` = (width, height): segmentation_mask.py:301-324 (one ratio when both axes agree)."""
@@ -260,7 +297,7 @@ class PolygonMasks:
             c = self.coords.clone()
             c[0::2] *= ratios[0]
             c[1::2] *= ratios[1]
-        return PolygonMasks(None, size, (c, self.polygon_start, self.instance_start))
+        return self._with(coords=c, size=size)
 
     def convert_to_binarymask(self):
         """uint8 [G, height, width]: every instance rasterised over the whole image (segmentation_mask.py:326-334)."""
@@ -271,7 +308,7 @@ class PolygonMasks:
         return _C.polygons_to_masks(self.coords, self.polygon_start, self.instance_start, self.size)
 
 
-class RleMasks:
+class RleMasks(TensorHolder):
     """Bitmap (COCO RLE) ground-truth masks of one image, the reference's ``SegmentationMask(rles, size, mode='mask')``
     (``BinaryMaskList``, structures/segmentation_mask.py:33-158), kept LAZY: the encodings, the geometry that was asked
     for, and an instance index -- never a canvas.  The mask head's targets come straight from the decoded bit words
@@ -291,10 +328,7 @@ class RleMasks:
 
     _TENSORS = ("chars", "char_offsets", "runs", "run_offsets", "sizes", "instance", "words", "word_offsets")
 
-    def __init__(self, items, source_hw, image_id=None, ann_ids=None, _state=None):
-        if _state is not None:
-            self.__dict__.update(_state)
-            return
+    def __init__(self, items, source_hw, image_id=None, ann_ids=None):
         h0, w0 = int(source_hw[0]), int(source_hw[1])
         if h0 < 1 or w0 < 1 or h0 * w0 > 0x7fffffef:
             raise ValueError(f"RleMasks: source size {h0} x {w0} is outside what the decoder takes")
@@ -337,15 +371,6 @@ class RleMasks:
         self.image_id = image_id
         self.ann_ids = list(ann_ids) if ann_ids is not None else list(range(n))
 
-    def _with(self, **changes):
-        state = dict(self.__dict__)
-        state.update(changes)
-        return RleMasks(None, None, _state=state)
-
-    def map_tensors(self, fn):
-        """A copy with ``fn`` applied to every tensor it holds (staging: data/prefetch.py::_map)."""
-        return self._with(**{k: fn(getattr(self, k)) for k in self._TENSORS if getattr(self, k) is not None})
-
     @property
     def words_per_mask(self):
         return (self.source_hw[0] * self.source_hw[1] + 63) // 64
@@ -353,11 +378,15 @@ class RleMasks:
     def __len__(self):
         return self.instance.numel()
 
-    def to(self, device):
-        return self.map_tensors(lambda t: t.to(device))
-
-    def device_tensors(self):
-        return [getattr(self, k) for k in self._TENSORS if getattr(self, k) is not None]
+    def project(self, gt_index, boxes, resolution):
+        """float32 [P, M, M] mask targets of ``boxes``: the decoded bit words tested per target pixel in one launch
+        (csrc/rle_targets.hip), on the device ``boxes`` live on."""
+        from .. import _C
+        if not boxes.is_cuda:
+            raise NotImplementedError("RLE ground-truth masks under MODEL.DEVICE cpu are not supported: the decoder and "
+                                      "the target kernel are device code; train on the GPU or use polygon ground truth")
+        m = self if self.instance.device == boxes.device else self.to(boxes.device)
+        return _C.project_rle_masks(m, gt_index, boxes, resolution)
 
     def __getitem__(self, item):
         """Instances selected by an int, a slice, an index tensor or a boolean mask: the instance index is indexed, the
@@ -494,18 +523,14 @@ def remove_small_boxes(boxlist, min_size):  # boxlist_ops.py:34-49
     return boxlist[(ws >= min_size) & (hs >= min_size)]
 
 
-class ImageList:
+class ImageList(TensorHolder):
     """Batched images padded to a common size (image_list.py:7-72)."""
+
+    _TENSORS = ("tensors",)  # the padded batch to_image_list allocates
 
     def __init__(self, tensors, image_sizes):
         self.tensors = tensors
         self.image_sizes = list(image_sizes)  # (height, width) per image
-
-    def to(self, *args, **kwargs):
-        return ImageList(self.tensors.to(*args, **kwargs), self.image_sizes)
-
-    def device_tensors(self):
-        return [self.tensors]  # the padded batch to_image_list allocates
 
 
 def to_image_list(tensors, size_divisible=0):

@@ -413,6 +413,154 @@ def test_synthetic_batches_through_worker_processes_keep_their_order():
     pre.close()
 
 
+# ---- the structures that hold tensors: one declaration, three derived protocols (modeling/structures.py::TensorHolder) ----
+def _gt_list(seed=0):
+    """A BoxList with every kind of field: a label tensor, a string, polygon masks and (resized, flipped) RLE masks."""
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import PolygonMasks, RleMasks
+
+    b = BoxList(torch.tensor([[2.0, 3.0, 20.0, 18.0], [10.0, 5.0, 30.0, 25.0]]) + seed, (50, 37))
+    b.add_field("labels", torch.tensor([3, 1]) + seed)
+    b.add_field("is_det", "Yes")
+    b.add_field("polygons", PolygonMasks([[[2.0, 3.0, 20.0, 3.0, 20.0, 18.0]], [[10.0, 5.0, 30.0, 5.0, 30.0, 25.0, 10.0, 25.0]]], (50, 37)))
+    rle = RleMasks([[100, 50, 37 * 50 - 150], "0000"], (37, 50), image_id=9, ann_ids=[41, 42])
+    b.add_field("rle", rle.resize((100, 74)).transpose(0))
+    return b
+
+
+def _sampled_list(seed=0):
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import SampledBoxList
+
+    return SampledBoxList(_gt_list(seed), torch.tensor([1]), all_positive=True)
+
+
+def _image_list(n=2):
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import ImageList
+
+    return ImageList(torch.arange(n * 3 * 4 * 6, dtype=torch.float32).view(n, 3, 4, 6), [(4, 5), (3, 6)][:n])
+
+
+def _holder(name):
+    """-> (holder, the non-tensor attributes a copy must keep)."""
+    from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import ViewBatch
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import PastedMasks
+
+    if name == "BoxList":
+        return _gt_list(), ("size", "mode")
+    if name == "SampledBoxList":
+        return _sampled_list(), ("size", "mode", "all_positive")
+    if name == "PastedMasks":
+        return PastedMasks(torch.rand(2, 14, 14), torch.tensor([[1.0, 2.0, 9.0, 8.0], [0.0, 0.0, 5.0, 5.0]]), (37, 50), 0.4, 1), \
+            ("image_size", "threshold", "padding")
+    if name == "PolygonMasks":
+        return _gt_list().get_field("polygons"), ("size",)
+    if name == "RleMasks":
+        return _gt_list().get_field("rle"), ("size", "flip_h", "flip_v", "source_hw", "image_id", "ann_ids", "num_items")
+    if name == "ImageList":
+        return _image_list(), ("image_sizes",)
+    assert name == "ViewBatch"
+    return ViewBatch([_image_list(), _image_list()], [False, True]), ("flips",)
+
+
+HOLDERS = ["BoxList", "SampledBoxList", "PastedMasks", "PolygonMasks", "RleMasks", "ImageList", "ViewBatch"]
+
+
+def _reached(obj, out):
+    """The tensors a recursive walk of ``device_tensors()`` reaches -- engine/trainer.py::_record_stream's walk."""
+    if torch.is_tensor(obj):
+        out.append(obj)
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            _reached(v, out)
+    elif isinstance(obj, (list, tuple)):
+        for v in obj:
+            _reached(v, out)
+    elif hasattr(obj, "device_tensors"):
+        _reached(obj.device_tensors(), out)
+    return out
+
+
+def _same_state(a, b, names):
+    assert type(a) is type(b)
+    for n in names:
+        assert getattr(a, n) == getattr(b, n), n
+
+
+@pytest.mark.parametrize("name", HOLDERS)
+def test_map_tensors_keeps_type_tensors_and_state(name):
+    holder, state = _holder(name)
+    copy = holder.map_tensors(lambda t: t.clone())
+    _same_state(holder, copy, state)
+    mine, theirs = _reached(holder, []), _reached(copy, [])
+    assert len(mine) == len(theirs) > 0
+    for a, b in zip(mine, theirs):
+        assert a is not b and a.dtype == b.dtype and torch.equal(a, b)
+    if name in ("BoxList", "SampledBoxList"):
+        assert copy.fields() == holder.fields() and copy.get_field("is_det") == "Yes"
+        _same_state(holder.get_field("polygons"), copy.get_field("polygons"), ("size",))
+        _same_state(holder.get_field("rle"), copy.get_field("rle"), ("size", "flip_h", "source_hw", "image_id", "ann_ids"))
+        assert copy.get_field("rle").size == (100, 74) and copy.get_field("rle").flip_h is True
+    if name == "SampledBoxList":
+        assert copy.all_positive is True and torch.equal(copy.pos_index, holder.pos_index)
+        moved = holder.to("cpu")
+        assert type(moved) is type(holder) and moved.all_positive is True and torch.equal(moved.pos_index, holder.pos_index)
+    if name == "RleMasks":
+        assert copy.words is None and copy.word_offsets is None   # None entries stay None
+    if name == "ImageList":
+        assert holder.to(torch.float64).tensors.dtype == torch.float64   # ``to`` keeps accepting a dtype
+    if name == "ViewBatch":
+        assert [v.image_sizes for v in copy.views] == [v.image_sizes for v in holder.views]
+
+
+@pytest.mark.parametrize("name", HOLDERS)
+def test_map_tensors_visits_what_device_tensors_reaches(name):
+    """One declaration feeds both protocols: the tensors ``map_tensors`` visits, by identity, are those a recursive walk of
+    ``device_tensors()`` reaches, each once."""
+    holder, _ = _holder(name)
+    visited = []
+    holder.map_tensors(lambda t: (visited.append(t), t)[1])
+    reached = _reached(holder, [])
+    assert len(visited) == len(set(map(id, visited))) and len(reached) == len(set(map(id, reached)))
+    assert set(map(id, visited)) == set(map(id, reached)) and len(visited) > 0
+
+
+def test_map_over_a_nested_batch_visits_every_tensor_once():
+    """data.prefetch._map over (ImageList, [BoxList, SampledBoxList], {"k": tensor}): the same nesting and types, every
+    tensor visited exactly once."""
+    from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import _map
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import ImageList, SampledBoxList
+
+    batch = (_image_list(), [_gt_list(0), _sampled_list(1)], {"k": torch.tensor([1.0, 2.0])})
+    visited = []
+    out = _map(batch, lambda t: (visited.append(t), t.clone())[1])
+    reached = _reached(batch, [])
+    assert sorted(map(id, visited)) == sorted(map(id, reached)) and len(set(map(id, visited))) == len(visited) == 1 + 11 + 12 + 1
+    assert type(out) is tuple and type(out[0]) is ImageList and type(out[1]) is list and type(out[2]) is dict
+    assert type(out[1][0]) is BoxList and type(out[1][1]) is SampledBoxList and out[1][1].all_positive is True
+    assert list(out[2]) == ["k"] and torch.equal(out[2]["k"], batch[2]["k"]) and out[2]["k"] is not batch[2]["k"]
+    for a, b in zip(reached, _reached(out, [])):
+        assert a is not b and torch.equal(a, b)
+    assert out[0].image_sizes == batch[0].image_sizes and out[1][0].get_field("is_det") == "Yes"
+
+
+def test_mask_targets_of_host_pasted_masks_equal_those_of_the_pasted_canvases():
+    """Pseudo-label masks moved to the host (a device step replayed on the CPU) give the targets their dense form gives."""
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import PastedMasks
+
+    gt = torch.tensor([[4.0, 5.0, 20.0, 30.0], [25.0, 3.0, 40.0, 20.0]])
+    pasted = PastedMasks(torch.rand(2, 14, 14, generator=torch.Generator().manual_seed(1)), gt, (40, 60))
+    prop = BoxList(torch.cat([gt + 1.0, gt - 0.5, torch.tensor([[45.0, 25.0, 55.0, 35.0]])]), (60, 40))
+    got = []
+    for masks in (pasted, pasted.materialize()):
+        target = BoxList(gt, (60, 40))
+        target.add_field("labels", torch.tensor([2, 1]))
+        target.add_field("masks", masks)
+        got.append(RH.MaskRCNNLossComputation(get_defaults()).prepare_targets([prop], [target]))
+    (labels_a,), (targets_a,) = got[0]
+    (labels_b,), (targets_b,) = got[1]
+    assert labels_a.tolist() == labels_b.tolist() == [2, 1, 2, 1, 0]
+    assert targets_a.shape == (4, 14, 14) and torch.equal(targets_a, targets_b) and 0.05 < float(targets_a.mean()) < 0.95
+
+
 def test_box_decode_with_image_clip_equals_decode_then_clip_to_image(z):
     """``BoxCoder.decode(..., rows_per_image, image_sizes)`` (the form the box post-processor calls; on the device one
     kernel) on CPU tensors: the reference's decode (fixture) followed by ``BoxList.clip_to_image`` per image."""

@@ -212,6 +212,61 @@ def test_project_pasted_masks_equals_paste_then_project(G, P, size):
     assert 0.05 < float(got.mean()) < 0.95
 
 
+@pytest.mark.parametrize("form", ["dense", "polygons", "rle", "pasted"])
+def test_prepare_targets_projects_every_ground_truth_form_through_its_own_kernel(form):
+    """A 60 x 40 image, 3 disjoint ground-truth rectangles, 8 proposals that are a ground-truth box moved by at most a
+    pixel (the match is unambiguous): ``MaskRCNNLossComputation.prepare_targets`` == that form's ``_C.project_*`` called with
+    the known indices, bit for bit, for a sampled list of positives (``matched_gt``) and for a plain list (matched here).  A
+    form is compared with itself only: polygon and bitmap rasterisation may differ at the edges."""
+    import numpy as np
+
+    from cvpr22_cross_modal_pseudo_labeling_amd import _C
+    from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.roi_heads import MaskRCNNLossComputation
+    from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import (BoxList, PastedMasks, PolygonMasks, RleMasks,
+                                                                           SampledBoxList)
+    from tests import coco_rle_reference as rle_ref
+    w, h, m = 60, 40, 14
+    rects = [[4, 5, 20, 30], [25, 3, 40, 20], [42, 18, 57, 36]]
+    gt = torch.tensor(rects, dtype=torch.float32).cuda()
+    gt_labels = torch.tensor([3, 1, 2]).cuda()
+    idx = torch.tensor([0, 1, 2, 0, 1, 2, 2, 0]).cuda()
+    shift = torch.tensor([[0, 0, 0, 0], [1, 0, 1, 0], [0, -1, 0, -1], [-1, 1, 0, 0], [0.5, 0.5, -0.5, 1], [1, 1, 1, 1],
+                          [-1, 0, 0, 1], [0.25, -0.75, 1, 0]]).cuda()
+    boxes = gt[idx] + shift
+    bitmaps = np.zeros((3, h, w), dtype=bool)
+    for k, (x0, y0, x1, y1) in enumerate(rects):
+        bitmaps[k, y0:y1 + 1, x0:x1 + 1] = True
+    if form == "dense":
+        masks = torch.from_numpy(bitmaps).to(torch.uint8).cuda()
+        want = _C.project_masks(masks, idx, boxes, m)
+    elif form == "polygons":
+        masks = PolygonMasks([[[x0, y0, x1 + 1, y0, x1 + 1, y1 + 1, x0, y1 + 1]] for x0, y0, x1, y1 in rects], (w, h)).to("cuda")
+        want = _C.project_polygon_masks(masks.coords, masks.polygon_start, masks.instance_start, idx, boxes, (w, h), m)
+    elif form == "rle":
+        masks = RleMasks([rle_ref.rle_encode(b) for b in bitmaps], (h, w)).to("cuda")
+        want = _C.project_rle_masks(masks, idx, boxes, m)
+    else:
+        probs = torch.rand(3, m, m, generator=torch.Generator().manual_seed(4)).cuda()
+        masks = PastedMasks(probs, gt, (h, w), threshold=0.4)
+        want = _C.project_pasted_masks(probs, gt, idx, boxes, (h, w), m, 0.4)
+    assert want.shape == (8, m, m) and 0.05 < float(want.mean()) < 1.0
+    targets = BoxList(gt, (w, h))
+    targets.add_field("labels", gt_labels)
+    targets.add_field("masks", masks)
+    cfg = get_defaults()
+    cfg.merge_from_list(["MODEL.ROI_MASK_HEAD.RESOLUTION", m])
+    loss = MaskRCNNLossComputation(cfg)
+    plain = BoxList(boxes, (w, h))
+    positives = BoxList(boxes, (w, h))
+    positives.add_field("labels", gt_labels[idx])
+    positives.add_field("matched_gt", idx)
+    for proposals in (SampledBoxList(positives, all_positive=True), plain):
+        (labels,), (got,) = loss.prepare_targets([proposals], [targets])
+        assert torch.equal(labels, gt_labels[idx])
+        assert got.shape == want.shape and torch.equal(got, want), int((got != want).sum())
+
+
 def _sampler_model(lab, batch, max_pos, seed):
     """NumPy statement of the sampler: per class the k smallest splitmix64 keys of (seed, index), ties by index."""
     import numpy as np
