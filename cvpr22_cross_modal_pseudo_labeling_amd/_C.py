@@ -509,6 +509,71 @@ def merge_view_detections(boxes, scores, segments, num_classes, score_thresh):
     return cand_boxes, cand_scores, cand_group, offsets
 
 
+def vote_boxes(cand_boxes, cand_scores, offsets, cand_group, kept, vote_thresh):
+    """Box voting over the candidate list of ``merge_view_detections`` (Detectron's ``box_voting``, scoring method ID; not
+    in the reference), ``ovis_vote_boxes_f32``: cand_boxes [K, 4] / cand_scores [K] float32, offsets [B * C + 1] and
+    cand_group [K] int32, kept [D] int64 = the candidate indices of the detections the NMS kept -> [D, 4] float32, row j =
+    sum s_k box_k / sum s_k over the candidates k of kept[j]'s own (image, class) run with IoU(box_kept[j], box_k) >=
+    vote_thresh (the NMS's IoU expression and comparison).  One wavefront per detection and a fixed butterfly: the same bits
+    on every call.  A kept index outside [0, K) or outside its group's run raises (the kernel reads nothing through it; the
+    status costs ONE host read).  D == 0 or K == 0: an empty result, nothing launched (K == 0 with D > 0 raises).  Host
+    tensors: ``libovis_cpu.so``, the same operations in the same order."""
+    tensors = (cand_boxes, cand_scores, offsets, cand_group, kept)
+    if len({t.is_cuda for t in tensors}) != 1:
+        raise RuntimeError("vote_boxes: host and device tensors mixed in one call")
+    k = cand_boxes.shape[0] if cand_boxes.dim() == 2 else -1
+    if (k < 0 or cand_boxes.shape[1] != 4 or tuple(cand_scores.shape) != (k,) or tuple(cand_group.shape) != (k,)
+            or offsets.dim() != 1 or offsets.numel() < 1 or kept.dim() != 1 or cand_boxes.dtype != torch.float32
+            or cand_scores.dtype != torch.float32 or offsets.dtype != torch.int32 or cand_group.dtype != torch.int32
+            or kept.dtype != torch.int64):
+        raise RuntimeError("vote_boxes: expected float32 cand_boxes [K, 4] and cand_scores [K], int32 offsets [G + 1] and "
+                           f"cand_group [K], int64 kept [D]; got {[(str(t.dtype), tuple(t.shape)) for t in tensors]}")
+    d = kept.shape[0]
+    if d and not k:
+        raise RuntimeError(f"vote_boxes: {d} kept indices into an empty candidate list")
+    if not cand_boxes.is_cuda:
+        return _cpu.vote_boxes(*(t.contiguous() for t in tensors), float(vote_thresh))
+    dev = cand_boxes.device
+    out = torch.empty((d, 4), dtype=torch.float32, device=dev)
+    if d == 0:
+        return out
+    cand_boxes = _dev(cand_boxes, "cand_boxes")
+    cand_scores, offsets, cand_group, kept = (t.contiguous() for t in tensors[1:])
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_L.ovis_vote_boxes_f32(cand_boxes.data_ptr(), cand_scores.data_ptr(), offsets.data_ptr(),
+                                          cand_group.data_ptr(), k, offsets.numel() - 1, kept.data_ptr(), d,
+                                          float(vote_thresh), out.data_ptr(), status.data_ptr(), _stream()), "vote_boxes")
+    if int(status.item()):
+        raise RuntimeError("vote_boxes: OVIS_ERANGE (a kept index outside the candidate list or outside its (image, class) run)")
+    return out
+
+
+def average_view_masks(maps, flips):
+    """The mean of the views' mask maps (``ovis_average_view_masks_f32``; not in the reference): maps [V, D, 1, M, M]
+    float32, ``flips``: V booleans -> [D, 1, M, M] = (((m_0 + m_1) + m_2) + ...) / float(V) in float32, the columns of a
+    mirrored view reversed first.  A division: one unflipped view returns its input bit for bit.  V <= 64.  Host tensors:
+    ``libovis_cpu.so``."""
+    flips = [bool(f) for f in flips]
+    if (maps.dim() != 5 or maps.shape[2] != 1 or maps.shape[3] != maps.shape[4] or maps.shape[3] < 1 or maps.shape[0] < 1
+            or maps.dtype != torch.float32 or len(flips) != maps.shape[0]):
+        raise RuntimeError(f"average_view_masks: expected float32 maps [V >= 1, D, 1, M, M] and V flips, got {maps.dtype} "
+                           f"{tuple(maps.shape)} and {len(flips)} flips")
+    v, d, _, m, _ = maps.shape
+    if v > 64:
+        raise RuntimeError(f"average_view_masks: OVIS_ERANGE ({v} views, at most 64)")
+    flip_bits = sum(1 << i for i, f in enumerate(flips) if f)
+    maps = maps.contiguous()
+    if not maps.is_cuda:
+        return _cpu.average_view_masks(maps, flip_bits)
+    out = torch.empty((d, 1, m, m), dtype=torch.float32, device=maps.device)
+    if d:
+        with _on(maps.device):
+            _lib.check(_L.ovis_average_view_masks_f32(maps.data_ptr(), v, d, m, flip_bits, out.data_ptr(), _stream()),
+                       "average_view_masks")
+    return out
+
+
 def rois_from_boxes(boxes, image_ids=None):
     """``Pooler.convert_to_roi_format`` (modeling/poolers.py:73-86) in one launch (``ovis_rois_from_boxes_f32``): a list of
     per-image [n_i, 4] float32 HIP tensors -> [sum n_i, 5] rows (image index, x1, y1, x2, y2); the image index of list

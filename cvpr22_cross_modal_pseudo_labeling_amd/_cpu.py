@@ -247,3 +247,26 @@ def merge_view_detections(boxes, scores, segments, num_classes, num_images, scor
                 torch.tensor(offsets, dtype=torch.int32))
     return (torch.cat(out_boxes, 0).reshape(-1, 4), torch.cat(out_scores, 0), torch.cat(out_group, 0),
             torch.tensor(offsets, dtype=torch.int32))
+
+
+# ---- box voting and view-averaged masks of test-time augmentation (not in the reference; Detectron's box_voting, method ID) ----
+def vote_boxes(cand_boxes, cand_scores, offsets, cand_group, kept, vote_thresh):
+    """[D, 4] (``ovis_cpu_vote_boxes_f32``); the operands as ``_C.vote_boxes`` checked them."""
+    k, d = cand_boxes.shape[0], kept.shape[0]
+    out = torch.empty((d, 4), dtype=torch.float32)
+    if d:
+        _check(load().ovis_cpu_vote_boxes_f32(cand_boxes.data_ptr() if k else 0, cand_scores.data_ptr() if k else 0,
+                                              offsets.data_ptr(), cand_group.data_ptr() if k else 0, k, offsets.numel() - 1,
+                                              kept.data_ptr(), d, float(vote_thresh), out.data_ptr()),
+               "vote_boxes: a kept index outside the candidate list or outside its (image, class) run")
+    return out
+
+
+def average_view_masks(maps, flip_bits):
+    """[D, 1, M, M] (``ovis_cpu_average_view_masks_f32``); the operands as ``_C.average_view_masks`` checked them."""
+    v, d, _, m, _ = maps.shape
+    out = torch.empty((d, 1, m, m), dtype=torch.float32)
+    if d:
+        _check(load().ovis_cpu_average_view_masks_f32(maps.data_ptr(), v, d, m, flip_bits, out.data_ptr()),
+               "average_view_masks")
+    return out

@@ -473,4 +473,73 @@ extern "C" int ovis_cpu_render_instances_u8(const uint8_t* image, int height, in
   return OVIS_CPU_OK;
 }
 
-extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 5 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets, input transform, prediction compositor; fp32, OpenMP)"; }
+// ---- box voting over the merged candidate list and the mean of the views' mask maps (not in the reference) --------------------
+// Twin of csrc/box_vote.hip: the IoU is ovis_cpu_nms_f32's (= nms.hip's) expression; lane l of 64 sums the voters lo + l,
+// lo + l + 64, ... in that order and the lanes are folded by the xor butterfly 32, 16, ... 1, as the wavefront does.
+extern "C" int ovis_cpu_vote_boxes_f32(const float* cand_boxes, const float* cand_scores, const int32_t* offsets,
+                                       const int32_t* cand_group, long num_candidates, int num_groups, const int64_t* kept,
+                                       long num_kept, float vote_thresh, float* voted) {
+  if (num_candidates < 0 || num_groups < 0 || num_kept < 0) return OVIS_CPU_EINVAL;
+  if (num_kept == 0) return OVIS_CPU_OK;
+  if (!kept || !voted || !offsets) return OVIS_CPU_EINVAL;
+  if (num_candidates > 0 && (!cand_boxes || !cand_scores || !cand_group)) return OVIS_CPU_EINVAL;
+  int bad = 0;
+#pragma omp parallel for schedule(dynamic, 16) reduction(| : bad)
+  for (long j = 0; j < num_kept; ++j) {
+    float* out = voted + 4 * j;
+    out[0] = out[1] = out[2] = out[3] = 0.f;
+    const int64_t d = kept[j];
+    if (d < 0 || d >= num_candidates) { bad |= 1; continue; }
+    const int g = cand_group[d];
+    if (g < 0 || g >= num_groups) { bad |= 1; continue; }
+    const long lo = offsets[g], hi = offsets[g + 1];
+    if (lo < 0 || hi > num_candidates || d < lo || d >= hi) { bad |= 1; continue; }
+    const float* a = cand_boxes + 4 * d;
+    const float area_a = (a[2] - a[0] + 1.f) * (a[3] - a[1] + 1.f);
+    float part[5][64];
+    for (int c = 0; c < 5; ++c)
+      for (int l = 0; l < 64; ++l) part[c][l] = 0.f;
+    for (long k = lo; k < hi; ++k) {
+      const float* b = cand_boxes + 4 * k;
+      const float left = std::max(a[0], b[0]), right = std::min(a[2], b[2]);
+      const float top = std::max(a[1], b[1]), bottom = std::min(a[3], b[3]);
+      const float w = std::max(right - left + 1.f, 0.f), h = std::max(bottom - top + 1.f, 0.f);
+      const float inter = w * h;
+      const float area_b = (b[2] - b[0] + 1.f) * (b[3] - b[1] + 1.f);
+      if (!(inter / (area_a + area_b - inter) >= vote_thresh)) continue;
+      const int l = (int)((k - lo) & 63);
+      const float s = cand_scores[k];
+      part[0][l] = part[0][l] + s;
+      for (int c = 0; c < 4; ++c) part[c + 1][l] = part[c + 1][l] + s * b[c];
+    }
+    for (int c = 0; c < 5; ++c)
+      for (int off = 32; off > 0; off >>= 1) {
+        float next[64];
+        for (int l = 0; l < 64; ++l) next[l] = part[c][l] + part[c][l ^ off];
+        for (int l = 0; l < 64; ++l) part[c][l] = next[l];
+      }
+    for (int c = 0; c < 4; ++c) out[c] = part[c + 1][0] / part[0][0];
+  }
+  return bad ? OVIS_CPU_ERANGE : OVIS_CPU_OK;
+}
+
+extern "C" int ovis_cpu_average_view_masks_f32(const float* maps, int num_views, long num_maps, int resolution,
+                                               uint64_t flip_bits, float* out) {
+  if (num_views < 1 || num_maps < 0 || resolution < 1) return OVIS_CPU_EINVAL;
+  if (num_views > 64 || resolution > 32768) return OVIS_CPU_ERANGE;
+  const long M = resolution, rows = num_maps * M, per_view = rows * M;
+  if (per_view == 0) return OVIS_CPU_OK;
+  if (!maps || !out) return OVIS_CPU_EINVAL;
+  const float count = (float)num_views;
+#pragma omp parallel for schedule(static)
+  for (long r = 0; r < rows; ++r)
+    for (long x = 0; x < M; ++x) {
+      const long i = r * M + x, mirrored = r * M + (M - 1 - x);
+      float acc = maps[(flip_bits & 1ull) ? mirrored : i];
+      for (int v = 1; v < num_views; ++v) acc = acc + maps[v * per_view + (((flip_bits >> v) & 1ull) ? mirrored : i)];
+      out[i] = acc / count;
+    }
+  return OVIS_CPU_OK;
+}
+
+extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 6 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets, input transform, prediction compositor, box voting and view-averaged masks; fp32, OpenMP)"; }

@@ -91,8 +91,9 @@ def run_rpn_recall(cfg, model, catalog, device, logger=None):
 
 
 def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
-                 export_results=False, recall=False):
-    """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}."""
+                 export_results=False, recall=False, vote_thresh=None, average_masks=False):
+    """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}.  ``vote_thresh`` /
+    ``average_masks``: box voting and view-averaged masks of multi-scale / flip testing (engine/bbox_aug.py)."""
     transform = build_transforms(cfg, is_train=False)
     results = {}
     for name in cfg.DATASETS.TEST:
@@ -102,7 +103,8 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
         out = os.path.join(cfg.OUTPUT_DIR, "inference", name) if cfg.OUTPUT_DIR else None
         try:  # the zero-shot heads classify against THIS dataset's class embeddings
             results[name] = inference.inference(model, batches, name, device, out,
-                                                class_embeddings=getattr(dataset, "class_emb_mtx", None), logger=logger)
+                                                class_embeddings=getattr(dataset, "class_emb_mtx", None), logger=logger,
+                                                vote_thresh=vote_thresh, average_masks=average_masks)
         finally:
             batches.close()
         if visualize_count > 0 and out and results[name] is not None:  # rank 0 only: the others got None

@@ -25,26 +25,32 @@ from ..modeling.structures import BoxList
 
 
 @torch.no_grad()
-def compute_on_dataset(model, batches, device, timer=None, forward=None):
+def compute_on_dataset(model, batches, device, timer=None, forward=None, vote_thresh=None, average_masks=False):
     """batches: iterable of (images, targets, image_ids) -> {image_id: BoxList on CPU} (inference.py:25-47).  ``forward``:
     a callable images -> [BoxList] that takes the place of the model's evaluation pass (``model.propose``: the RPN's
     proposals instead of detections); it has no multi-view form, so a ``ViewBatch`` raises.  Without it: a batch whose
     images are a ``ViewBatch`` (TEST.BBOX_AUG: build_transforms(cfg, False) made every view) goes through
     ``im_detect_bbox_aug`` (inference.py:34-35).  A model configured with TEST.BBOX_AUG.ENABLED that is handed ready-made
     images instead raises: the views are made from raw bytes, which such a stream (``tools/test_net.py``'s float32 synthetic
-    one) does not have -- ``tools/infer_net.py`` reads datasets through the raw input path."""
+    one) does not have -- ``tools/infer_net.py`` reads datasets through the raw input path.  ``vote_thresh`` /
+    ``average_masks``: ``im_detect_bbox_aug``'s box voting and view-averaged masks; they act on the views of a
+    ``ViewBatch``, so any other batch (or ``forward=``) raises instead of ignoring them."""
     model.eval()
+    options = vote_thresh is not None or average_masks
     augmented = model_cfg(model) is not None and model_cfg(model).TEST.BBOX_AUG.ENABLED
     results = {}
     cpu = torch.device("cpu")
     for images, targets, image_ids in batches:
         t0 = time.perf_counter()
+        if options and (forward is not None or not isinstance(images, ViewBatch)):
+            raise ValueError("compute_on_dataset: vote_thresh / average_masks act on the views of multi-scale / flip testing "
+                             "(TEST.BBOX_AUG.ENABLED True, a ViewBatch stream)")
         if forward is not None:
             if isinstance(images, ViewBatch):
                 raise ValueError("compute_on_dataset: forward= takes single-view batches (TEST.BBOX_AUG.ENABLED False)")
             output = forward(images.to(device))
         elif isinstance(images, ViewBatch):
-            output = im_detect_bbox_aug(model, images.to(device))
+            output = im_detect_bbox_aug(model, images.to(device), vote_thresh=vote_thresh, average_masks=average_masks)
         elif augmented:
             raise ValueError("TEST.BBOX_AUG.ENABLED, but the batch holds already-transformed images: the views are made from "
                              "raw bytes by build_transforms(cfg, is_train=False); tools/infer_net.py feeds such a stream")
@@ -137,18 +143,20 @@ def accumulate_predictions(predictions, logger=None):
 
 
 def inference(model, batches, dataset_name="synthetic", device="cuda", output_folder=None, class_embeddings=None,
-              logger=None, forward=None, file_name="predictions.pth"):
+              logger=None, forward=None, file_name="predictions.pth", vote_thresh=None, average_masks=False):
     """Detections of every image of ``batches`` (this rank's shard), gathered on rank 0 in image-id order and saved
     as ``predictions.pth`` (inference.py:104-170, without the dataset-specific ``evaluate`` call).  ``forward`` /
     ``file_name``: what ``compute_on_dataset`` runs instead of the model's evaluation pass, and the file its BoxLists are
-    saved to (``model.propose`` and ``proposals.pth`` for the RPN's proposals)."""
+    saved to (``model.propose`` and ``proposals.pth`` for the RPN's proposals).  ``vote_thresh`` / ``average_masks``: handed
+    to ``compute_on_dataset``."""
     logger = logger or logging.getLogger("ovis.inference")
     device = torch.device(device)
     if class_embeddings is not None:  # zero-shot heads map predicted embeddings to classes (inference.py:124-131)
         model.set_class_embeddings(class_embeddings.to(device))
     times = []
     start = time.perf_counter()
-    predictions = compute_on_dataset(model, batches, device, times, forward=forward)
+    predictions = compute_on_dataset(model, batches, device, times, forward=forward, vote_thresh=vote_thresh,
+                                     average_masks=average_masks)
     comm.synchronize()
     total = time.perf_counter() - start
     world = comm.get_world_size()

@@ -390,7 +390,7 @@ class PostProcessor(nn.Module):
             results.append(boxlist)
         return results
 
-    def filter_merged(self, merged, image_sizes, num_classes, max_candidates=None, slice_candidates=None):
+    def filter_merged(self, merged, image_sizes, num_classes, max_candidates=None, slice_candidates=None, return_kept=False):
         """``filter_results`` for the candidate list of ``_C.merge_view_detections`` (``merged`` = cand_boxes, cand_scores,
         cand_group, offsets; already above the score threshold and class-major per image): per-class NMS, then the
         DETECTIONS_PER_IMG best of every image -> one BoxList per image of ``image_sizes`` ((width, height)), with
@@ -400,7 +400,8 @@ class PostProcessor(nn.Module):
         ``slice_candidates`` asks for slices of about that size although the list would fit one call -- a call visits every
         pair of its candidates, so two half-size calls do half the work -- and never raises: a larger single run gets a
         slice of its own, up to ``max_candidates``.  Same detections either way.  Host tensors: the reference's per-class
-        loop (``filter_results_per_class``) over the runs of the list."""
+        loop (``filter_results_per_class``) over the runs of the list.  ``return_kept``: -> (results, kept), ``kept[i]`` the
+        int64 indices into the candidate list of image i's detections, in their order (what ``_C.vote_boxes`` is given)."""
         cand_boxes, cand_scores, cand_group, offsets = merged
         c, b = int(num_classes), len(image_sizes)
         if offsets.numel() != b * c + 1:
@@ -408,7 +409,7 @@ class PostProcessor(nn.Module):
         limit = _C.NMS_MAX_CANDIDATES if max_candidates is None else int(max_candidates)
         k = cand_boxes.shape[0]
         if not cand_boxes.is_cuda:
-            return self._filter_merged_per_class(merged, image_sizes, c)
+            return self._filter_merged_per_class(merged, image_sizes, c, return_kept)
         if k == 0:
             keep = torch.zeros((0,), dtype=torch.int64, device=cand_boxes.device)
         elif k <= (limit if slice_candidates is None else min(limit, int(slice_candidates))):
@@ -429,7 +430,7 @@ class PostProcessor(nn.Module):
                 lo = hi
             keep = _cat([kp[: int(num.item())] + at for kp, num, at in parts], 0)
         bounds = torch.searchsorted(keep, offsets[::c].to(torch.int64)).tolist()   # the images' shares of the survivors
-        results = []
+        results, kept = [], []
         for i, size in enumerate(image_sizes):
             idx = keep[bounds[i]:bounds[i + 1]]
             result = BoxList(cand_boxes[idx], size)
@@ -439,13 +440,18 @@ class PostProcessor(nn.Module):
             if n > self.detections_per_img > 0:
                 s = result.get_field("scores")
                 thresh = torch.kthvalue(s, n - self.detections_per_img + 1).values
-                result = result[torch.nonzero(s >= thresh).squeeze(1)]
+                best = torch.nonzero(s >= thresh).squeeze(1)
+                result = result[best]
+                if return_kept:
+                    idx = idx[best]
             results.append(result)
-        return results
+            kept.append(idx)
+        return (results, kept) if return_kept else results
 
-    def _filter_merged_per_class(self, merged, image_sizes, num_classes):
+    def _filter_merged_per_class(self, merged, image_sizes, num_classes, return_kept=False):
         """inference.py:137-163 over a merged candidate list: the (image, class) runs are what ``nonzero(scores > thresh)``
-        selects from the concatenated views, in that order."""
+        selects from the concatenated views, in that order.  ``return_kept``: a candidate's index rides through the NMS
+        and the cut as a field, and comes back as ``filter_merged`` describes."""
         cand_boxes, cand_scores, _, offsets = merged
         starts = offsets.tolist()
         results = []
@@ -457,6 +463,8 @@ class PostProcessor(nn.Module):
                     continue
                 cls_boxes = BoxList(cand_boxes[lo:hi], size)
                 cls_boxes.add_field("scores", cand_scores[lo:hi])
+                if return_kept:
+                    cls_boxes.add_field("candidate", torch.arange(lo, hi, dtype=torch.int64, device=cand_scores.device))
                 cls_boxes = boxlist_nms(cls_boxes, self.nms)
                 cls_boxes.add_field("labels", torch.full((len(cls_boxes),), j, dtype=torch.int64, device=cand_scores.device))
                 result.append(cls_boxes)
@@ -464,6 +472,8 @@ class PostProcessor(nn.Module):
                 empty = BoxList(cand_boxes.new_zeros((0, 4)), size)
                 empty.add_field("scores", cand_scores.new_zeros((0,)))
                 empty.add_field("labels", torch.zeros((0,), dtype=torch.int64, device=cand_scores.device))
+                if return_kept:
+                    empty.add_field("candidate", torch.zeros((0,), dtype=torch.int64, device=cand_scores.device))
                 results.append(empty)
                 continue
             result = cat_boxlist(result)
@@ -473,6 +483,8 @@ class PostProcessor(nn.Module):
                 thresh = torch.kthvalue(s, n - self.detections_per_img + 1).values
                 result = result[torch.nonzero(s >= thresh).squeeze(1)]
             results.append(result)
+        if return_kept:
+            return results, [r.extra_fields.pop("candidate") for r in results]
         return results
 
     def filter_results(self, boxlist, num_classes):  # inference.py:121-163

@@ -70,6 +70,18 @@ int ovis_cpu_render_instances_u8(const uint8_t* image, int height, int width, co
                                  const float* colors, float alpha, const uint8_t* outline_colors, int outline_thickness,
                                  uint8_t* out, int threads);
 
+/* Box voting and the mean of the views' mask maps on host tensors: twins of ovis_vote_boxes_f32 and
+ * ovis_average_view_masks_f32 (include/ovis_hip.h: same arguments, same rule, same float32 operations in the same order --
+ * the vote keeps the 64 strided partial sums and the xor butterfly of the device's wavefront, so the bits agree).  Not in
+ * the reference (mb/engine/bbox_aug.py:53-69); Detectron's box_voting, scoring method ID.  A kept index outside [0, K), a
+ * group outside [0, num_groups) or a kept index outside its group's run: OVIS_CPU_ERANGE, nothing is read through it.
+ * `boxes` / `voted` need no alignment here. */
+int ovis_cpu_vote_boxes_f32(const float* cand_boxes, const float* cand_scores, const int32_t* offsets,
+                            const int32_t* cand_group, long num_candidates, int num_groups, const int64_t* kept,
+                            long num_kept, float vote_thresh, float* voted);
+int ovis_cpu_average_view_masks_f32(const float* maps, int num_views, long num_maps, int resolution, uint64_t flip_bits,
+                                    float* out);
+
 const char* ovis_cpu_version(void);
 
 #ifdef __cplusplus

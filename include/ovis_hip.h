@@ -246,6 +246,29 @@ int ovis_view_merge_scatter_f32(const float* boxes, const float* scores, long nu
                                 const int32_t* starts, long num_counts, long num_candidates, float* cand_boxes,
                                 float* cand_scores, int32_t* cand_group, int32_t* offsets, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Box voting over the merged candidate list, and the mean of the views' mask maps        csrc/box_vote.hip
+ *   Neither is in the reference (mb/engine/bbox_aug.py:53-69 hands out the NMS survivors, boxes only); the voting rule is
+ *   Detectron's box_voting with scoring method ID.
+ * vote: cand_boxes [K, 4] (16-byte aligned), cand_scores [K], cand_group [K] int32 and offsets [num_groups + 1] int32 are the
+ * outputs of the view merge above; kept [num_kept] int64 are candidate indices (the detections the NMS kept).  voted
+ * [num_kept, 4] (16-byte aligned) row j = sum_k s_k * box_k / sum_k s_k over the candidates k of kept[j]'s own run
+ * offsets[g] .. offsets[g + 1], g = cand_group[kept[j]], with IoU(box_kept[j], box_k) >= vote_thresh -- the IoU of ovis_nms_f32
+ * operand for operand, so a pair is on the same side of a threshold for the NMS and for the vote.  One wavefront per
+ * detection, five float32 partial sums per lane (lane l takes candidates lo + l, lo + l + 64, ...), a fixed xor butterfly:
+ * no atomics, the same bits on every call.  Every load is bounded by offsets and K: a kept index outside [0, K), a group
+ * outside [0, num_groups) or a kept index outside its group's run stores 1 to *status (device int32, zeroed by the caller)
+ * and a zero row, and no address is formed from it.  num_kept == 0: nothing is launched.
+ * average: maps [num_views, num_maps, resolution, resolution] f32 -> out [num_maps, resolution, resolution] =
+ * (((m_0 + m_1) + m_2) + ...) / float(num_views), view v's columns reversed when bit v of flip_bits is set; a division, so
+ * one unflipped view returns its input bit for bit.  num_views <= 64 (more: OVIS_ERANGE).  One launch.
+ * ---------------------------------------------------------------------------------- */
+int ovis_vote_boxes_f32(const float* cand_boxes, const float* cand_scores, const int32_t* offsets, const int32_t* cand_group,
+                        long num_candidates, int num_groups, const int64_t* kept, long num_kept, float vote_thresh,
+                        float* voted, int32_t* status, void* stream);
+int ovis_average_view_masks_f32(const float* maps, int num_views, long num_maps, int resolution, uint64_t flip_bits,
+                                float* out, void* stream);
+
 /* Pooler.convert_to_roi_format (mb/modeling/poolers.py:73-86): boxes[i] (HOST array of device pointers) holds image i's
  * [boxes_per_image[i], 4] boxes (boxes_per_image: HOST array); rois [sum, 5] receives (id_i, x1, y1, x2, y2) rows in list
  * order, id_i = image_ids[i] (HOST array) or i when image_ids is NULL.  One launch per OVIS_BOX_DECODE_MAX_IMAGES images. */

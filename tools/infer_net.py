@@ -24,7 +24,10 @@ files next to ``predictions.pth`` (engine/coco_results.py): ``bbox.json``, and `
 detection, boxes as xywh and masks as compressed RLE at the ORIGINAL image sizes, the masks encoded on the device; it needs
 OUTPUT_DIR, and MODEL.DEVICE cuda when MODEL.MASK_ON.  ``TEST.BBOX_AUG.ENABLED True`` (with H_FLIP / SCALES / MAX_SIZE / SCALE_H_FLIP) turns on multi-scale / flip testing:
 ``build_transforms(cfg, False)`` then makes every view on the device from the one upload and ``engine/bbox_aug.py`` merges the
-views' detections; the saved BoxLists are in the first view's frame and keep their masks.  ``tools/test_net.py`` stays the
+views' detections; the saved BoxLists are in the first view's frame and keep their masks.  Two options of that mode, neither
+in the reference: ``--bbox-vote THR`` replaces every kept box by the score-weighted mean of the merged candidates of its class
+that overlap it by IoU >= THR (box voting), ``--mask-aug`` runs the mask head on every view and saves the mean of the views'
+maps instead of the first view's (engine/bbox_aug.py).  ``tools/test_net.py`` stays the
 synthetic-stream tool; LVIS scoring is outside this build.
 """
 import argparse
@@ -78,6 +81,12 @@ def main(argv=None):
                         help="run backbone + RPN alone over every test set, save the proposals as "
                              "OUTPUT_DIR/inference/<name>/proposals.pth and score their recall by objectness on the device: an "
                              "rpn_proposal task in the log and in rpn_recall.json (rank 0); no detections are made")
+    parser.add_argument("--bbox-vote", type=float, default=None, metavar="THR",
+                        help="with TEST.BBOX_AUG.ENABLED True: box voting -- every kept box becomes the score-weighted mean of "
+                             "the merged candidates of its class with IoU >= THR, a float in (0, 1]")
+    parser.add_argument("--mask-aug", action="store_true",
+                        help="with TEST.BBOX_AUG.ENABLED True and MODEL.MASK_ON: the masks are the mean of every view's "
+                             "mask-head pass instead of the first view's")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
     args = parser.parse_args(argv)
 
@@ -110,6 +119,14 @@ def main(argv=None):
     if args.export_results and cfg.MODEL.MASK_ON and cfg.MODEL.DEVICE != "cuda":
         parser.error("--export-results encodes the masks of segm.json on the HIP device (the run-length encoder has no host "
                      "implementation): set MODEL.DEVICE cuda")
+    if args.bbox_vote is not None and not cfg.TEST.BBOX_AUG.ENABLED:
+        parser.error("--bbox-vote votes over the views of multi-scale / flip testing: set TEST.BBOX_AUG.ENABLED True")
+    if args.mask_aug and not cfg.TEST.BBOX_AUG.ENABLED:
+        parser.error("--mask-aug averages the masks of the views of multi-scale / flip testing: set TEST.BBOX_AUG.ENABLED True")
+    if args.mask_aug and not cfg.MODEL.MASK_ON:
+        parser.error("--mask-aug averages the mask head's maps: set MODEL.MASK_ON True")
+    if args.bbox_vote is not None and not 0.0 < args.bbox_vote <= 1.0:
+        parser.error(f"--bbox-vote takes an IoU threshold in (0, 1], got {args.bbox_vote}")
     device = torch.device(cfg.MODEL.DEVICE, args.local_rank) if cfg.MODEL.DEVICE == "cuda" else torch.device(cfg.MODEL.DEVICE)
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
@@ -136,7 +153,8 @@ def main(argv=None):
         run_rpn_recall(cfg, model, catalog, device, logger)
     else:
         for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
-                                        args.evaluate, args.export_results, args.recall).items():
+                                        args.evaluate, args.export_results, args.recall, args.bbox_vote,
+                                        args.mask_aug).items():
             if preds is not None:
                 logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:
