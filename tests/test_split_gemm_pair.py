@@ -754,7 +754,7 @@ def test_split_gemm_pair_gated_epilogue():
         want_p, _ = C.gate_split_pair(d, yp)
         _, got_p = C.split_gemm_pair_gated(ap, wp, yp, conv=(7, 7, 3, 3, True), config=cfg)
         assert torch.equal(got_p, want_p)
-    # the teacher step's layer3 data gradient (50 x 84 maps, 132 tiles walking 72 k-steps: four K slices): sliced == plain
+    # the teacher step's layer3 data gradient (50 x 84 maps, 132 tiles walking 72 k-steps: three K slices): sliced == plain
     # product + gate bit for bit, and within the split product's error of the un-split order
     m2, c2 = 2 * 50 * 84, 256
     a2, y2 = torch.randn(m2, c2, device="cuda"), torch.randn(m2, c2, device="cuda").clamp(min=0)
