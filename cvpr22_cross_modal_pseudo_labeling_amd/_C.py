@@ -2015,6 +2015,64 @@ def coco_mask_iou(det_words, det_areas, gt_words, gt_areas, gt_crowd, problems=N
     return out.view(d, g) if dense else out
 
 
+def coco_boundary_words(words, height, width, dilation):
+    """(boundary words int64 [P, Wn], boundary areas int64 [P]) of packed masks ``words`` [P, Wn = ceil(height * width /
+    64)] of ONE image size (``coco_pack_masks``' layout): ``m & ~eroded(m)``, eroded = ``dilation`` iterations of a 3x3
+    erosion with the outside of the image 0 (``ovis_coco_boundary_words_u64``; the rule: include/ovis_hip.h).  The caller
+    computes ``dilation`` (engine/coco_eval.py: ``boundary_dilation``).  Enqueue only; P words of scratch are allocated."""
+    words = _dev(words, "words", torch.int64)
+    height, width, dilation = int(height), int(width), int(dilation)
+    if words.dim() != 2 or (height >= 1 and width >= 1 and words.shape[1] != (height * width + 63) // 64):
+        raise RuntimeError(f"coco_boundary_words: expected words [P, ceil({height} * {width} / 64)], got {tuple(words.shape)}")
+    p = words.shape[0]
+    out, areas = torch.empty_like(words), torch.zeros((p,), dtype=torch.int64, device=words.device)
+    scratch = torch.empty_like(words)
+    with _on(words.device):
+        rc = _L.ovis_coco_boundary_words_u64(words.data_ptr() if p else 0, p, height, width, dilation,
+                                             scratch.data_ptr() if p else 0, out.data_ptr() if p else 0,
+                                             areas.data_ptr() if p else 0, _stream())
+    _lib.check(rc, "coco_boundary_words")
+    return out, areas
+
+
+def coco_boundary_iou(det_words, det_bwords, det_areas, det_bareas, gt_words, gt_bwords, gt_areas, gt_bareas, gt_crowd,
+                      problems=None):
+    """fp64 min(mask IoU, boundary IoU) of packed masks and their boundaries (``coco_boundary_words``) -- the IoU Boundary AP
+    matches (``ovis_coco_boundary_iou_f64``): both ratios as in ``coco_mask_iou``, the crowd form included, so exact and
+    elementwise <= ``coco_mask_iou`` of the same masks.  Without ``problems``: words [D, Wn] / [G, Wn] -> [D, G]; with a
+    ``CocoProblems``: flat word buffers addressed by the table (the boundary words lie as the mask words do) -> the flat IoU
+    buffer ``coco_match`` takes."""
+    det_words, gt_words = _dev(det_words, "det_words", torch.int64), _dev(gt_words, "gt_words", torch.int64)
+    det_bwords, gt_bwords = _dev(det_bwords, "det_bwords", torch.int64), _dev(gt_bwords, "gt_bwords", torch.int64)
+    det_areas, gt_areas = _dev(det_areas, "det_areas", torch.int64), _dev(gt_areas, "gt_areas", torch.int64)
+    det_bareas, gt_bareas = _dev(det_bareas, "det_bareas", torch.int64), _dev(gt_bareas, "gt_bareas", torch.int64)
+    gt_crowd = _dev(gt_crowd, "gt_crowd", torch.uint8)
+    d, g = det_areas.numel(), gt_areas.numel()
+    if gt_crowd.shape != (g,) or det_bareas.numel() != d or gt_bareas.numel() != g \
+            or det_bwords.shape != det_words.shape or gt_bwords.shape != gt_words.shape:
+        raise RuntimeError("coco_boundary_iou: expected gt_crowd [G], boundary areas [D] / [G] and boundary words shaped "
+                           "as the mask words")
+    dense = problems is None
+    if dense:
+        if det_words.dim() != 2 or gt_words.dim() != 2 or det_words.shape[0] != d or gt_words.shape[0] != g \
+                or det_words.shape[1] != gt_words.shape[1]:
+            raise RuntimeError("coco_boundary_iou: expected det_words [D,Wn] and gt_words [G,Wn]")
+        if d == 0 or g == 0:
+            return torch.empty((d, g), dtype=torch.float64, device=det_words.device)
+        problems = CocoProblems.dense(d, g, det_words.device, det_words.shape[1])
+    problems.check("coco_boundary_iou", d, g, det_words=det_words.numel(), gt_words=gt_words.numel())
+    out = torch.zeros((problems.iou_numel,), dtype=torch.float64, device=det_words.device)
+    if problems.max_pairs:
+        with _on(det_words.device):
+            rc = _L.ovis_coco_boundary_iou_f64(det_words.data_ptr(), det_bwords.data_ptr(), det_areas.data_ptr(),
+                                               det_bareas.data_ptr(), gt_words.data_ptr(), gt_bwords.data_ptr(),
+                                               gt_areas.data_ptr(), gt_bareas.data_ptr(), gt_crowd.data_ptr(),
+                                               problems.dev.data_ptr(), len(problems), problems.max_pairs, out.data_ptr(),
+                                               _stream())
+        _lib.check(rc, "coco_boundary_iou")
+    return out.view(d, g) if dense else out
+
+
 def coco_match(iou, problems, det_areas, gt_areas, gt_crowd, area_ranges, thresholds):
     """COCOeval.evaluateImg for every problem, area range and IoU threshold in one launch (``ovis_coco_match``).  iou:
     the flat fp64 buffer of ``coco_box_iou`` / ``coco_mask_iou`` for the same ``problems``; det_areas [D], gt_areas [G]

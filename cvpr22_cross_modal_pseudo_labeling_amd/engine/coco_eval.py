@@ -35,6 +35,15 @@ detections in score order, so the first k columns of the maxDets = 100 tables ar
 pycocotools itself slices them.  The ``box_proposal`` task of the reference's table is a different, class-agnostic matching
 with a kernel of its own: engine/proposal_recall.py.  Keypoints are not scored.
 
+BOUNDARY AP.  A third ``iou_type``, ``"boundary"`` (Cheng et al., "Boundary IoU", CVPR 2021): segm's matching on min(mask IoU,
+boundary IoU), where a mask's boundary is what d = max(1, round(0.02 x diagonal)) iterations of a 3x3 erosion take away.
+boundary-iou-api is not a dependency either; the rule is restated in include/ovis_hip.h and the numbers follow THAT text --
+they have not been compared with boundary-iou-api's output.  It works on the words segm already has: per image size one
+``_C.coco_boundary_words`` call for the detections and one for the ground truths (csrc/coco_boundary.hip), then
+``_C.coco_boundary_iou`` fills the IoU buffer the matching reads; a chunk plans 11 / 8 byte per pixel and mask instead of
+9 / 8 (the boundary words and the erosion's scratch).  Asked for together, segm and boundary share one paste / rasterise /
+decode / pack per chunk, and segm's tables are those of a run without boundary, bit for bit.
+
 SHARDED.  ``evaluate_coco_sharded`` is ``evaluate_coco`` for a caller that holds one rank's {dataset index: BoxList} instead of
 the gathered list (a training run's periodic evaluation, engine/evaluation.py): an image's matching does not depend on any
 other image, so every rank scores the images it predicted on its own device and only the match tables go to rank 0, where
@@ -42,6 +51,7 @@ other image, so every rank scores the images it predicted on its own device and 
 """
 import contextlib
 import json
+import math
 import os
 from collections import OrderedDict
 
@@ -63,6 +73,32 @@ MAX_CALL_MASKS = 65535  # what one paste_masks / polygons_to_masks call takes: m
 # the masks of one pasted_masks_rle call of the results export (engine/coco_results.py): inside MAX_CALL_MASKS, and small
 # enough that a chunk's maps (25 MB at M = 28) and runs (a few hundred int32 per mask) are no burden on the device
 MAX_EXPORT_MASKS = 8192
+IOU_TYPES = ("bbox", "segm", "boundary")
+MASK_IOU_TYPES = ("segm", "boundary")  # scored from the packed mask words: one pass over a chunk serves both
+BOUNDARY_DILATION_RATIO = 0.02
+
+
+def _check_iou_type(iou_type, who):
+    if iou_type not in IOU_TYPES:
+        raise ValueError(f"{who}: iou_type '{iou_type}' is not supported ({', '.join(IOU_TYPES)})")
+
+
+def boundary_dilation(height, width, ratio=BOUNDARY_DILATION_RATIO):
+    """The erosion depth d of Boundary IoU for a ``height`` x ``width`` image, rule 1 of include/ovis_hip.h: ``ratio`` of
+    the diagonal, rounded half to even (Python 3's ``round``), at least 1.  Host arithmetic; the device gets the integer."""
+    return max(1, int(round(ratio * math.sqrt(height * height + width * width))))
+
+
+def _jobs(iou_types):
+    """The scoring passes ``iou_types`` take, in order of first appearance: each a name, or -- when both are asked for --
+    the tuple ("segm", "boundary"), which one pass over the chunks' mask words serves."""
+    both = all(t in iou_types for t in MASK_IOU_TYPES)
+    jobs = []
+    for t in iou_types:
+        job = MASK_IOU_TYPES if both and t in MASK_IOU_TYPES else t
+        if job not in jobs:
+            jobs.append(job)
+    return jobs
 
 
 # ---- host: COCOeval.accumulate / summarize --------------------------------------------------------------------------------
@@ -304,8 +340,7 @@ def load_coco_results(dataset, results, iou_type):
     place of ``maps`` / ``xyxy`` (the area comes from the decoder); ``entry`` is every row's index in the file.  Entries of
     a category the annotation file does not have are dropped (COCOeval never evaluates them).  ValueError, naming the
     entry: an image_id the file does not have, a polygon segmentation, a ``size`` that is not the image's, a missing key."""
-    if iou_type not in ("bbox", "segm"):
-        raise ValueError(f"load_coco_results: iou_type '{iou_type}' is not supported (bbox, segm)")
+    _check_iou_type(iou_type, "load_coco_results")  # boundary: the rows of segm, it scores the same segm.json
     if isinstance(results, (str, bytes, os.PathLike)):
         with open(results) as f:
             results = json.load(f)
@@ -358,17 +393,18 @@ def load_coco_results(dataset, results, iou_type):
     return rows
 
 
-def _chunks(images, dets, with_masks, budget, max_images=None):
+def _chunks(images, dets, with_masks, budget, max_images=None, boundary=False):
     """Lists of consecutive image indices: a chunk closes before the image that would take it over ``budget`` bytes of
     masks, over ``max_images`` (None: MAX_CHUNK_IMAGES) or -- for segm -- over MAX_CALL_MASKS detections, ground truths or
-    polygons.  An image that breaks a limit alone still gets its own chunk."""
+    polygons.  An image that breaks a limit alone still gets its own chunk.  ``boundary``: a mask costs 11 / 8 byte per
+    pixel instead of 9 / 8 -- its boundary words (10 / 8), and as much again for ``_C.coco_boundary_words``' scratch."""
     max_images = MAX_CHUNK_IMAGES if max_images is None else max_images
     chunk, used = [], np.zeros(4, dtype=np.int64)
     limits = np.asarray([budget, MAX_CALL_MASKS, MAX_CALL_MASKS, MAX_CALL_MASKS], dtype=np.float64)
     for i, (image, det) in enumerate(zip(images, dets)):
         n_det, n_gt = len(det["cats"]), len(image["cats"])
-        cost = np.asarray([(n_det + n_gt) * image["height"] * image["width"] * 9 // 8, n_det, n_gt, image["polygons"]],
-                          dtype=np.int64) * (1 if with_masks else 0)
+        cost = np.asarray([(n_det + n_gt) * image["height"] * image["width"] * (11 if boundary else 9) // 8, n_det, n_gt,
+                           image["polygons"]], dtype=np.int64) * (1 if with_masks else 0)
         if chunk and (np.any(used + cost > limits) or len(chunk) >= max_images):
             yield chunk
             chunk, used = [], np.zeros(4, dtype=np.int64)
@@ -415,12 +451,29 @@ def _pack_group(group_rows, masks, words_parts, areas_out, base, rle=None):
     return base + words.numel()
 
 
-def score_chunk(images, dets, iou_type, device, timer=None):
+def _boundary_group(words_parts, bwords_parts, bareas_out, group_rows, height, width, ratio, timer):
+    """The boundary words and areas (``_C.coco_boundary_words``) of the image-size group whose mask words were appended to
+    ``words_parts`` last."""
+    nwords = (height * width + 63) // 64
+    with _stage(timer, "boundary"):
+        bwords, bareas = _C.coco_boundary_words(words_parts[-1].view(-1, nwords), height, width,
+                                                boundary_dilation(height, width, ratio))
+    bwords_parts.append(bwords.reshape(-1))
+    bareas_out[group_rows] = bareas
+
+
+def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
     """The match tables of one chunk of images (the NumPy form ``accumulate`` takes): a constant number of launches --
     box or mask IoU and the matching -- plus, for segm, the paste, rasterise and pack calls of every image size; detections
     that carry ``rle`` (``load_coco_results``) and RLE ground truth take one ``_C.coco_rle_words`` call per image size
-    instead -- a malformed encoding raises a ValueError that names the entry or the annotation."""
-    with_masks = iou_type == "segm"
+    instead -- a malformed encoding raises a ValueError that names the entry or the annotation.
+
+    boundary (Boundary AP: the rule is in include/ovis_hip.h) works on the words segm makes: one
+    ``_C.coco_boundary_words`` call per image size and side, then ``_C.coco_boundary_iou`` writes min(mask IoU, boundary
+    IoU) where segm has the mask IoU, and the same matching follows -- with the MASK areas.  ``iou_type`` may be the tuple
+    ("segm", "boundary"): the words are made once, both IoU buffers are matched, and {name: tables} comes back."""
+    types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type)
+    with_masks, boundary = types[0] != "bbox", "boundary" in types
     rows, det_base, gt_base, iou_off = [], 0, 0, 0
     det_image_base, gt_image_base = [], []
     for i, (image, det) in enumerate(zip(images, dets)):
@@ -452,6 +505,8 @@ def score_chunk(images, dets, iou_type, device, timer=None):
         det_words, gt_words, det_word_base, gt_word_base = [], [], 0, 0
         det_areas_i = torch.zeros(num_dets, dtype=torch.int64, device=device)
         gt_areas_i = torch.zeros(num_gts, dtype=torch.int64, device=device)
+        det_bwords, gt_bwords = [], []  # boundary: the boundary words, laid out as the mask words
+        det_bareas_i, gt_bareas_i = torch.zeros_like(det_areas_i), torch.zeros_like(gt_areas_i)
         image_words = {}  # image -> (first det word, first gt word, words per mask)
         for (height, width), members in groups.items():
             nwords = (height * width + 63) // 64
@@ -479,6 +534,9 @@ def score_chunk(images, dets, iou_type, device, timer=None):
                     det_word_base = _pack_group(torch.from_numpy(det_rows).to(device), pasted, det_words,
                                                 det_areas_i, det_word_base)
                 del pasted
+            if boundary and len(det_rows):
+                _boundary_group(det_words, det_bwords, det_bareas_i, torch.from_numpy(det_rows).to(device), height, width,
+                                boundary_dilation_ratio, timer)
             if len(gt_rows):
                 anns = [a for i in members for a in images[i]["anns"]]
                 for a in anns:
@@ -503,6 +561,9 @@ def score_chunk(images, dets, iou_type, device, timer=None):
                     gt_word_base = _pack_group(torch.from_numpy(gt_rows).to(device), masks, gt_words, gt_areas_i,
                                                gt_word_base, rle)
                 del masks
+                if boundary:
+                    _boundary_group(gt_words, gt_bwords, gt_bareas_i, torch.from_numpy(gt_rows).to(device), height, width,
+                                    boundary_dilation_ratio, timer)
         if len(table):  # the word columns of every problem, from its image's share of the word buffers
             img = table[:, 9]
             first = np.asarray([image_words[i] for i in range(len(images))], dtype=np.int64).reshape(-1, 3)
@@ -511,18 +572,28 @@ def score_chunk(images, dets, iou_type, device, timer=None):
             table[:, 6] = first[img, 1] + (table[:, 2] - np.asarray(gt_image_base)[img]) * table[:, 7]
         problems = _C.CocoProblems(table[:, :8], device)
         empty = torch.zeros(0, dtype=torch.int64, device=device)
-        with _stage(timer, "iou"):
-            iou = _C.coco_mask_iou(torch.cat(det_words) if det_words else empty, det_areas_i,
-                                   torch.cat(gt_words) if gt_words else empty, gt_areas_i, crowd, problems)
-        det_areas = det_areas_i.double()
+        det_words, gt_words = torch.cat(det_words) if det_words else empty, torch.cat(gt_words) if gt_words else empty
+        if "segm" in types:
+            with _stage(timer, "iou"):
+                iou = _C.coco_mask_iou(det_words, det_areas_i, gt_words, gt_areas_i, crowd, problems)
+        if boundary:
+            with _stage(timer, "boundary_iou"):
+                boundary_iou = _C.coco_boundary_iou(det_words, torch.cat(det_bwords) if det_bwords else empty, det_areas_i,
+                                                    det_bareas_i, gt_words, torch.cat(gt_bwords) if gt_bwords else empty,
+                                                    gt_areas_i, gt_bareas_i, crowd, problems)
+        det_areas = det_areas_i.double()  # boundary too: the area ranges stay those of the masks
     thresholds = torch.from_numpy(IOU_THRESHOLDS).to(device)
     area_ranges = torch.from_numpy(AREA_RANGES).to(device)
-    with _stage(timer, "match"):
-        dt_match, dt_ignore, gt_ignore = _C.coco_match(iou, problems, det_areas, gt_areas, crowd, area_ranges, thresholds)
-    return {"category": table[:, 8].copy(),
-            "det_start": np.concatenate([table[:, 0], [num_dets]]), "gt_start": np.concatenate([table[:, 2], [num_gts]]),
-            "scores": scores, "dt_match": dt_match.cpu().numpy(), "dt_ignore": dt_ignore.cpu().numpy(),
-            "gt_ignore": gt_ignore.cpu().numpy()}
+    tables = {}
+    for name in types:
+        with _stage(timer, "match"):
+            dt_match, dt_ignore, gt_ignore = _C.coco_match(boundary_iou if name == "boundary" else iou, problems, det_areas,
+                                                           gt_areas, crowd, area_ranges, thresholds)
+        tables[name] = {"category": table[:, 8].copy(), "det_start": np.concatenate([table[:, 0], [num_dets]]),
+                        "gt_start": np.concatenate([table[:, 2], [num_gts]]), "scores": scores,
+                        "dt_match": dt_match.cpu().numpy(), "dt_ignore": dt_ignore.cpu().numpy(),
+                        "gt_ignore": gt_ignore.cpu().numpy()}
+    return tables[iou_type] if isinstance(iou_type, str) else tables
 
 
 def concatenate_tables(parts):
@@ -543,13 +614,24 @@ def concatenate_tables(parts):
             "gt_ignore": np.concatenate([p["gt_ignore"] for p in parts] + [np.zeros((num_a, 0), bool)], axis=1)}
 
 
-def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None):
+def _job_types(iou_type, who):
+    """The names of one scoring pass: ``iou_type`` itself, or the members of the tuple ("segm", "boundary")."""
+    types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type)
+    for t in types:
+        _check_iou_type(t, who)
+    if len(types) != 1 and types != MASK_IOU_TYPES:
+        raise ValueError(f"{who}: one pass scores one iou_type or {MASK_IOU_TYPES}, not {types}")
+    return types
+
+
+def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None,
+                 boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
     """-> (the match tables of every (image, category) problem of the annotation file, in image-id order; the sorted
     category ids).  ``budget``: the bytes of device memory a chunk may plan with (None: a quarter of what is free);
     ``max_images``: the most images of a chunk (None: MAX_CHUNK_IMAGES); ``ground_truth``: ``_ground_truth(dataset)`` when
-    the caller already has it."""
-    if iou_type not in ("bbox", "segm"):
-        raise ValueError(f"evaluate_coco: iou_type '{iou_type}' is not supported (bbox, segm)")
+    the caller already has it.  ``iou_type``: bbox, segm, boundary, or the tuple ("segm", "boundary") -- then the first
+    item is {name: tables}, both from one set of mask words per chunk."""
+    types = _job_types(iou_type, "evaluate_coco")
     if len(predictions) > len(dataset):
         raise ValueError(f"evaluate_coco: {len(predictions)} predictions for a dataset of {len(dataset)} images")
     device = torch.device(device)
@@ -557,26 +639,30 @@ def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None
     cat_index = {c: i for i, c in enumerate(cat_ids)}
     label_to_cat = {label: cat_index[json_id] for label, json_id in dataset.contiguous_category_id_to_json_id.items()}
     by_image = {dataset.id_to_img_map[idx]: pred for idx, pred in enumerate(predictions)}
-    with_masks = iou_type == "segm"
-    dets = [_detections(by_image.get(image["id"]), image, label_to_cat, with_masks) for image in images]
-    return _score_rows(images, dets, iou_type, device, budget, timer, max_images), cat_ids
+    dets = [_detections(by_image.get(image["id"]), image, label_to_cat, types[0] != "bbox") for image in images]
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio), cat_ids
 
 
-def _score_rows(images, dets, iou_type, device, budget, timer, max_images):
-    """The match tables of the images' ground truth and detection rows, chunk by chunk."""
+def _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+    """The match tables of the images' ground truth and detection rows, chunk by chunk ({name: tables} for a tuple)."""
     if budget is None:
         budget = torch.cuda.mem_get_info(device)[0] // 4
-    parts = [score_chunk([images[i] for i in chunk], [dets[i] for i in chunk], iou_type, device, timer)
-             for chunk in _chunks(images, dets, iou_type == "segm", budget, max_images)]
-    return concatenate_tables(parts)
+    types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type)
+    parts = [score_chunk([images[i] for i in chunk], [dets[i] for i in chunk], iou_type, device, timer, boundary_dilation_ratio)
+             for chunk in _chunks(images, dets, types[0] != "bbox", budget, max_images, "boundary" in types)]
+    if isinstance(iou_type, str):
+        return concatenate_tables(parts)
+    return {name: concatenate_tables([part[name] for part in parts]) for name in types}
 
 
-def results_match_tables(dataset, results, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None):
+def results_match_tables(dataset, results, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None,
+                         boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
     """``match_tables`` for the detections of a results file (``results``: what ``load_coco_results`` takes)."""
+    types = _job_types(iou_type, "evaluate_coco_results")
     device = torch.device(device)
     cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset)
-    dets = load_coco_results(dataset, results, iou_type)
-    return _score_rows(images, dets, iou_type, device, budget, timer, max_images), cat_ids
+    dets = load_coco_results(dataset, results, types[0])
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio), cat_ids
 
 
 def _scoring_device(device, who):
@@ -588,16 +674,21 @@ def _scoring_device(device, who):
 
 def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth=None):
     """{iou_type: ``summarize`` of ``accumulate`` of ``tables_of(iou_type, ground truth)``} with the dataset's names,
-    splits and class order; ``recall``: followed by ``summarize_recall`` of ``accumulate_recall`` of the same tables."""
-    results = OrderedDict()
+    splits and class order; ``recall``: followed by ``summarize_recall`` of ``accumulate_recall`` of the same tables.
+    When segm and boundary are both asked for, ``tables_of`` is called ONCE for the two, with the tuple ("segm",
+    "boundary"), and returns {name: tables} (``_jobs``)."""
+    results, scored = OrderedDict(), {}
     ground_truth = ground_truth if ground_truth is not None else _ground_truth(dataset)
     cat_ids = ground_truth[0]
     cat_index = {c: i for i, c in enumerate(cat_ids)}
     splits = OrderedDict((split, [cat_index[c] for c in ids]) for split, ids in dataset.class_splits.items())
     class_order = [cat_index[c] for c in dataset.categories if c in cat_index]
     with torch.cuda.device(device):
+        for job in _jobs(iou_types):
+            tables, _ = tables_of(job, ground_truth)
+            scored.update({job: tables} if isinstance(job, str) else tables)
         for iou_type in iou_types:
-            tables, _ = tables_of(iou_type, ground_truth)
+            tables = scored[iou_type]
             results[iou_type] = summarize(accumulate(tables, len(cat_ids)), [dataset.categories[c] for c in cat_ids], splits,
                                           class_order)
             if recall:
@@ -606,31 +697,49 @@ def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth
     return results
 
 
-def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda", recall=False):
+def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda", recall=False,
+                  boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
     """{iou_type: OrderedDict of AP, AP50, AP75, APs, APm, APl, AP50_class_<name> per category (in the order of
     ``dataset.categories``, as ``COCOResults.update`` iterates) and AP50_split_<split> per key of ``dataset.class_splits``}
     for ``predictions``: the list ``inference()`` returns or ``torch.load`` gives from ``predictions.pth`` (BoxLists in
     dataset-index order, fields ``scores``, ``labels`` and -- for segm -- ``mask`` [K, 1, M, M]).  ``recall``: followed by
     AR1, AR10, AR100, ARs, ARm, ARl and AR100_split_<split> (``summarize_recall``).  ``device``: the HIP device that scores;
-    there is no host-only scoring."""
+    there is no host-only scoring.
+
+    ``"boundary"`` among ``iou_types`` is Boundary AP (Cheng et al., CVPR 2021): segm's keys from a matching on min(mask
+    IoU, boundary IoU), the boundary band ``boundary_dilation_ratio`` of the image diagonal deep -- the rule is written
+    out in include/ovis_hip.h.  Beside segm it costs no second paste / rasterise / pack, and leaves segm's numbers alone."""
     device = _scoring_device(device, "evaluate_coco")
+    for iou_type in iou_types:
+        _check_iou_type(iou_type, "evaluate_coco")
     return _summaries(dataset, iou_types, device,
-                      lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt), recall)
+                      lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt,
+                                                        boundary_dilation_ratio=boundary_dilation_ratio), recall)
 
 
-def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="cuda", recall=False):
+def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="cuda", recall=False,
+                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
     """``evaluate_coco``'s numbers, in the same structure, for detections that come from COCO results files: ``results`` is
-    {iou_type: a path or the parsed list} (``load_coco_results``); an iou_type it does not have is skipped.  Whatever wrote
-    the files -- ``export_coco_results``, the reference, another tool -- nothing but the annotation file is needed beside
-    them.  ``recall``: as in ``evaluate_coco``.  ``device``: the HIP device that decodes the masks and scores; there is no
-    host-only scoring."""
+    {iou_type: a path or the parsed list} (``load_coco_results``); an iou_type it does not have is skipped -- but boundary
+    reads the ``"boundary"`` entry when there is one and else the ``"segm"`` one: it scores the same ``segm.json``.  Whatever
+    wrote the files -- ``export_coco_results``, the reference, another tool -- nothing but the annotation file is needed
+    beside them.  ``recall``, ``boundary_dilation_ratio``: as in ``evaluate_coco``.  ``device``: the HIP device that decodes
+    the masks and scores; there is no host-only scoring."""
     device = _scoring_device(device, "evaluate_coco_results")
     for iou_type in results:
-        if iou_type not in ("bbox", "segm"):
-            raise ValueError(f"evaluate_coco_results: iou_type '{iou_type}' is not supported (bbox, segm)")
-    return _summaries(dataset, [t for t in iou_types if t in results], device,
-                      lambda iou_type, gt: results_match_tables(dataset, results[iou_type], iou_type, device, ground_truth=gt),
-                      recall)
+        _check_iou_type(iou_type, "evaluate_coco_results")
+    files = dict(results)
+    if "boundary" not in files and "segm" in files:
+        files["boundary"] = files["segm"]
+    iou_types = [t for t in iou_types if t in files]
+    if all(t in iou_types for t in MASK_IOU_TYPES) and files["boundary"] is not files["segm"]:  # two files: two passes
+        return OrderedDict((t, evaluate_coco_results(dataset, {t: files[t]}, (t,), device, recall, boundary_dilation_ratio)[t])
+                           for t in iou_types)
+
+    def tables_of(job, gt):
+        return results_match_tables(dataset, files[job if isinstance(job, str) else job[0]], job, device, ground_truth=gt,
+                                    boundary_dilation_ratio=boundary_dilation_ratio)
+    return _summaries(dataset, iou_types, device, tables_of, recall)
 
 
 # ---- every rank scores what it predicted: only match tables travel --------------------------------------------------------
@@ -678,7 +787,8 @@ def merge_shard_tables(parts):
     return concatenate_tables(ordered)
 
 
-def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm"), device="cuda", recall=False):
+def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm"), device="cuda", recall=False,
+                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
     """``evaluate_coco``'s numbers without gathering the predictions: ``local_predictions`` is THIS rank's {dataset index:
     BoxList} (what ``engine.inference.compute_on_dataset`` returns), every rank calls this, rank 0 gets the OrderedDict and
     the others None.  The ranks exchange their index lists; ``shard_owners`` says who scores an image that sits on two of
@@ -689,8 +799,7 @@ def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm")
     ``match_tables`` has.  One process: the same code with one shard."""
     device = _scoring_device(device, "evaluate_coco_sharded")
     for iou_type in iou_types:
-        if iou_type not in ("bbox", "segm"):
-            raise ValueError(f"evaluate_coco_sharded: iou_type '{iou_type}' is not supported (bbox, segm)")
+        _check_iou_type(iou_type, "evaluate_coco_sharded")
     world, rank = comm.get_world_size(), comm.get_rank()
     index_lists = [sorted(int(i) for i in local_predictions)]
     if index_lists[0] and not 0 <= index_lists[0][0] <= index_lists[0][-1] < len(dataset):
@@ -708,21 +817,24 @@ def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm")
     by_image = {dataset.id_to_img_map[idx]: local_predictions[idx] for idx in index_lists[rank]}
     merged = {}
     with torch.cuda.device(device):
-        for iou_type in iou_types:
-            dets = [_detections(by_image.get(image["id"]), image, label_to_cat, iou_type == "segm") for image in images]
-            tables = _score_rows(images, dets, iou_type, device, None, None, None)
+        for job in _jobs(iou_types):  # segm and boundary together: one pass over the mask words, two tables
+            dets = [_detections(by_image.get(image["id"]), image, label_to_cat, job != "bbox") for image in images]
+            scored = _score_rows(images, dets, job, device, None, None, None, boundary_dilation_ratio)
             problems = np.asarray([len(np.union1d(det["cats"], image["cats"])) for image, det in zip(images, dets)],
                                   dtype=np.int64)
-            tables["image"] = np.repeat(np.asarray([image["id"] for image in images], dtype=np.int64), problems)
-            parts = [tables]
-            if world > 1:
-                parts = [None] * world
-                dist.all_gather_object(parts, tables)
-            if rank == 0:
-                merged[iou_type] = merge_shard_tables(parts)
+            for iou_type, tables in ({job: scored} if isinstance(job, str) else scored).items():
+                tables["image"] = np.repeat(np.asarray([image["id"] for image in images], dtype=np.int64), problems)
+                parts = [tables]
+                if world > 1:
+                    parts = [None] * world
+                    dist.all_gather_object(parts, tables)
+                if rank == 0:
+                    merged[iou_type] = merge_shard_tables(parts)
     if rank != 0:
         return None
-    return _summaries(dataset, iou_types, device, lambda iou_type, gt: (merged[iou_type], cat_ids), recall, ground_truth)
+    return _summaries(dataset, iou_types, device,
+                      lambda job, gt: (merged[job] if isinstance(job, str) else {t: merged[t] for t in job}, cat_ids), recall,
+                      ground_truth)
 
 
 def annotation_dataset(ann_file):

@@ -90,10 +90,20 @@ def run_rpn_recall(cfg, model, catalog, device, logger=None):
     return results
 
 
+def scored_iou_types(cfg, boundary_ap=False):
+    """The tasks of a scoring run: bbox, segm when MODEL.MASK_ON, and -- ``boundary_ap`` -- boundary behind segm (Boundary AP
+    is a mask metric: without MODEL.MASK_ON it is a ValueError)."""
+    if boundary_ap and not cfg.MODEL.MASK_ON:
+        raise ValueError("Boundary AP scores the mask head's masks: set MODEL.MASK_ON True")
+    return ("bbox",) + (("segm",) if cfg.MODEL.MASK_ON else ()) + (("boundary",) if boundary_ap else ())
+
+
 def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
-                 export_results=False, recall=False, vote_thresh=None, average_masks=False):
+                 export_results=False, recall=False, vote_thresh=None, average_masks=False, boundary_ap=False):
     """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}.  ``vote_thresh`` /
-    ``average_masks``: box voting and view-averaged masks of multi-scale / flip testing (engine/bbox_aug.py)."""
+    ``average_masks``: box voting and view-averaged masks of multi-scale / flip testing (engine/bbox_aug.py);
+    ``boundary_ap``: with ``evaluate``, a ``boundary`` task behind ``segm`` (engine/coco_eval.py: Boundary AP)."""
+    iou_types = scored_iou_types(cfg, boundary_ap and evaluate)
     transform = build_transforms(cfg, is_train=False)
     results = {}
     for name in cfg.DATASETS.TEST:
@@ -115,19 +125,19 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
             raise ValueError("run_datasets: export_results=True writes OUTPUT_DIR/inference/<name>/bbox.json and segm.json: "
                              "set OUTPUT_DIR")
         if evaluate and results[name] is not None:
-            save_evaluation(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",), device,
-                            logger or logging.getLogger("ovis.inference"), recall)
+            save_evaluation(dataset, results[name], out, iou_types, device, logger or logging.getLogger("ovis.inference"),
+                            recall)
         if export_results and results[name] is not None:
             coco_results.export_coco_results(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",),
                                              device)
     return results
 
 
-def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_embeddings, logger=None):
+def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_embeddings, logger=None, boundary_ap=False):
     """The SOLVER.TEST_PERIOD evaluation of a live training process, behind iteration ``iteration`` (trainer.py:174-203):
     every DATASETS.TEST name through the model's evaluation pass on this rank's shard, scored where it was predicted
-    (``coco_eval.evaluate_coco_sharded``: AP keys of ``bbox``, and of ``segm`` when MODEL.MASK_ON) -> {name: the numbers
-    (rank 0) or None}.  Rank 0 logs the table under the iteration and writes
+    (``coco_eval.evaluate_coco_sharded``: AP keys of ``bbox``, of ``segm`` when MODEL.MASK_ON, and of ``boundary`` behind it
+    when ``boundary_ap``) -> {name: the numbers (rank 0) or None}.  Rank 0 logs the table under the iteration and writes
     ``OUTPUT_DIR/inference/<name>/coco_results_<iteration:07d>.json`` in the structure of ``coco_results.json``; no
     predictions are gathered or saved.  The caller has joined whatever else runs the model (``PipelinedTrainer.drain``).
     On return the model is as it was: every module's mode, ``train_class_embeddings`` as its class matrix (trainer.py:198-202),
@@ -141,7 +151,7 @@ def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_emb
     if device.type != "cuda":
         raise ValueError("evaluate_in_training scores on the HIP device (mask IoU and matching have no host implementation)")
     logger = logger or logging.getLogger("ovis.trainer")
-    iou_types = ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",)
+    iou_types = scored_iou_types(cfg, boundary_ap)
     comm.synchronize()
     modes = [(m, m.training) for m in model.modules()]
     host_rng, device_rng = torch.get_rng_state(), torch.cuda.get_rng_state(device)

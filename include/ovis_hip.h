@@ -933,6 +933,37 @@ int ovis_coco_match(const double* iou, const int64_t* problems, int num_problems
                     const double* thresholds, int num_thresholds, long num_dets, long num_gts, int32_t* dt_match,
                     uint8_t* dt_ignore, uint8_t* gt_ignore, void* stream);
 
+/* Boundary IoU for Boundary AP (csrc/coco_boundary.hip; Cheng et al., "Boundary IoU", CVPR 2021 -- the reference does not
+ * score it; neither pycocotools nor boundary-iou-api is a dependency, so the rule is restated and THIS TEXT is the
+ * contract).  For a binary mask m of a height x width image:
+ *   1. d = max(1, int(round(0.02 * sqrt(height^2 + width^2)))), Python 3's round (half to even), computed by the CALLER
+ *      and passed as `dilation` (15x20: 1, 45x60: 2, 75x100: 2, 70x129: 3, 480x640: 16, 800x1333: 31, 1x1: 1).
+ *   2. eroded(m) = d iterations of a 3x3 erosion with everything outside the image counted as 0 (mask_to_boundary's
+ *      one-pixel zero border and cv2.erode(iterations = d)): pixel (y, x) survives iff y - d >= 0, y + d < height,
+ *      x - d >= 0, x + d < width and all (2d + 1)^2 pixels of the square around it are set.
+ *   3. boundary(m) = m & ~eroded(m): a mask the image border cuts off has boundary along the border.
+ *   4. boundary_iou(D, G) = |b(D) & b(G)| / |b(D) | b(G)|, for a crowd G over |b(D)| -- ovis_coco_mask_iou_f64's forms on
+ *      the boundary words, a zero denominator gives 0 -- and the IoU that is matched is min(mask_iou, boundary_iou),
+ *      for crowds too.  Areas (the area ranges of ovis_coco_match) stay the MASK areas.
+ * ovis_coco_boundary_words_u64: words [num, ceil(height * width / 64)] in ovis_coco_pack_masks_u64's layout (tail bits
+ *   zero), all masks of one image size -> boundary_words (same shape; every word is written, tail bits zero) and
+ *   boundary_areas [num] = their set bits.  scratch: num * ceil(height * width / 64) words the call may overwrite (the
+ *   row-eroded words).  Three launches per 65535 masks, enqueue only, vector loads and stores, no atomics, no host read:
+ *   the same bits on every call.  Any dilation >= 1 is served (2 * dilation + 1 > 64, and dilation >= min(height, width)
+ *   / 2, where nothing survives and the boundary is the mask).  OVIS_EINVAL: num < 0, height < 1, width < 1,
+ *   dilation < 1, a null pointer with num > 0; OVIS_ERANGE: height * width > 0x7fffffef (the encoder's pixel bound);
+ *   num == 0: OVIS_OK without a launch.
+ * ovis_coco_boundary_iou_f64: ovis_coco_mask_iou_f64 with the boundary words / areas of both sides beside the mask
+ *   words / areas (the same `problems` table addresses both word buffers of a side): writes min(mask_iou, boundary_iou)
+ *   to the flat IoU buffer ovis_coco_match consumes.  Both ratios are integer / integer converted to fp64: exact. */
+int ovis_coco_boundary_words_u64(const uint64_t* words, int num, int height, int width, int dilation, uint64_t* scratch,
+                                 uint64_t* boundary_words, int64_t* boundary_areas, void* stream);
+int ovis_coco_boundary_iou_f64(const uint64_t* det_words, const uint64_t* det_boundary_words, const int64_t* det_areas,
+                               const int64_t* det_boundary_areas, const uint64_t* gt_words,
+                               const uint64_t* gt_boundary_words, const int64_t* gt_areas,
+                               const int64_t* gt_boundary_areas, const uint8_t* gt_crowd, const int64_t* problems,
+                               int num_problems, long max_pairs, double* iou, void* stream);
+
 /* ovis_coco_rle_* / ovis_coco_runs_to_words (csrc/coco_rle_decode.hip): COCO run-length encodings -- the `segmentation` of a
  * results file (what mb/data/datasets/evaluation/coco/coco_eval.py:139-144 writes and COCOeval reads back through
  * pycocotools' rleFrString / rleDecode) or of an RLE annotation -- as the bit words of ovis_coco_pack_masks_u64, for `num`

@@ -1,11 +1,15 @@
 """Time of COCO scoring (engine/coco_eval.py) for one chunk of synthetic images, split by stage:
 
     python tools/bench_coco_eval.py [--images 32] [--height 480] [--width 640] [--detections 100] [--ground-truths 20]
+        [--boundary] [--repeats 1]
 
 Seeded, no model: every image gets ``--detections`` random boxes with 28 x 28 mask maps over 10 categories and
 ``--ground-truths`` random hexagons.  The whole set is scored as ONE chunk, once to warm up (code objects, allocator) and
 once under device events around the paste, rasterise, pack, IoU and match calls; the host accumulate / summarise is timed
-with the wall clock.  Prints one JSON line per IoU type.
+with the wall clock.  Prints one JSON line per IoU type.  ``--boundary`` adds a third pass, segm and Boundary AP scored
+TOGETHER from one set of mask words (``iou_type`` "segm+boundary": what ``--boundary-ap`` costs on top is that line minus the
+segm line; its stages ``boundary`` -- the erosion -- and ``boundary_iou`` are new, the others are segm's).  ``--repeats N``
+times every pass N times and prints each: the spread is the noise a difference has to clear.
 """
 import argparse
 import json
@@ -68,27 +72,36 @@ def main():
     parser.add_argument("--width", type=int, default=640)
     parser.add_argument("--detections", type=int, default=100)
     parser.add_argument("--ground-truths", type=int, default=20)
+    parser.add_argument("--boundary", action="store_true", help="also time segm and Boundary AP scored together")
+    parser.add_argument("--repeats", type=int, default=1, help="timed runs per pass, each printed")
     args = parser.parse_args()
     device = torch.device("cuda", torch.cuda.current_device())
     with tempfile.TemporaryDirectory() as folder:
         dataset, predictions = make_case(folder, args.images, args.height, args.width, args.detections, args.ground_truths)
     budget = 1 << 62   # one chunk
-    for iou_type in ("bbox", "segm"):
+    passes = ["bbox", "segm"] + ([("segm", "boundary")] if args.boundary else [])
+    for iou_type in passes:
         coco_eval.match_tables(dataset, predictions, iou_type, device, budget)   # warm-up
-        torch.cuda.synchronize()
-        timer = {}
-        t0 = time.perf_counter()
-        tables, cat_ids = coco_eval.match_tables(dataset, predictions, iou_type, device, budget, timer)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        results = coco_eval.summarize(coco_eval.accumulate(tables, len(cat_ids)), [str(c) for c in cat_ids], {})
-        t2 = time.perf_counter()
-        stages = {name: round(sum(s.elapsed_time(e) for s, e in events), 3) for name, events in timer.items()}
-        print(json.dumps({"iou_type": iou_type, "images": args.images, "size": [args.height, args.width],
-                          "detections": int(tables["det_start"][-1]), "ground_truths": int(tables["gt_start"][-1]),
-                          "problems": len(tables["category"]), "device_ms": stages,
-                          "chunk_wall_ms": round((t1 - t0) * 1e3, 2), "host_accumulate_ms": round((t2 - t1) * 1e3, 2),
-                          "AP": results["AP"]}))
+    for _ in range(args.repeats):   # the passes alternate, so a drift of the machine meets all of them
+        for iou_type in passes:
+            torch.cuda.synchronize()
+            timer = {}
+            t0 = time.perf_counter()
+            tables, cat_ids = coco_eval.match_tables(dataset, predictions, iou_type, device, budget, timer)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            tables = {iou_type: tables} if isinstance(iou_type, str) else tables
+            results = {name: coco_eval.summarize(coco_eval.accumulate(t, len(cat_ids)), [str(c) for c in cat_ids], {})
+                       for name, t in tables.items()}
+            t2 = time.perf_counter()
+            stages = {name: round(sum(s.elapsed_time(e) for s, e in events), 3) for name, events in timer.items()}
+            first = next(iter(tables.values()))
+            line = {"iou_type": "+".join(tables), "images": args.images, "size": [args.height, args.width],
+                    "detections": int(first["det_start"][-1]), "ground_truths": int(first["gt_start"][-1]),
+                    "problems": len(first["category"]), "device_ms": stages, "device_ms_total": round(sum(stages.values()), 3),
+                    "chunk_wall_ms": round((t1 - t0) * 1e3, 2), "host_accumulate_ms": round((t2 - t1) * 1e3, 2)}
+            line.update({"AP" if isinstance(iou_type, str) else f"AP_{name}": r["AP"] for name, r in results.items()})
+            print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":

@@ -16,7 +16,9 @@ per class and per seen / unseen split), logs the reference's ``Task: ... / names
 ``<OUTPUT_DIR>/inference/<name>/coco_results.json``; it needs OUTPUT_DIR and MODEL.DEVICE cuda -- there is no host-only
 scoring.  ``--recall`` (with ``--evaluate``) completes the reference's table: a ``box_proposal`` task first -- AR@100, ARs@100,
 ... ARl@1000 of the detections scored as class-agnostic proposals, and AR@<limit>_split_<split> (engine/proposal_recall.py, matched
-on the device) -- and COCO's AR1 / AR10 / AR100 / ARs / ARm / ARl plus AR100_split_<split> behind the AP keys.  ``--rpn-recall``
+on the device) -- and COCO's AR1 / AR10 / AR100 / ARs / ARm / ARl plus AR100_split_<split> behind the AP keys.
+``--boundary-ap`` (with ``--evaluate`` and MODEL.MASK_ON) adds a ``boundary`` task behind ``segm``: Boundary AP (Cheng et al.,
+CVPR 2021; engine/coco_eval.py), segm's keys from a matching on min(mask IoU, boundary IoU).  ``--rpn-recall``
 is a run of its own: backbone + RPN alone (``model.propose``), the proposals gathered like detections into
 ``<OUTPUT_DIR>/inference/<name>/proposals.pth`` and scored by ``objectness`` as an ``rpn_proposal`` task, written to
 ``rpn_recall.json`` -- whether the RPN proposes the unseen classes at all.  ``--export-results`` (rank 0, after the gather, independent of ``--evaluate``) writes the detections as COCO results
@@ -77,6 +79,10 @@ def main(argv=None):
                         help="with --evaluate: the reference's whole table -- a box_proposal task first (AR@100 ... ARl@1000 of "
                              "the detections scored as proposals, and per split) and COCO AR1 / AR10 / AR100 / ARs / ARm / ARl "
                              "and AR100 per split behind the AP keys")
+    parser.add_argument("--boundary-ap", action="store_true",
+                        help="with --evaluate and MODEL.MASK_ON: also score Boundary AP (Cheng et al., CVPR 2021) -- a boundary "
+                             "task behind segm in the table and in coco_results.json: segm's keys, matched on min(mask IoU, "
+                             "boundary IoU)")
     parser.add_argument("--rpn-recall", action="store_true",
                         help="run backbone + RPN alone over every test set, save the proposals as "
                              "OUTPUT_DIR/inference/<name>/proposals.pth and score their recall by objectness on the device: an "
@@ -105,6 +111,10 @@ def main(argv=None):
                      "set MODEL.DEVICE cuda")
     if args.recall and not args.evaluate:
         parser.error("--recall adds the recall numbers to what --evaluate scores: give --evaluate too")
+    if args.boundary_ap and not args.evaluate:
+        parser.error("--boundary-ap adds the boundary task to what --evaluate scores: give --evaluate too")
+    if args.boundary_ap and not cfg.MODEL.MASK_ON:
+        parser.error("--boundary-ap scores the mask head's masks: set MODEL.MASK_ON True")
     if args.rpn_recall and not cfg.OUTPUT_DIR:
         parser.error("--rpn-recall writes OUTPUT_DIR/inference/<name>/proposals.pth and rpn_recall.json: set OUTPUT_DIR")
     if args.rpn_recall and cfg.MODEL.DEVICE != "cuda":
@@ -154,7 +164,7 @@ def main(argv=None):
     else:
         for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
                                         args.evaluate, args.export_results, args.recall, args.bbox_vote,
-                                        args.mask_aug).items():
+                                        args.mask_aug, args.boundary_ap).items():
             if preds is not None:
                 logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:

@@ -6,9 +6,13 @@ without a model, a configuration or the images (engine/coco_eval.py: ``evaluate_
 
   python tools/score_results.py --ann-file instances_val.json --results-dir OUTPUT_DIR/inference/<name>
   python tools/score_results.py --ann-file instances_val.json --segm segm.json --output scores.json
+  python tools/score_results.py --ann-file instances_val.json --segm segm.json --boundary-ap
 
 Prints the ``Task: ... / names / values`` table ``--evaluate`` logs; ``--output`` writes the numbers as
-``coco_results.json`` has them.  ``--recall`` adds COCO's AR numbers behind the AP keys, from the same match tables.  There is no host-only scoring: the device must be a HIP device.
+``coco_results.json`` has them.  ``--recall`` adds COCO's AR numbers behind the AP keys, from the same match tables.  ``--boundary-ap`` adds a ``boundary`` task
+behind ``segm``: Boundary AP (Cheng et al., CVPR 2021) of the same ``segm.json`` -- segm's keys from a matching on min(mask IoU,
+boundary IoU), the rule as include/ovis_hip.h states it (not compared with boundary-iou-api's output); the masks are decoded
+once for both.  There is no host-only scoring: the device must be a HIP device.
 """
 import argparse
 import json
@@ -20,7 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-IOU_TYPES = ("bbox", "segm")
+IOU_TYPES = ("bbox", "segm")  # the results files there are; --boundary-ap scores segm.json a second way
 
 
 def main(argv=None):
@@ -33,6 +37,9 @@ def main(argv=None):
     parser.add_argument("--recall", action="store_true",
                         help="add COCO's AR1 / AR10 / AR100 / ARs / ARm / ARl and AR100 per split behind the AP keys (results "
                              "files are capped per category, so they are not proposal lists: no box_proposal task)")
+    parser.add_argument("--boundary-ap", action="store_true",
+                        help="also score Boundary AP (Cheng et al., CVPR 2021) from the segm results file: a boundary task "
+                             "behind segm -- segm's keys, matched on min(mask IoU, boundary IoU)")
     parser.add_argument("--device", default="cuda", help="the HIP device that scores (cuda, cuda:1, ...)")
     args = parser.parse_args(argv)
     files = {}
@@ -44,6 +51,9 @@ def main(argv=None):
             files[iou_type] = path
     if not files:
         parser.error("no results file: give --bbox, --segm or a --results-dir that holds bbox.json or segm.json")
+    if args.boundary_ap and "segm" not in files:
+        parser.error("--boundary-ap scores the masks of a segm results file: give --segm or a --results-dir that holds "
+                     "segm.json")
     for path in [args.ann_file] + list(files.values()):
         if not os.path.exists(path):
             parser.error(f"{path} does not exist")
@@ -58,7 +68,8 @@ def main(argv=None):
     from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval
 
     dataset = coco_eval.annotation_dataset(args.ann_file)
-    results = coco_eval.evaluate_coco_results(dataset, files, IOU_TYPES, device, recall=args.recall)
+    iou_types = IOU_TYPES + (("boundary",) if args.boundary_ap else ())
+    results = coco_eval.evaluate_coco_results(dataset, files, iou_types, device, recall=args.recall)
     print(coco_eval.format_results(results))
     if args.output:
         with open(args.output, "w") as f:
