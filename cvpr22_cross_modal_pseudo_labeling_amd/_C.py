@@ -2103,6 +2103,40 @@ def coco_match(iou, problems, det_areas, gt_areas, gt_crowd, area_ranges, thresh
     return dt_match, dt_ignore, gt_ignore
 
 
+def lvis_match(iou, problems, det_areas, gt_areas, gt_ignore_in, problem_not_exhaustive, area_ranges, thresholds):
+    """The matching of LVIS-style federated scoring (rules 7 and 8 of include/ovis_hip.h) for every problem, area range and
+    IoU threshold in one launch (``ovis_lvis_match``): ``coco_match``'s inputs and outputs, with gt_ignore_in [G] uint8 (the
+    ground truths' input ignore flags; a matched ground truth is never matched again) in place of gt_crowd, and
+    problem_not_exhaustive [P] uint8, one flag per row of ``problems``, ORed into the ignore flag of that problem's
+    unmatched detections.  ``iou`` is the non-crowd form: the buffer of ``coco_box_iou`` / ``coco_mask_iou`` /
+    ``coco_boundary_iou`` called with all-zero crowd flags."""
+    iou, det_areas, gt_areas = _dev(iou, "iou", torch.float64), _dev(det_areas, "det_areas", torch.float64), \
+        _dev(gt_areas, "gt_areas", torch.float64)
+    gt_ignore_in = _dev(gt_ignore_in, "gt_ignore_in", torch.uint8)
+    problem_not_exhaustive = _dev(problem_not_exhaustive, "problem_not_exhaustive", torch.uint8)
+    area_ranges, thresholds = _dev(area_ranges, "area_ranges", torch.float64), _dev(thresholds, "thresholds", torch.float64)
+    if area_ranges.dim() != 2 or area_ranges.shape[1] != 2 or thresholds.dim() != 1 or gt_ignore_in.shape != gt_areas.shape \
+            or det_areas.dim() != 1 or gt_areas.dim() != 1 or not area_ranges.numel() or not thresholds.numel() \
+            or problem_not_exhaustive.shape != (len(problems),):
+        raise RuntimeError("lvis_match: expected det_areas [D], gt_areas / gt_ignore_in [G], problem_not_exhaustive [P], "
+                           "area_ranges [A,2], thresholds [T]")
+    d, g, a, t = det_areas.numel(), gt_areas.numel(), area_ranges.shape[0], thresholds.numel()
+    problems.check("lvis_match", d, g, iou_numel=iou.numel())
+    dt_match = torch.full((a, t, d), -1, dtype=torch.int32, device=iou.device)
+    dt_ignore = torch.zeros((a, t, d), dtype=torch.bool, device=iou.device)
+    gt_ignore = torch.zeros((a, g), dtype=torch.bool, device=iou.device)
+    if len(problems) == 0:
+        return dt_match, dt_ignore, gt_ignore
+    with _on(iou.device):
+        rc = _L.ovis_lvis_match(iou.data_ptr() if iou.numel() else 0, problems.dev.data_ptr(), len(problems), problems.max_gts,
+                                det_areas.data_ptr() if d else 0, gt_areas.data_ptr() if g else 0,
+                                gt_ignore_in.data_ptr() if g else 0, problem_not_exhaustive.data_ptr(), area_ranges.data_ptr(),
+                                a, thresholds.data_ptr(), t, d, g, dt_match.data_ptr() if d else 0,
+                                dt_ignore.data_ptr() if d else 0, gt_ignore.data_ptr() if g else 0, _stream())
+    _lib.check(rc, "lvis_match")
+    return dt_match, dt_ignore, gt_ignore
+
+
 COCO_RLE_STATUS = {_lib.OVIS_COCO_RLE_BAD_CHAR: "a character outside '0'..'o'",
                    _lib.OVIS_COCO_RLE_UNTERMINATED: "the last value is not terminated",
                    _lib.OVIS_COCO_RLE_OVERFLOW: "a value does not fit 32 bits",

@@ -44,6 +44,15 @@ they have not been compared with boundary-iou-api's output.  It works on the wor
 9 / 8 (the boundary words and the erosion's scratch).  Asked for together, segm and boundary share one paste / rasterise /
 decode / pack per chunk, and segm's tables are those of a run without boundary, bit for bit.
 
+LVIS.  ``rules="lvis"`` (default ``"coco"``: nothing changes) scores an annotation file that is only FEDERATEDLY annotated -- its
+images carry ``neg_category_ids`` and ``not_exhaustive_category_ids``, its categories ``frequency`` -- by the ten rules restated in
+include/ovis_hip.h (lvis-api is not a dependency; the numbers follow THAT text and have not been compared with lvis-api's own
+output): the image's 300 best detections over all categories instead of 100 per category, detections of categories nobody
+looked for in the image dropped (``_kept_rows``), ``ignore`` keys instead of crowds, a matching that never re-matches a ground
+truth and ignores the unmatched detections of not-exhaustive categories (``_C.lvis_match``, csrc/lvis_eval.hip), no maxDets
+dimension (``accumulate_lvis``) and APr / APc / APf beside the COCO keys (``summarize_lvis``).  Every iou_type takes the
+keyword, boundary included; everything image-sized is shared with COCO scoring.
+
 SHARDED.  ``evaluate_coco_sharded`` is ``evaluate_coco`` for a caller that holds one rank's {dataset index: BoxList} instead of
 the gathered list (a training run's periodic evaluation, engine/evaluation.py): an image's matching does not depend on any
 other image, so every rank scores the images it predicted on its own device and only the match tables go to rank 0, where
@@ -76,6 +85,16 @@ MAX_EXPORT_MASKS = 8192
 IOU_TYPES = ("bbox", "segm", "boundary")
 MASK_IOU_TYPES = ("segm", "boundary")  # scored from the packed mask words: one pass over a chunk serves both
 BOUNDARY_DILATION_RATIO = 0.02
+RULES = ("coco", "lvis")  # lvis: LVIS-style federated scoring, the ten rules of include/ovis_hip.h
+LVIS_MAX_DETS = 300  # per image, over all categories together (rule 3)
+LVIS_METRICS = METRICS + ("APr", "APc", "APf")
+LVIS_FREQUENCIES = ("r", "c", "f")
+LVIS_RECALL_METRICS = ("AR@300", "ARs@300", "ARm@300", "ARl@300")
+
+
+def _check_rules(rules, who):
+    if rules not in RULES:
+        raise ValueError(f"{who}: rules '{rules}' is not supported ({', '.join(RULES)})")
 
 
 def _check_iou_type(iou_type, who):
@@ -135,17 +154,23 @@ def accumulate(tables, num_categories):
                 tp_sum = np.cumsum(np.logical_and(dtm, np.logical_not(dt_ig)), axis=1).astype(dtype=np.float64)
                 fp_sum = np.cumsum(np.logical_and(np.logical_not(dtm), np.logical_not(dt_ig)), axis=1).astype(dtype=np.float64)
                 for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
-                    nd = len(tp)
-                    rc = tp / npig
-                    pr = tp / (fp + tp + np.spacing(1))
-                    q = np.zeros((num_r,))
-                    if nd:  # the right-to-left envelope: pr[i - 1] = max(pr[i - 1], pr[i])
-                        pr = np.maximum.accumulate(pr[::-1])[::-1]
-                    inds = np.searchsorted(rc, RECALL_THRESHOLDS, side="left")
-                    ok = inds < nd  # a recall point past the last detection keeps precision 0
-                    q[ok] = pr[inds[ok]]
-                    precision[t, :, k, a, m] = q
+                    precision[t, :, k, a, m] = _sampled_precision(tp, fp, npig)
     return precision
+
+
+def _sampled_precision(tp, fp, npig):
+    """The precision at the 101 recall thresholds, from the running tp / fp sums (fp64 [n]) of one category, area range and
+    IoU threshold over its score-ordered non-ignored detections and its ``npig`` non-ignored ground truths."""
+    nd = len(tp)
+    rc = tp / npig
+    pr = tp / (fp + tp + np.spacing(1))
+    q = np.zeros((len(RECALL_THRESHOLDS),))
+    if nd:  # the right-to-left envelope: pr[i - 1] = max(pr[i - 1], pr[i])
+        pr = np.maximum.accumulate(pr[::-1])[::-1]
+    inds = np.searchsorted(rc, RECALL_THRESHOLDS, side="left")
+    ok = inds < nd  # a recall point past the last detection keeps precision 0
+    q[ok] = pr[inds[ok]]
+    return q
 
 
 def _mean(s):
@@ -225,6 +250,66 @@ def summarize_recall(recall, category_names, class_splits):
     return res
 
 
+def accumulate_lvis(tables, num_categories):
+    """Rule 9 of include/ovis_hip.h -> (precision fp64 [T, R, K, A], recall fp64 [T, K, A]) from the match tables of
+    ``rules="lvis"`` (the structure ``accumulate`` takes; a problem holds every detection that survived the image's cap and
+    the federated filter -- there is no maxDets dimension).  -1: the (category, area) has no non-ignored ground truth."""
+    cat = np.asarray(tables["category"], dtype=np.int64)
+    det_start, gt_start = np.asarray(tables["det_start"], dtype=np.int64), np.asarray(tables["gt_start"], dtype=np.int64)
+    scores_all = np.asarray(tables["scores"], dtype=np.float64)
+    matched_all, dt_ignore_all = np.asarray(tables["dt_match"]) >= 0, np.asarray(tables["dt_ignore"], dtype=bool)
+    gt_ignore_all = np.asarray(tables["gt_ignore"], dtype=bool)
+    det_cat, gt_cat = np.repeat(cat, np.diff(det_start)), np.repeat(cat, np.diff(gt_start))
+    num_t, num_r, num_a = len(IOU_THRESHOLDS), len(RECALL_THRESHOLDS), len(AREA_RANGES)
+    precision, recall = -np.ones((num_t, num_r, num_categories, num_a)), -np.ones((num_t, num_categories, num_a))
+    for k in range(num_categories):
+        sel, gts_k = np.nonzero(det_cat == k)[0], gt_cat == k
+        if not gts_k.any():
+            continue
+        sel = sel[np.argsort(-scores_all[sel], kind="mergesort")]  # a stable sort: equal scores stay in image order
+        for a in range(num_a):
+            npig = np.count_nonzero(~gt_ignore_all[a][gts_k])
+            if npig == 0:
+                continue
+            dtm, dt_ig = matched_all[a][:, sel], dt_ignore_all[a][:, sel]
+            tp_sum = np.cumsum(np.logical_and(dtm, np.logical_not(dt_ig)), axis=1).astype(dtype=np.float64)
+            fp_sum = np.cumsum(np.logical_and(np.logical_not(dtm), np.logical_not(dt_ig)), axis=1).astype(dtype=np.float64)
+            for t, (tp, fp) in enumerate(zip(tp_sum, fp_sum)):
+                precision[t, :, k, a] = _sampled_precision(tp, fp, npig)
+                recall[t, k, a] = (tp / npig)[-1] if len(tp) else 0
+    return precision, recall
+
+
+def summarize_lvis(precision, category_names, class_splits, frequencies, class_order=None, recall=None):
+    """Rule 10 of include/ovis_hip.h -> OrderedDict: AP, AP50, AP75, APs, APm, APl, then APr, APc, APf (area "all" over the
+    categories whose ``frequencies`` entry is r, c, f), AP50_class_<name> (``class_order`` as in ``summarize``) and
+    AP50_split_<split>; ``recall`` (``accumulate_lvis``' second array): followed by AR@300, ARs@300, ARm@300, ARl@300 and
+    AR@300_split_<split>.  The 300 of the keys is the cap the numbers are usually made with (``LVIS_MAX_DETS``)."""
+    if len(category_names) != precision.shape[2] or len(frequencies) != precision.shape[2]:
+        raise ValueError(f"summarize_lvis: {len(category_names)} names and {len(frequencies)} frequencies for a precision "
+                         f"array of {precision.shape[2]} categories")
+    t50, t75 = np.where(.5 == IOU_THRESHOLDS)[0], np.where(.75 == IOU_THRESHOLDS)[0]
+    res = OrderedDict()
+    res["AP"] = _mean(precision[:, :, :, 0])
+    res["AP50"] = _mean(precision[t50][:, :, :, 0])
+    res["AP75"] = _mean(precision[t75][:, :, :, 0])
+    for name, a in (("APs", 1), ("APm", 2), ("APl", 3)):
+        res[name] = _mean(precision[:, :, :, a])
+    for f in LVIS_FREQUENCIES:
+        res[f"AP{f}"] = _mean(precision[:, :, np.asarray([k for k, v in enumerate(frequencies) if v == f], dtype=np.int64), 0])
+    s = precision[t50][:, :, :, 0]  # [1, R, K]
+    for k in range(len(category_names)) if class_order is None else class_order:
+        res[f"AP50_class_{category_names[k]}"] = _mean(s[:, :, [k]])
+    for split, cats in class_splits.items():
+        res[f"AP50_split_{split}"] = _mean(s[:, :, list(cats)])
+    if recall is not None:
+        for name, a in zip(LVIS_RECALL_METRICS, range(len(AREA_RANGES))):
+            res[name] = _mean(recall[:, :, a])
+        for split, cats in class_splits.items():
+            res[f"AR@300_split_{split}"] = _mean(recall[:, list(cats), 0])
+    return res
+
+
 def format_results(results):
     """The reference's ``Task: ... / names / values`` table (``COCOResults.__repr__``, coco_eval.py:406-414)."""
     out = "\n"
@@ -267,12 +352,31 @@ def rle_decode(rle, height, width):
     return np.ascontiguousarray(flat.reshape(width, height).T)
 
 
-def _ground_truth(dataset):
+def category_frequencies(dataset):
+    """The ``frequency`` (r, c or f) of every category of the annotation file, in sorted-id order (rule 1 of LVIS-style
+    scoring, include/ovis_hip.h).  ValueError naming the first category without one."""
+    coco = dataset.coco
+    out = []
+    for c in coco.cat_ids():
+        f = coco.cats[c].get("frequency")
+        if f not in LVIS_FREQUENCIES:
+            raise ValueError(f"rules='lvis': category {c} ({coco.cats[c].get('name')}) has no 'frequency' in "
+                             f"{LVIS_FREQUENCIES} (got {f!r}); the annotation file is not federatedly annotated")
+        out.append(f)
+    return out
+
+
+def _ground_truth(dataset, rules="coco"):
     """-> (category ids sorted, per image of the file in id order a record of its annotations sorted by category index,
-    stably: annotation order inside a category)."""
+    stably: annotation order inside a category).  ``rules="lvis"`` (rules 1 and 2 of include/ovis_hip.h): every record also
+    holds ``neg`` and ``not_exhaustive`` (int64 arrays of category indices, sorted) and ``ignore`` (the annotations'
+    ``ignore`` keys), its ``crowd`` is all zero (``iscrowd`` is not read), and an image without either list or a category
+    without ``frequency`` is a ValueError that names it."""
+    _check_rules(rules, "evaluate_coco")
     coco = dataset.coco
     cat_ids = coco.cat_ids()
     cat_index = {c: i for i, c in enumerate(cat_ids)}
+    lvis = rules == "lvis"
     images = []
     for img_id in sorted(coco.imgs):
         info = coco.imgs[img_id]
@@ -283,8 +387,20 @@ def _ground_truth(dataset):
             "id": img_id, "width": int(info["width"]), "height": int(info["height"]), "anns": anns, "boxes": boxes,
             "cats": np.asarray([cat_index[a["category_id"]] for a in anns], dtype=np.int64),
             "areas": np.asarray([a["area"] if "area" in a else a["bbox"][2] * a["bbox"][3] for a in anns], dtype=np.float64),
-            "crowd": np.asarray([1 if a.get("iscrowd", 0) else 0 for a in anns], dtype=np.uint8),
+            "crowd": np.asarray([1 if a.get("iscrowd", 0) and not lvis else 0 for a in anns], dtype=np.uint8),
             "polygons": sum(len(a["segmentation"]) for a in anns if isinstance(a.get("segmentation"), list))})
+        if lvis:
+            for key in ("neg_category_ids", "not_exhaustive_category_ids"):
+                if not isinstance(info.get(key), (list, tuple)):
+                    raise ValueError(f"rules='lvis': image {img_id} has no '{key}' list; the annotation file is not "
+                                     "federatedly annotated")
+            images[-1].update(
+                neg=np.unique([cat_index[c] for c in info["neg_category_ids"] if c in cat_index]).astype(np.int64),
+                not_exhaustive=np.unique([cat_index[c] for c in info["not_exhaustive_category_ids"]
+                                          if c in cat_index]).astype(np.int64),
+                ignore=np.asarray([1 if a.get("ignore", 0) else 0 for a in anns], dtype=np.uint8))
+    if lvis:
+        category_frequencies(dataset)  # raises on the first category without a frequency
     return cat_ids, images
 
 
@@ -311,18 +427,33 @@ def mask_maps(pred):
     return maps
 
 
-def _detections(pred, image, label_to_cat, with_masks):
+def _kept_rows(cats, scores, image, rules, lvis_max_dets):
+    """The detections of one image that are scored, as indices into ``cats`` / ``scores`` sorted by (category index,
+    descending score), stably: ties keep the input order.  coco: at most 100 per category.  lvis (rules 3 to 5 of
+    include/ovis_hip.h): the ``lvis_max_dets`` best of the image over all categories together (negative: all), and of those
+    the ones whose category is a negative of the image or has a ground truth in it."""
+    if rules != "lvis":
+        order = np.lexsort((-scores, cats))
+        rank = np.arange(len(order)) - np.searchsorted(cats[order], cats[order], side="left")
+        return order[rank < MAX_DETS[-1]]
+    order = np.argsort(-scores, kind="mergesort")
+    if lvis_max_dets >= 0:
+        order = order[:lvis_max_dets]
+    order = order[np.isin(cats[order], np.union1d(image["neg"], image["cats"]))]
+    return order[np.lexsort((-scores[order], cats[order]))]  # equal scores stay in the order the first sort left them in
+
+
+def _detections(pred, image, label_to_cat, with_masks, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
     """One image's prediction as rows sorted by (category index, descending score), stably, at most 100 per category
-    (coco_eval.py:71-105 / :108-162 and the ``dt[0:maxDets[-1]]`` of COCOeval.computeIoU)."""
+    (coco_eval.py:71-105 / :108-162 and the ``dt[0:maxDets[-1]]`` of COCOeval.computeIoU); ``rules="lvis"``: the image's
+    cap and the federated filter instead (``_kept_rows``)."""
     empty = {"cats": np.zeros(0, np.int64), "scores": np.zeros(0), "xywh": np.zeros((0, 4)), "xyxy": None, "maps": None}
     if pred is None or len(pred) == 0:
         return empty
     xyxy, xywh = detection_boxes(pred, image["width"], image["height"])
     scores = pred.get_field("scores").detach().cpu().double().numpy()
     cats = np.asarray([label_to_cat[int(l)] for l in pred.get_field("labels").tolist()], dtype=np.int64)
-    order = np.lexsort((-scores, cats))  # stable: ties keep prediction order
-    rank = np.arange(len(order)) - np.searchsorted(cats[order], cats[order], side="left")
-    order = order[rank < MAX_DETS[-1]]
+    order = _kept_rows(cats, scores, image, rules, lvis_max_dets)  # stable: ties keep prediction order
     out = {"cats": cats[order], "scores": scores[order], "xywh": xywh.double().numpy()[order], "xyxy": None, "maps": None}
     if with_masks:
         maps = mask_maps(pred)
@@ -331,7 +462,7 @@ def _detections(pred, image, label_to_cat, with_masks):
     return out
 
 
-def load_coco_results(dataset, results, iou_type):
+def load_coco_results(dataset, results, iou_type, rules="coco", lvis_max_dets=LVIS_MAX_DETS, images=None):
     """The detections of a COCO results file as per-image rows, for the images of ``_ground_truth(dataset)`` in its order
     (pycocotools' ``loadRes`` and the ``dt[0:maxDets[-1]]`` of COCOeval): ``results`` is a path or the parsed list of
     {"image_id", "category_id", "score", "bbox" (xywh) or "segmentation" ({"size": [h, w], "counts": str or list})}.  Rows
@@ -339,8 +470,13 @@ def load_coco_results(dataset, results, iou_type):
     category and image.  bbox: ``xywh`` as written (the area is w * h).  segm: ``rle`` holds the rows' segmentation dicts in
     place of ``maps`` / ``xyxy`` (the area comes from the decoder); ``entry`` is every row's index in the file.  Entries of
     a category the annotation file does not have are dropped (COCOeval never evaluates them).  ValueError, naming the
-    entry: an image_id the file does not have, a polygon segmentation, a ``size`` that is not the image's, a missing key."""
-    _check_iou_type(iou_type, "load_coco_results")  # boundary: the rows of segm, it scores the same segm.json
+    entry: an image_id the file does not have, a polygon segmentation, a ``size`` that is not the image's, a missing key.
+    ``rules="lvis"``: the image's cap of ``lvis_max_dets`` and the federated filter take the place of the 100 per category
+    (``_kept_rows``); ``images``: the records of ``_ground_truth(dataset, "lvis")`` when the caller already has them."""
+    _check_iou_type(iou_type, "load_coco_results")
+    _check_rules(rules, "load_coco_results")
+    if rules == "lvis" and images is None:
+        images = _ground_truth(dataset, rules)[1]  # boundary: the rows of segm, it scores the same segm.json
     if isinstance(results, (str, bytes, os.PathLike)):
         with open(results) as f:
             results = json.load(f)
@@ -375,13 +511,12 @@ def load_coco_results(dataset, results, iou_type):
                 raise ValueError(f"{where}: RLE of size {seg['size']} on an image of {info['height']} x {info['width']}")
         per_image.setdefault(entry["image_id"], []).append(index)
     rows = []
-    for img_id in sorted(coco.imgs):
+    for position, img_id in enumerate(sorted(coco.imgs)):
         members = per_image.get(img_id, [])
         scores = np.asarray([results[k]["score"] for k in members], dtype=np.float64)
         cats = np.asarray([cat_index[results[k]["category_id"]] for k in members], dtype=np.int64)
-        order = np.lexsort((-scores, cats))  # stable: ties keep file order
-        rank = np.arange(len(order)) - np.searchsorted(cats[order], cats[order], side="left")
-        order = order[rank < MAX_DETS[-1]]
+        # stable: ties keep file order
+        order = _kept_rows(cats, scores, images[position] if rules == "lvis" else None, rules, lvis_max_dets)
         members = [members[k] for k in order]
         row = {"cats": cats[order], "scores": scores[order], "xywh": np.zeros((len(members), 4)), "xyxy": None, "maps": None,
                "entry": np.asarray(members, dtype=np.int64)}
@@ -462,7 +597,7 @@ def _boundary_group(words_parts, bwords_parts, bareas_out, group_rows, height, w
     bareas_out[group_rows] = bareas
 
 
-def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco"):
     """The match tables of one chunk of images (the NumPy form ``accumulate`` takes): a constant number of launches --
     box or mask IoU and the matching -- plus, for segm, the paste, rasterise and pack calls of every image size; detections
     that carry ``rle`` (``load_coco_results``) and RLE ground truth take one ``_C.coco_rle_words`` call per image size
@@ -471,7 +606,11 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
     boundary (Boundary AP: the rule is in include/ovis_hip.h) works on the words segm makes: one
     ``_C.coco_boundary_words`` call per image size and side, then ``_C.coco_boundary_iou`` writes min(mask IoU, boundary
     IoU) where segm has the mask IoU, and the same matching follows -- with the MASK areas.  ``iou_type`` may be the tuple
-    ("segm", "boundary"): the words are made once, both IoU buffers are matched, and {name: tables} comes back."""
+    ("segm", "boundary"): the words are made once, both IoU buffers are matched, and {name: tables} comes back.
+
+    ``rules="lvis"`` (``images`` / ``dets`` from ``_ground_truth`` / ``_detections`` under the same rules): the IoU entries
+    get all-zero crowd flags, and ``_C.lvis_match`` takes the place of ``_C.coco_match`` -- with the annotations' ignore
+    flags and one not-exhaustive flag per problem (rules 7 and 8 of include/ovis_hip.h)."""
     types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type)
     with_masks, boundary = types[0] != "bbox", "boundary" in types
     rows, det_base, gt_base, iou_off = [], 0, 0, 0
@@ -489,6 +628,10 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
     table = np.asarray(rows, dtype=np.int64).reshape(-1, 10)
     num_dets, num_gts = det_base, gt_base
     crowd = torch.from_numpy(np.concatenate([im["crowd"] for im in images] + [np.zeros(0, np.uint8)])).to(device)
+    if rules == "lvis":  # crowd is all zero here: no IoU takes the crowd form
+        gt_ignore_in = torch.from_numpy(np.concatenate([im["ignore"] for im in images] + [np.zeros(0, np.uint8)])).to(device)
+        open_flags = np.asarray([c in images[i]["not_exhaustive"] for c, i in zip(table[:, 8], table[:, 9])], dtype=np.uint8)
+        not_exhaustive = torch.from_numpy(open_flags.reshape(-1)).to(device)
     gt_areas = torch.from_numpy(np.concatenate([im["areas"] for im in images] + [np.zeros(0)])).to(device)
     scores = np.concatenate([d["scores"] for d in dets] + [np.zeros(0)])
     if not with_masks:
@@ -587,8 +730,13 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
     tables = {}
     for name in types:
         with _stage(timer, "match"):
-            dt_match, dt_ignore, gt_ignore = _C.coco_match(boundary_iou if name == "boundary" else iou, problems, det_areas,
-                                                           gt_areas, crowd, area_ranges, thresholds)
+            if rules == "lvis":
+                dt_match, dt_ignore, gt_ignore = _C.lvis_match(boundary_iou if name == "boundary" else iou, problems,
+                                                               det_areas, gt_areas, gt_ignore_in, not_exhaustive,
+                                                               area_ranges, thresholds)
+            else:
+                dt_match, dt_ignore, gt_ignore = _C.coco_match(boundary_iou if name == "boundary" else iou, problems,
+                                                               det_areas, gt_areas, crowd, area_ranges, thresholds)
         tables[name] = {"category": table[:, 8].copy(), "det_start": np.concatenate([table[:, 0], [num_dets]]),
                         "gt_start": np.concatenate([table[:, 2], [num_gts]]), "scores": scores,
                         "dt_match": dt_match.cpu().numpy(), "dt_ignore": dt_ignore.cpu().numpy(),
@@ -625,30 +773,36 @@ def _job_types(iou_type, who):
 
 
 def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None,
-                 boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+                 boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
     """-> (the match tables of every (image, category) problem of the annotation file, in image-id order; the sorted
     category ids).  ``budget``: the bytes of device memory a chunk may plan with (None: a quarter of what is free);
-    ``max_images``: the most images of a chunk (None: MAX_CHUNK_IMAGES); ``ground_truth``: ``_ground_truth(dataset)`` when
-    the caller already has it.  ``iou_type``: bbox, segm, boundary, or the tuple ("segm", "boundary") -- then the first
-    item is {name: tables}, both from one set of mask words per chunk."""
+    ``max_images``: the most images of a chunk (None: MAX_CHUNK_IMAGES); ``ground_truth``: ``_ground_truth(dataset, rules)``
+    when the caller already has it.  ``iou_type``: bbox, segm, boundary, or the tuple ("segm", "boundary") -- then the first
+    item is {name: tables}, both from one set of mask words per chunk.  ``rules="lvis"``: LVIS-style federated scoring
+    (include/ovis_hip.h), at most ``lvis_max_dets`` detections per image."""
     types = _job_types(iou_type, "evaluate_coco")
+    _check_rules(rules, "evaluate_coco")
     if len(predictions) > len(dataset):
         raise ValueError(f"evaluate_coco: {len(predictions)} predictions for a dataset of {len(dataset)} images")
     device = torch.device(device)
-    cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset)
+    cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset, rules)
     cat_index = {c: i for i, c in enumerate(cat_ids)}
     label_to_cat = {label: cat_index[json_id] for label, json_id in dataset.contiguous_category_id_to_json_id.items()}
     by_image = {dataset.id_to_img_map[idx]: pred for idx, pred in enumerate(predictions)}
-    dets = [_detections(by_image.get(image["id"]), image, label_to_cat, types[0] != "bbox") for image in images]
-    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio), cat_ids
+    dets = [_detections(by_image.get(image["id"]), image, label_to_cat, types[0] != "bbox", rules, lvis_max_dets)
+            for image in images]
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio, rules), cat_ids
 
 
-def _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+def _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO,
+                rules="coco"):
     """The match tables of the images' ground truth and detection rows, chunk by chunk ({name: tables} for a tuple)."""
     if budget is None:
         budget = torch.cuda.mem_get_info(device)[0] // 4
     types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type)
-    parts = [score_chunk([images[i] for i in chunk], [dets[i] for i in chunk], iou_type, device, timer, boundary_dilation_ratio)
+    extra = {} if rules == "coco" else {"rules": rules}
+    parts = [score_chunk([images[i] for i in chunk], [dets[i] for i in chunk], iou_type, device, timer, boundary_dilation_ratio,
+                         **extra)
              for chunk in _chunks(images, dets, types[0] != "bbox", budget, max_images, "boundary" in types)]
     if isinstance(iou_type, str):
         return concatenate_tables(parts)
@@ -656,13 +810,14 @@ def _score_rows(images, dets, iou_type, device, budget, timer, max_images, bound
 
 
 def results_match_tables(dataset, results, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None,
-                         boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+                         boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
     """``match_tables`` for the detections of a results file (``results``: what ``load_coco_results`` takes)."""
     types = _job_types(iou_type, "evaluate_coco_results")
+    _check_rules(rules, "evaluate_coco_results")
     device = torch.device(device)
-    cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset)
-    dets = load_coco_results(dataset, results, types[0])
-    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio), cat_ids
+    cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset, rules)
+    dets = load_coco_results(dataset, results, types[0], rules, lvis_max_dets, images)
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio, rules), cat_ids
 
 
 def _scoring_device(device, who):
@@ -672,13 +827,14 @@ def _scoring_device(device, who):
     return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
 
 
-def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth=None):
+def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth=None, rules="coco"):
     """{iou_type: ``summarize`` of ``accumulate`` of ``tables_of(iou_type, ground truth)``} with the dataset's names,
     splits and class order; ``recall``: followed by ``summarize_recall`` of ``accumulate_recall`` of the same tables.
     When segm and boundary are both asked for, ``tables_of`` is called ONCE for the two, with the tuple ("segm",
-    "boundary"), and returns {name: tables} (``_jobs``)."""
+    "boundary"), and returns {name: tables} (``_jobs``).  ``rules="lvis"``: ``summarize_lvis`` of ``accumulate_lvis``."""
     results, scored = OrderedDict(), {}
-    ground_truth = ground_truth if ground_truth is not None else _ground_truth(dataset)
+    ground_truth = ground_truth if ground_truth is not None else _ground_truth(dataset, rules)
+    frequencies = category_frequencies(dataset) if rules == "lvis" else None
     cat_ids = ground_truth[0]
     cat_index = {c: i for i, c in enumerate(cat_ids)}
     splits = OrderedDict((split, [cat_index[c] for c in ids]) for split, ids in dataset.class_splits.items())
@@ -689,6 +845,11 @@ def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth
             scored.update({job: tables} if isinstance(job, str) else tables)
         for iou_type in iou_types:
             tables = scored[iou_type]
+            if rules == "lvis":
+                precision, recalls = accumulate_lvis(tables, len(cat_ids))
+                results[iou_type] = summarize_lvis(precision, [dataset.categories[c] for c in cat_ids], splits, frequencies,
+                                                   class_order, recalls if recall else None)
+                continue
             results[iou_type] = summarize(accumulate(tables, len(cat_ids)), [dataset.categories[c] for c in cat_ids], splits,
                                           class_order)
             if recall:
@@ -698,7 +859,7 @@ def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth
 
 
 def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda", recall=False,
-                  boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+                  boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
     """{iou_type: OrderedDict of AP, AP50, AP75, APs, APm, APl, AP50_class_<name> per category (in the order of
     ``dataset.categories``, as ``COCOResults.update`` iterates) and AP50_split_<split> per key of ``dataset.class_splits``}
     for ``predictions``: the list ``inference()`` returns or ``torch.load`` gives from ``predictions.pth`` (BoxLists in
@@ -708,24 +869,38 @@ def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda
 
     ``"boundary"`` among ``iou_types`` is Boundary AP (Cheng et al., CVPR 2021): segm's keys from a matching on min(mask
     IoU, boundary IoU), the boundary band ``boundary_dilation_ratio`` of the image diagonal deep -- the rule is written
-    out in include/ovis_hip.h.  Beside segm it costs no second paste / rasterise / pack, and leaves segm's numbers alone."""
+    out in include/ovis_hip.h.  Beside segm it costs no second paste / rasterise / pack, and leaves segm's numbers alone.
+
+    ``rules="lvis"``: LVIS-style federated scoring of an annotation file whose images carry ``neg_category_ids`` and
+    ``not_exhaustive_category_ids`` and whose categories carry ``frequency`` -- the ten rules of include/ovis_hip.h, for
+    every iou_type, boundary included: at most ``lvis_max_dets`` detections per image over all categories (negative: no
+    cap), detections of categories nobody looked for in the image are not judged, and the keys are AP ... APl, APr, APc,
+    APf, AP50_class_<name>, AP50_split_<split>, with ``recall`` AR@300, ARs@300, ARm@300, ARl@300, AR@300_split_<split>.
+    The rules are restated, not imported: the numbers have not been compared with lvis-api's output."""
     device = _scoring_device(device, "evaluate_coco")
     for iou_type in iou_types:
         _check_iou_type(iou_type, "evaluate_coco")
+    _check_rules(rules, "evaluate_coco")
+    if rules == "coco":
+        return _summaries(dataset, iou_types, device,
+                          lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt,
+                                                            boundary_dilation_ratio=boundary_dilation_ratio), recall)
     return _summaries(dataset, iou_types, device,
                       lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt,
-                                                        boundary_dilation_ratio=boundary_dilation_ratio), recall)
+                                                        boundary_dilation_ratio=boundary_dilation_ratio, rules=rules,
+                                                        lvis_max_dets=lvis_max_dets), recall, rules=rules)
 
 
 def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="cuda", recall=False,
-                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
     """``evaluate_coco``'s numbers, in the same structure, for detections that come from COCO results files: ``results`` is
     {iou_type: a path or the parsed list} (``load_coco_results``); an iou_type it does not have is skipped -- but boundary
     reads the ``"boundary"`` entry when there is one and else the ``"segm"`` one: it scores the same ``segm.json``.  Whatever
     wrote the files -- ``export_coco_results``, the reference, another tool -- nothing but the annotation file is needed
-    beside them.  ``recall``, ``boundary_dilation_ratio``: as in ``evaluate_coco``.  ``device``: the HIP device that decodes
-    the masks and scores; there is no host-only scoring."""
+    beside them.  ``recall``, ``boundary_dilation_ratio``, ``rules``, ``lvis_max_dets``: as in ``evaluate_coco``.  ``device``:
+    the HIP device that decodes the masks and scores; there is no host-only scoring."""
     device = _scoring_device(device, "evaluate_coco_results")
+    _check_rules(rules, "evaluate_coco_results")
     for iou_type in results:
         _check_iou_type(iou_type, "evaluate_coco_results")
     files = dict(results)
@@ -733,13 +908,14 @@ def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="
         files["boundary"] = files["segm"]
     iou_types = [t for t in iou_types if t in files]
     if all(t in iou_types for t in MASK_IOU_TYPES) and files["boundary"] is not files["segm"]:  # two files: two passes
-        return OrderedDict((t, evaluate_coco_results(dataset, {t: files[t]}, (t,), device, recall, boundary_dilation_ratio)[t])
+        return OrderedDict((t, evaluate_coco_results(dataset, {t: files[t]}, (t,), device, recall, boundary_dilation_ratio,
+                                                     rules, lvis_max_dets)[t])
                            for t in iou_types)
 
     def tables_of(job, gt):
         return results_match_tables(dataset, files[job if isinstance(job, str) else job[0]], job, device, ground_truth=gt,
-                                    boundary_dilation_ratio=boundary_dilation_ratio)
-    return _summaries(dataset, iou_types, device, tables_of, recall)
+                                    boundary_dilation_ratio=boundary_dilation_ratio, rules=rules, lvis_max_dets=lvis_max_dets)
+    return _summaries(dataset, iou_types, device, tables_of, recall, rules=rules)
 
 
 # ---- every rank scores what it predicted: only match tables travel --------------------------------------------------------
@@ -788,7 +964,7 @@ def merge_shard_tables(parts):
 
 
 def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm"), device="cuda", recall=False,
-                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO):
+                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
     """``evaluate_coco``'s numbers without gathering the predictions: ``local_predictions`` is THIS rank's {dataset index:
     BoxList} (what ``engine.inference.compute_on_dataset`` returns), every rank calls this, rank 0 gets the OrderedDict and
     the others None.  The ranks exchange their index lists; ``shard_owners`` says who scores an image that sits on two of
@@ -796,8 +972,10 @@ def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm")
     to rank 0 with zero detections.  Every rank then makes the detection rows of its images and scores them against their
     ground truth on its own device (``_detections``, ``_score_rows``), and its match tables -- about 208 B per detection, not
     the M x M maps -- go to rank 0 with the image id of every problem, where ``merge_shard_tables`` puts them into the order
-    ``match_tables`` has.  One process: the same code with one shard."""
+    ``match_tables`` has.  One process: the same code with one shard.  ``rules``, ``lvis_max_dets``: as in ``evaluate_coco``
+    -- cap, federated filter and matching are per image, so nothing else changes."""
     device = _scoring_device(device, "evaluate_coco_sharded")
+    _check_rules(rules, "evaluate_coco_sharded")
     for iou_type in iou_types:
         _check_iou_type(iou_type, "evaluate_coco_sharded")
     world, rank = comm.get_world_size(), comm.get_rank()
@@ -809,7 +987,7 @@ def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm")
         mine, index_lists = index_lists[0], [None] * world
         dist.all_gather_object(index_lists, mine)
     owner_of_image = {dataset.id_to_img_map[idx]: r for idx, r in shard_owners(index_lists).items()}
-    ground_truth = _ground_truth(dataset)
+    ground_truth = _ground_truth(dataset, rules)
     cat_ids, images = ground_truth
     cat_index = {c: i for i, c in enumerate(cat_ids)}
     label_to_cat = {label: cat_index[json_id] for label, json_id in dataset.contiguous_category_id_to_json_id.items()}
@@ -818,8 +996,9 @@ def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm")
     merged = {}
     with torch.cuda.device(device):
         for job in _jobs(iou_types):  # segm and boundary together: one pass over the mask words, two tables
-            dets = [_detections(by_image.get(image["id"]), image, label_to_cat, job != "bbox") for image in images]
-            scored = _score_rows(images, dets, job, device, None, None, None, boundary_dilation_ratio)
+            dets = [_detections(by_image.get(image["id"]), image, label_to_cat, job != "bbox", rules, lvis_max_dets)
+                    for image in images]
+            scored = _score_rows(images, dets, job, device, None, None, None, boundary_dilation_ratio, rules)
             problems = np.asarray([len(np.union1d(det["cats"], image["cats"])) for image, det in zip(images, dets)],
                                   dtype=np.int64)
             for iou_type, tables in ({job: scored} if isinstance(job, str) else scored).items():
@@ -834,7 +1013,7 @@ def evaluate_coco_sharded(dataset, local_predictions, iou_types=("bbox", "segm")
         return None
     return _summaries(dataset, iou_types, device,
                       lambda job, gt: (merged[job] if isinstance(job, str) else {t: merged[t] for t in job}, cat_ids), recall,
-                      ground_truth)
+                      ground_truth, rules)
 
 
 def annotation_dataset(ann_file):

@@ -43,19 +43,29 @@ def save_visualizations(dataset, predictions, folder, count, threshold, device):
         Image.fromarray(picture).save(os.path.join(folder, stem + ".png"))
 
 
-def save_evaluation(dataset, predictions, folder, iou_types, device, logger, recall=False):
+def results_file_name(lvis=False, iteration=None):
+    """``coco_results.json`` / ``coco_results_<iteration:07d>.json``; under LVIS-style federated rules ``lvis_results*`` -- the
+    two sets of numbers cannot be mistaken for each other."""
+    stem = "lvis_results" if lvis else "coco_results"
+    return stem + ".json" if iteration is None else "{}_{:07d}.json".format(stem, iteration)
+
+
+def save_evaluation(dataset, predictions, folder, iou_types, device, logger, recall=False, lvis=False):
     """COCO scoring of one test set (engine/coco_eval.py): the table goes to the log, the numbers to
     ``folder``/coco_results.json as {iou_type: {metric: value}}.  ``recall``: the reference's whole table -- a
     ``box_proposal`` task first (engine/proposal_recall.py: the detections scored as proposals by their ``scores``, which is
     what the reference's table shows, its post-processor copying ``scores`` into ``objectness``), and the AR keys behind the
-    AP keys of every iou_type."""
+    AP keys of every iou_type.  ``lvis``: every iou_type under LVIS-style federated rules (``evaluate_coco(rules="lvis")``:
+    APr / APc / APf, AR@300; the annotation file must be federatedly annotated), written to ``lvis_results.json``; the
+    ``box_proposal`` task keeps its own rules."""
+    rules = {"rules": "lvis"} if lvis else {}
     if recall:
         results = OrderedDict(box_proposal=proposal_recall.evaluate_box_proposals(dataset, predictions, device, "scores"))
-        results.update(coco_eval.evaluate_coco(dataset, predictions, iou_types, device, recall=True))
+        results.update(coco_eval.evaluate_coco(dataset, predictions, iou_types, device, recall=True, **rules))
     else:
-        results = coco_eval.evaluate_coco(dataset, predictions, iou_types, device)
+        results = coco_eval.evaluate_coco(dataset, predictions, iou_types, device, **rules)
     logger.info(coco_eval.format_results(results))
-    with open(os.path.join(folder, "coco_results.json"), "w") as f:
+    with open(os.path.join(folder, results_file_name(lvis)), "w") as f:
         json.dump(results, f, indent=1)
     return results
 
@@ -99,10 +109,13 @@ def scored_iou_types(cfg, boundary_ap=False):
 
 
 def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
-                 export_results=False, recall=False, vote_thresh=None, average_masks=False, boundary_ap=False):
+                 export_results=False, recall=False, vote_thresh=None, average_masks=False, boundary_ap=False, lvis=False):
     """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}.  ``vote_thresh`` /
     ``average_masks``: box voting and view-averaged masks of multi-scale / flip testing (engine/bbox_aug.py);
-    ``boundary_ap``: with ``evaluate``, a ``boundary`` task behind ``segm`` (engine/coco_eval.py: Boundary AP)."""
+    ``boundary_ap``: with ``evaluate``, a ``boundary`` task behind ``segm`` (engine/coco_eval.py: Boundary AP); ``lvis``: with
+    ``evaluate``, LVIS-style federated rules and ``lvis_results.json`` (``save_evaluation``)."""
+    if lvis and not evaluate:
+        raise ValueError("run_datasets: lvis=True changes the rules of what evaluate=True scores")
     iou_types = scored_iou_types(cfg, boundary_ap and evaluate)
     transform = build_transforms(cfg, is_train=False)
     results = {}
@@ -126,20 +139,22 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
                              "set OUTPUT_DIR")
         if evaluate and results[name] is not None:
             save_evaluation(dataset, results[name], out, iou_types, device, logger or logging.getLogger("ovis.inference"),
-                            recall)
+                            recall, lvis)
         if export_results and results[name] is not None:
             coco_results.export_coco_results(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",),
                                              device)
     return results
 
 
-def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_embeddings, logger=None, boundary_ap=False):
+def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_embeddings, logger=None, boundary_ap=False,
+                         lvis=False):
     """The SOLVER.TEST_PERIOD evaluation of a live training process, behind iteration ``iteration`` (trainer.py:174-203):
     every DATASETS.TEST name through the model's evaluation pass on this rank's shard, scored where it was predicted
     (``coco_eval.evaluate_coco_sharded``: AP keys of ``bbox``, of ``segm`` when MODEL.MASK_ON, and of ``boundary`` behind it
     when ``boundary_ap``) -> {name: the numbers (rank 0) or None}.  Rank 0 logs the table under the iteration and writes
     ``OUTPUT_DIR/inference/<name>/coco_results_<iteration:07d>.json`` in the structure of ``coco_results.json``; no
-    predictions are gathered or saved.  The caller has joined whatever else runs the model (``PipelinedTrainer.drain``).
+    predictions are gathered or saved.  ``lvis``: LVIS-style federated rules (``evaluate_coco_sharded(rules="lvis")``), written
+    to ``lvis_results_<iteration:07d>.json`` instead.  The caller has joined whatever else runs the model (``PipelinedTrainer.drain``).
     On return the model is as it was: every module's mode, ``train_class_embeddings`` as its class matrix (trainer.py:198-202),
     torch's random generators; a loader's worker processes live for one test set only."""
     if not cfg.OUTPUT_DIR:
@@ -171,7 +186,8 @@ def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_emb
                 batches.close()
             comm.synchronize()
             predicted = time.perf_counter()
-            results[name] = coco_eval.evaluate_coco_sharded(dataset, predictions, iou_types, device)
+            results[name] = coco_eval.evaluate_coco_sharded(dataset, predictions, iou_types, device,
+                                                            **({"rules": "lvis"} if lvis else {}))
             scored = time.perf_counter()
             logger.info("iteration %d, %s: %d images on this rank, inference %.2f s, scoring %.2f s", iteration, name,
                         len(predictions), predicted - start, scored - predicted)
@@ -179,7 +195,7 @@ def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_emb
                 logger.info("iteration %d, %s:%s", iteration, name, coco_eval.format_results(results[name]))
                 out = os.path.join(cfg.OUTPUT_DIR, "inference", name)
                 os.makedirs(out, exist_ok=True)
-                with open(os.path.join(out, "coco_results_{:07d}.json".format(iteration)), "w") as f:
+                with open(os.path.join(out, results_file_name(lvis, iteration)), "w") as f:
                     json.dump(results[name], f, indent=1)
     finally:
         model.train()

@@ -964,6 +964,58 @@ int ovis_coco_boundary_iou_f64(const uint64_t* det_words, const uint64_t* det_bo
                                const int64_t* gt_boundary_areas, const uint8_t* gt_crowd, const int64_t* problems,
                                int num_problems, long max_pairs, double* iou, void* stream);
 
+/* LVIS-style federated AP -- APr / APc / APf (csrc/lvis_eval.hip, engine/coco_eval.py rules="lvis"; Gupta et al., "LVIS",
+ * CVPR 2019 -- the reference does not score it).  lvis-api is not a dependency: the rules are restated and THIS TEXT is the
+ * contract; the numbers follow it and have NOT been compared with lvis-api's own output.  "COCO's" below means what
+ * engine/coco_eval.py and csrc/coco_eval.hip do under rules="coco".
+ *   1. SCOPE.  All images and all categories of the annotation file, sorted by id.  Every image must carry
+ *      neg_category_ids and not_exhaustive_category_ids (lists of category ids) and every category frequency in {r, c, f};
+ *      a missing key is a ValueError naming the first offending image or category -- never silently empty.
+ *   2. GROUND TRUTH.  Every annotation is ground truth.  iscrowd is not read: no ground truth is a crowd and no IoU uses the
+ *      crowd form.  A ground truth's input ignore flag is its `ignore` key if present, else 0.  Its area is COCO's: `area`
+ *      if present, else the box w * h.
+ *   3. CAP PER IMAGE, before anything else: an image's detections are sorted by descending score, stably (ties keep
+ *      prediction or file order), and the first max_dets = 300 are kept across all categories together.  No per-category
+ *      cap of 100.  (Python keyword lvis_max_dets = 300; negative: no cap.)
+ *   4. FEDERATED FILTER, after the cap: a kept detection of category c in image i is dropped unless c is in
+ *      neg_category_ids(i) or image i has at least one ground truth of c.
+ *   5. PROBLEMS.  A problem is an (image, category) pair with a surviving detection or a ground truth; inside it the
+ *      detections are ordered by descending score, stably, the ground truths in annotation order.
+ *   6. IOU.  COCO's non-crowd form for bbox and segm; for boundary min(mask IoU, boundary IoU) with the dilation rule
+ *      above, non-crowd form.  A zero union gives 0 (the stated deviation).
+ *   7. MATCHING, one per problem, area range and IoU threshold (COCO's four ranges and ten thresholds).  A ground truth is
+ *      ignored in area range a if its input ignore flag is set or its area lies outside the range.  Ground truths are
+ *      scanned non-ignored first, in stable order; detections are taken in score order.  A detection takes, among the
+ *      UNMATCHED ground truths with IoU >= min(t, 1 - 1e-10), the non-ignored one of largest IoU, an equal IoU going to
+ *      the later ground truth; failing a non-ignored match, the same among the ignored ones.  A matched ground truth is
+ *      never matched again, ignored or not (the one difference from COCO's loop, where a crowd can be re-matched).  A
+ *      detection matched to an ignored ground truth is ignored.
+ *   8. UNMATCHED DETECTIONS.  Ignored if the detection's area lies outside the range OR its category is in
+ *      not_exhaustive_category_ids of its image.  Area: box w * h for bbox, the mask pixel count for segm and boundary.
+ *   9. ACCUMULATE, per category and area range over all images: detections merged by descending score with a stable
+ *      (merge) sort in image-id order; tp / fp cumulative sums over the non-ignored detections; precision = tp / (tp + fp +
+ *      spacing(1)), made non-increasing from the right, sampled at the 101 recall thresholds by searchsorted(side = left),
+ *      recall points past the last detection get 0; recall[t, k, a] = the last tp / num_gt, 0 with no detections.  A
+ *      (category, area) with no non-ignored ground truth stays -1.  There is no maxDets dimension.
+ *  10. SUMMARISE.  The mean over entries > -1, -1 if there are none: AP, AP50, AP75, APs, APm, APl, then APr, APc, APf
+ *      (area "all", restricted to the categories of that frequency), then the project's AP50_class_<name> and
+ *      AP50_split_<split>; with recall AR@300, ARs@300, ARm@300, ARl@300 and AR@300_split_<split>.  Fractions.
+ * Out of scope: a comparison with lvis-api; LVIS's "fixed AP" variant (10 000 detections per class); a federated training
+ * loss; another cap from the command line; keypoints; host-only scoring.
+ *
+ * ovis_lvis_match (rules 7 and 8): ovis_coco_match's inputs, tables and outputs with two changes -- gt_ignore_in u8
+ *   [num_gts] (rule 2's input ignore flag) takes the place of gt_crowd and a matched ground truth is never matched again;
+ *   problem_not_exhaustive u8 [num_problems], one flag per row of `problems`, is ORed into the ignore flag of that
+ *   problem's unmatched detections.  A problem without ground truth reads no IoU and shuffles nothing: its detections are
+ *   written lane-parallel as -1 / (area outside the range | problem flag).  With all-zero gt_ignore_in and flags the output
+ *   equals ovis_coco_match's with all-zero gt_crowd, bit for bit.  max_gts > 4096: OVIS_ERANGE; null and zero-size handling
+ *   as ovis_coco_match (problem_not_exhaustive must not be NULL when num_problems > 0); iou may be NULL when no pair exists.
+ *   Deterministic, no atomics, no LDS. */
+int ovis_lvis_match(const double* iou, const int64_t* problems, int num_problems, int max_gts, const double* det_areas,
+                    const double* gt_areas, const uint8_t* gt_ignore_in, const uint8_t* problem_not_exhaustive,
+                    const double* area_ranges, int num_areas, const double* thresholds, int num_thresholds, long num_dets,
+                    long num_gts, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore, void* stream);
+
 /* ovis_coco_rle_* / ovis_coco_runs_to_words (csrc/coco_rle_decode.hip): COCO run-length encodings -- the `segmentation` of a
  * results file (what mb/data/datasets/evaluation/coco/coco_eval.py:139-144 writes and COCOeval reads back through
  * pycocotools' rleFrString / rleDecode) or of an RLE annotation -- as the bit words of ovis_coco_pack_masks_u64, for `num`

@@ -1,7 +1,7 @@
 """Time of COCO scoring (engine/coco_eval.py) for one chunk of synthetic images, split by stage:
 
     python tools/bench_coco_eval.py [--images 32] [--height 480] [--width 640] [--detections 100] [--ground-truths 20]
-        [--boundary] [--repeats 1]
+        [--boundary] [--repeats 1] [--lvis]
 
 Seeded, no model: every image gets ``--detections`` random boxes with 28 x 28 mask maps over 10 categories and
 ``--ground-truths`` random hexagons.  The whole set is scored as ONE chunk, once to warm up (code objects, allocator) and
@@ -10,6 +10,14 @@ with the wall clock.  Prints one JSON line per IoU type.  ``--boundary`` adds a 
 TOGETHER from one set of mask words (``iou_type`` "segm+boundary": what ``--boundary-ap`` costs on top is that line minus the
 segm line; its stages ``boundary`` -- the erosion -- and ``boundary_iou`` are new, the others are segm's).  ``--repeats N``
 times every pass N times and prints each: the spread is the noise a difference has to clear.
+
+``--lvis`` scores an LVIS-shaped chunk under ``rules="lvis"`` instead (``make_lvis_case``: 1203 categories with frequencies, per
+image 300 detections over about 150 of them, about 12 ground truths in about 6 categories, about 20 negative categories among
+those the detector fired on, two not-exhaustive ones), with the same stage lines, and then times the MATCHING alone on the
+chunk's own problem table: ``_C.lvis_match`` against ``_C.coco_match`` with all-zero flags -- the tables of the two must be
+identical, which is asserted -- and both again on the sub-table of the problems WITHOUT ground truth, where ``lvis_match``
+reads no IoU and shuffles nothing.  ``--repeats`` runs of 50 launches each of the C entries into outputs allocated once, device events around the 50; one JSON line
+(``"match"``) with every run's time per launch in microseconds.
 """
 import argparse
 import json
@@ -65,6 +73,108 @@ def make_case(folder, images, height, width, detections, ground_truths, seed=0):
     return dataset, predictions
 
 
+LVIS_CATEGORIES = 1203
+
+
+def make_lvis_case(folder, images, height, width, detections=300, fired=150, ground_truths=12, positives=6, negatives=20,
+                   seed=0):
+    """An LVIS-shaped chunk: per image ``detections`` boxes over ``fired`` of the 1203 categories, ``ground_truths`` hexagons in
+    ``positives`` of those categories, ``negatives`` more of them verified absent, two of the positives not exhaustive."""
+    rs = np.random.RandomState(seed)
+    g = torch.Generator().manual_seed(seed)
+    anns, infos, predictions = [], [], []
+    for i in range(images):
+        cats = rs.choice(np.arange(1, LVIS_CATEGORIES + 1), size=fired, replace=False)
+        pos, neg = cats[:positives], cats[positives:positives + negatives]
+        for k in range(ground_truths):
+            cx, cy = rs.uniform(40, width - 40), rs.uniform(40, height - 40)
+            rx, ry = rs.uniform(10, 120), rs.uniform(10, 120)
+            poly = []
+            for v in range(6):
+                poly += [float(np.clip(cx + rx * math.cos(v * math.pi / 3), 0, width)),
+                         float(np.clip(cy + ry * math.sin(v * math.pi / 3), 0, height))]
+            x0, y0, x1, y1 = min(poly[0::2]), min(poly[1::2]), max(poly[0::2]), max(poly[1::2])
+            anns.append({"id": len(anns) + 1, "image_id": i, "category_id": int(pos[k % positives]),
+                         "bbox": [x0, y0, x1 - x0, y1 - y0], "area": (x1 - x0) * (y1 - y0) * .65, "segmentation": [poly]})
+        infos.append({"id": i, "file_name": f"{i}.png", "width": width, "height": height,
+                      "neg_category_ids": [int(c) for c in neg], "not_exhaustive_category_ids": [int(c) for c in pos[:2]]})
+        xy = torch.rand(detections, 2, generator=g) * torch.tensor([width - 60.0, height - 60.0])
+        wh = torch.rand(detections, 2, generator=g) * 200 + 16
+        pred = BoxList(torch.cat((xy, torch.minimum(xy + wh, torch.tensor([width - 1.0, height - 1.0]))), 1), (width, height))
+        pred.add_field("scores", torch.rand(detections, generator=g))
+        pred.add_field("labels", torch.from_numpy(cats[torch.randint(0, fired, (detections,), generator=g).numpy()]))
+        pred.add_field("mask", torch.rand(detections, 1, MAP, MAP, generator=g))
+        predictions.append(pred)
+    path = os.path.join(folder, "lvis_instances.json")
+    with open(path, "w") as f:
+        json.dump({"images": infos, "annotations": anns,
+                   "categories": [{"id": c, "name": f"class{c}", "frequency": "rcf"[c % 3]} for c in range(1, LVIS_CATEGORIES + 1)]}, f)
+    return COCODataset(path, folder, False), predictions   # labels = json ids: the ids are 1 .. 1203, contiguous
+
+
+def time_matching(dataset, predictions, device, budget, repeats, launches=50):
+    """``_C.lvis_match`` against ``_C.coco_match`` on the problem table the chunk's segm pass makes, flags all zero, and on its
+    sub-table of the problems without ground truth -> the ``"match"`` line."""
+    from cvpr22_cross_modal_pseudo_labeling_amd import _C
+
+    seen = {}
+    real = _C.lvis_match
+
+    def capture(*args):
+        seen["args"] = args
+        return real(*args)
+    _C.lvis_match = capture
+    try:
+        coco_eval.match_tables(dataset, predictions, "segm", device, budget, rules="lvis")
+    finally:
+        _C.lvis_match = real
+    iou, problems, det_areas, gt_areas, gt_ignore_in, flags, area_ranges, thresholds = seen["args"]
+    zero_gt, zero_flags = torch.zeros_like(gt_ignore_in), torch.zeros_like(flags)
+    empty = problems.host[problems.host[:, 3] == 0]
+    sub = _C.CocoProblems(empty, device)
+    sub_flags = torch.zeros(len(sub), dtype=torch.uint8, device=device)
+    for a, b in zip(_C.lvis_match(iou, problems, det_areas, gt_areas, zero_gt, zero_flags, area_ranges, thresholds),
+                    _C.coco_match(iou, problems, det_areas, gt_areas, zero_gt, area_ranges, thresholds)):
+        assert torch.equal(a, b), "lvis_match and coco_match differ on a table with all-zero flags"
+    for a, b in zip(_C.lvis_match(iou, sub, det_areas, gt_areas, zero_gt, sub_flags, area_ranges, thresholds),
+                    _C.coco_match(iou, sub, det_areas, gt_areas, zero_gt, area_ranges, thresholds)):
+        assert torch.equal(a, b), "lvis_match and coco_match differ on the problems without ground truth"
+    # the C entries themselves, into outputs allocated once: a call is one launch and nothing else
+    num_a, num_t, d, g = area_ranges.shape[0], thresholds.numel(), det_areas.numel(), gt_areas.numel()
+    dt_match = torch.empty((num_a, num_t, d), dtype=torch.int32, device=device)
+    dt_ignore = torch.empty((num_a, num_t, d), dtype=torch.uint8, device=device)
+    gt_ignore = torch.empty((num_a, g), dtype=torch.uint8, device=device)
+
+    def entry(name, table, *flag_args):
+        def call():
+            rc = getattr(_C._L, name)(iou.data_ptr(), table.dev.data_ptr(), len(table), table.max_gts, det_areas.data_ptr(),
+                                      gt_areas.data_ptr(), *[f.data_ptr() for f in flag_args], area_ranges.data_ptr(), num_a,
+                                      thresholds.data_ptr(), num_t, d, g, dt_match.data_ptr(), dt_ignore.data_ptr(),
+                                      gt_ignore.data_ptr(), _C._stream())
+            assert rc == 0, (name, rc)
+        return call
+    cases = {"lvis_match": entry("ovis_lvis_match", problems, zero_gt, zero_flags),
+             "coco_match": entry("ovis_coco_match", problems, zero_gt),
+             "lvis_match_flags": entry("ovis_lvis_match", problems, gt_ignore_in, flags),
+             "lvis_match_no_gt": entry("ovis_lvis_match", sub, zero_gt, sub_flags),
+             "coco_match_no_gt": entry("ovis_coco_match", sub, zero_gt)}
+    times = {name: [] for name in cases}
+    for _ in range(repeats):   # the entries alternate, so a drift of the machine meets all of them
+        for name, call in cases.items():
+            call()
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            start.record()
+            for _ in range(launches):
+                call()
+            end.record()
+            torch.cuda.synchronize()
+            times[name].append(round(start.elapsed_time(end) / launches * 1e3, 2))
+    return {"match": "per launch in us", "problems": len(problems), "problems_without_gt": len(sub),
+            "detections": int(det_areas.numel()), "ground_truths": int(gt_areas.numel()), "pairs": int(iou.numel()),
+            "launches_per_run": launches, "us": times, "identical_tables": True}
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     parser.add_argument("--images", type=int, default=32)
@@ -74,34 +184,48 @@ def main():
     parser.add_argument("--ground-truths", type=int, default=20)
     parser.add_argument("--boundary", action="store_true", help="also time segm and Boundary AP scored together")
     parser.add_argument("--repeats", type=int, default=1, help="timed runs per pass, each printed")
+    parser.add_argument("--lvis", action="store_true",
+                        help="an LVIS-shaped chunk (300 detections per image over 150 of 1203 categories, 12 ground truths, 20 "
+                             "negatives) under rules='lvis', and lvis_match against coco_match on its problem table")
     args = parser.parse_args()
     device = torch.device("cuda", torch.cuda.current_device())
     with tempfile.TemporaryDirectory() as folder:
-        dataset, predictions = make_case(folder, args.images, args.height, args.width, args.detections, args.ground_truths)
+        if args.lvis:
+            dataset, predictions = make_lvis_case(folder, args.images, args.height, args.width)
+        else:
+            dataset, predictions = make_case(folder, args.images, args.height, args.width, args.detections, args.ground_truths)
+    rules = {"rules": "lvis"} if args.lvis else {}
+    frequencies = coco_eval.category_frequencies(dataset) if args.lvis else None
     budget = 1 << 62   # one chunk
     passes = ["bbox", "segm"] + ([("segm", "boundary")] if args.boundary else [])
     for iou_type in passes:
-        coco_eval.match_tables(dataset, predictions, iou_type, device, budget)   # warm-up
+        coco_eval.match_tables(dataset, predictions, iou_type, device, budget, **rules)   # warm-up
     for _ in range(args.repeats):   # the passes alternate, so a drift of the machine meets all of them
         for iou_type in passes:
             torch.cuda.synchronize()
             timer = {}
             t0 = time.perf_counter()
-            tables, cat_ids = coco_eval.match_tables(dataset, predictions, iou_type, device, budget, timer)
+            tables, cat_ids = coco_eval.match_tables(dataset, predictions, iou_type, device, budget, timer, **rules)
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             tables = {iou_type: tables} if isinstance(iou_type, str) else tables
-            results = {name: coco_eval.summarize(coco_eval.accumulate(t, len(cat_ids)), [str(c) for c in cat_ids], {})
-                       for name, t in tables.items()}
+            if args.lvis:
+                results = {name: coco_eval.summarize_lvis(coco_eval.accumulate_lvis(t, len(cat_ids))[0], [str(c) for c in cat_ids],
+                                                          {}, frequencies) for name, t in tables.items()}
+            else:
+                results = {name: coco_eval.summarize(coco_eval.accumulate(t, len(cat_ids)), [str(c) for c in cat_ids], {})
+                           for name, t in tables.items()}
             t2 = time.perf_counter()
             stages = {name: round(sum(s.elapsed_time(e) for s, e in events), 3) for name, events in timer.items()}
             first = next(iter(tables.values()))
-            line = {"iou_type": "+".join(tables), "images": args.images, "size": [args.height, args.width],
+            line = {"rules": "lvis" if args.lvis else "coco", "iou_type": "+".join(tables), "images": args.images, "size": [args.height, args.width],
                     "detections": int(first["det_start"][-1]), "ground_truths": int(first["gt_start"][-1]),
                     "problems": len(first["category"]), "device_ms": stages, "device_ms_total": round(sum(stages.values()), 3),
                     "chunk_wall_ms": round((t1 - t0) * 1e3, 2), "host_accumulate_ms": round((t2 - t1) * 1e3, 2)}
             line.update({"AP" if isinstance(iou_type, str) else f"AP_{name}": r["AP"] for name, r in results.items()})
             print(json.dumps(line), flush=True)
+    if args.lvis:
+        print(json.dumps(time_matching(dataset, predictions, device, budget, max(args.repeats, 1))), flush=True)
 
 
 if __name__ == "__main__":

@@ -18,7 +18,12 @@ scoring.  ``--recall`` (with ``--evaluate``) completes the reference's table: a 
 ... ARl@1000 of the detections scored as class-agnostic proposals, and AR@<limit>_split_<split> (engine/proposal_recall.py, matched
 on the device) -- and COCO's AR1 / AR10 / AR100 / ARs / ARm / ARl plus AR100_split_<split> behind the AP keys.
 ``--boundary-ap`` (with ``--evaluate`` and MODEL.MASK_ON) adds a ``boundary`` task behind ``segm``: Boundary AP (Cheng et al.,
-CVPR 2021; engine/coco_eval.py), segm's keys from a matching on min(mask IoU, boundary IoU).  ``--rpn-recall``
+CVPR 2021; engine/coco_eval.py), segm's keys from a matching on min(mask IoU, boundary IoU).  ``--lvis`` (with
+``--evaluate``) scores every task under LVIS-style federated rules instead -- the annotation file carries
+``neg_category_ids``, ``not_exhaustive_category_ids`` and ``frequency``; AP ... APl, APr, APc, APf, 300 detections per image
+(engine/coco_eval.py ``rules="lvis"``; the rules are restated in include/ovis_hip.h and have not been compared with
+lvis-api's output) -- and writes ``lvis_results.json`` in place of ``coco_results.json``; it combines with ``--boundary-ap``
+and ``--recall``, whose ``box_proposal`` task keeps its own rules.  ``--rpn-recall``
 is a run of its own: backbone + RPN alone (``model.propose``), the proposals gathered like detections into
 ``<OUTPUT_DIR>/inference/<name>/proposals.pth`` and scored by ``objectness`` as an ``rpn_proposal`` task, written to
 ``rpn_recall.json`` -- whether the RPN proposes the unseen classes at all.  ``--export-results`` (rank 0, after the gather, independent of ``--evaluate``) writes the detections as COCO results
@@ -83,6 +88,10 @@ def main(argv=None):
                         help="with --evaluate and MODEL.MASK_ON: also score Boundary AP (Cheng et al., CVPR 2021) -- a boundary "
                              "task behind segm in the table and in coco_results.json: segm's keys, matched on min(mask IoU, "
                              "boundary IoU)")
+    parser.add_argument("--lvis", action="store_true",
+                        help="with --evaluate: score under LVIS-style federated rules (neg_category_ids, "
+                             "not_exhaustive_category_ids, frequency: AP ... APl, APr, APc, APf; 300 detections per image) and "
+                             "write lvis_results.json in place of coco_results.json; box_proposal keeps its own rules")
     parser.add_argument("--rpn-recall", action="store_true",
                         help="run backbone + RPN alone over every test set, save the proposals as "
                              "OUTPUT_DIR/inference/<name>/proposals.pth and score their recall by objectness on the device: an "
@@ -111,6 +120,8 @@ def main(argv=None):
                      "set MODEL.DEVICE cuda")
     if args.recall and not args.evaluate:
         parser.error("--recall adds the recall numbers to what --evaluate scores: give --evaluate too")
+    if args.lvis and not args.evaluate:
+        parser.error("--lvis changes the rules of what --evaluate scores: it is valid only with --evaluate")
     if args.boundary_ap and not args.evaluate:
         parser.error("--boundary-ap adds the boundary task to what --evaluate scores: give --evaluate too")
     if args.boundary_ap and not cfg.MODEL.MASK_ON:
@@ -164,7 +175,7 @@ def main(argv=None):
     else:
         for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
                                         args.evaluate, args.export_results, args.recall, args.bbox_vote,
-                                        args.mask_aug, args.boundary_ap).items():
+                                        args.mask_aug, args.boundary_ap, args.lvis).items():
             if preds is not None:
                 logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:

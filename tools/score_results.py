@@ -7,12 +7,15 @@ without a model, a configuration or the images (engine/coco_eval.py: ``evaluate_
   python tools/score_results.py --ann-file instances_val.json --results-dir OUTPUT_DIR/inference/<name>
   python tools/score_results.py --ann-file instances_val.json --segm segm.json --output scores.json
   python tools/score_results.py --ann-file instances_val.json --segm segm.json --boundary-ap
+  python tools/score_results.py --ann-file lvis_v1_val.json --results-dir DIR --lvis --boundary-ap --recall
 
 Prints the ``Task: ... / names / values`` table ``--evaluate`` logs; ``--output`` writes the numbers as
 ``coco_results.json`` has them.  ``--recall`` adds COCO's AR numbers behind the AP keys, from the same match tables.  ``--boundary-ap`` adds a ``boundary`` task
 behind ``segm``: Boundary AP (Cheng et al., CVPR 2021) of the same ``segm.json`` -- segm's keys from a matching on min(mask IoU,
 boundary IoU), the rule as include/ovis_hip.h states it (not compared with boundary-iou-api's output); the masks are decoded
-once for both.  There is no host-only scoring: the device must be a HIP device.
+once for both.  ``--lvis`` scores every task under LVIS-style federated rules instead -- AP ... APl, APr, APc, APf, with
+``--recall`` AR@300 ...; the annotation file must carry ``neg_category_ids``, ``not_exhaustive_category_ids`` and ``frequency``
+(the ten rules of include/ovis_hip.h; not compared with lvis-api's output).  There is no host-only scoring: the device must be a HIP device.
 """
 import argparse
 import json
@@ -40,6 +43,10 @@ def main(argv=None):
     parser.add_argument("--boundary-ap", action="store_true",
                         help="also score Boundary AP (Cheng et al., CVPR 2021) from the segm results file: a boundary task "
                              "behind segm -- segm's keys, matched on min(mask IoU, boundary IoU)")
+    parser.add_argument("--lvis", action="store_true",
+                        help="LVIS-style federated rules: the annotation file's neg_category_ids / "
+                             "not_exhaustive_category_ids / frequency decide what is judged; 300 detections per image; adds "
+                             "APr / APc / APf (with --recall: AR@300, ARs@300, ARm@300, ARl@300)")
     parser.add_argument("--device", default="cuda", help="the HIP device that scores (cuda, cuda:1, ...)")
     args = parser.parse_args(argv)
     files = {}
@@ -69,7 +76,8 @@ def main(argv=None):
 
     dataset = coco_eval.annotation_dataset(args.ann_file)
     iou_types = IOU_TYPES + (("boundary",) if args.boundary_ap else ())
-    results = coco_eval.evaluate_coco_results(dataset, files, iou_types, device, recall=args.recall)
+    results = coco_eval.evaluate_coco_results(dataset, files, iou_types, device, recall=args.recall,
+                                              **({"rules": "lvis"} if args.lvis else {}))
     print(coco_eval.format_results(results))
     if args.output:
         with open(args.output, "w") as f:

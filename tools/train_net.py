@@ -1,7 +1,7 @@
 """Training entry point with the reference's command line (tools/train_net.py:162-234):
 
     python -m torch.distributed.run --nproc-per-node N tools/train_net.py --config-file CFG [--dataset-catalog FILE]
-        [--evaluate] [--boundary-ap] [--skip-test] KEY VALUE ...
+        [--evaluate] [--boundary-ap] [--lvis] [--skip-test] KEY VALUE ...
 
 One process per GPU (RCCL via torch.distributed, env:// rendezvous), config = defaults <- yaml <- trailing overrides,
 frozen before use.  Without ``--dataset-catalog`` the data stream is the synthetic COCO-shaped generator
@@ -19,7 +19,11 @@ maskrcnn_benchmark/engine/trainer.py:174-203: every rank scores the images it pr
 and after the last iteration the final test (tools/train_net.py:129-159 of the reference), which is what
 ``tools/infer_net.py --evaluate`` does with the final weights -- ``predictions.pth`` and ``coco_results.json`` under
 ``OUTPUT_DIR/inference/<name>/`` -- unless ``--skip-test``.  ``--boundary-ap`` (with ``--evaluate`` and MODEL.MASK_ON) adds
-Boundary AP to both: a ``boundary`` task behind ``segm`` in every table and ``coco_results*.json`` (engine/coco_eval.py).  Without ``--evaluate`` neither runs and ``--skip-test`` has
+Boundary AP to both: a ``boundary`` task behind ``segm`` in every table and ``coco_results*.json`` (engine/coco_eval.py).  ``--lvis`` (with ``--evaluate``) scores both
+under LVIS-style federated rules -- APr / APc / APf of an annotation file with ``neg_category_ids``,
+``not_exhaustive_category_ids`` and ``frequency`` (engine/coco_eval.py ``rules="lvis"``; the rules are restated in
+include/ovis_hip.h and have not been compared with lvis-api's output) -- and writes ``lvis_results*.json`` in place of
+``coco_results*.json``.  Without ``--evaluate`` neither runs and ``--skip-test`` has
 nothing to skip.  The validation loss of the reference's loop is not computed (every shipped yaml sets
 SOLVER.SKIP_VAL_LOSS True; the reference's version runs the training forward, which moves the student-teacher model's
 iteration count), TEST.BBOX_AUG belongs to ``tools/infer_net.py``, and TensorBoard and best-checkpoint tracking are outside
@@ -75,11 +79,14 @@ def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter
 
 
 def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False, dataset_catalog=None,
-          data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False):
+          data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False, lvis=False):
     """``evaluate``: score every DATASETS.TEST set behind every SOLVER.TEST_PERIOD-th iteration
     (engine/evaluation.py::evaluate_in_training) and, unless ``skip_test``, run the final test behind the last one
     (``evaluation.run_datasets``: predictions.pth and coco_results.json under OUTPUT_DIR/inference/<name>/).
-    ``boundary_ap``: both also score the ``boundary`` task (engine/coco_eval.py: Boundary AP), behind ``segm``."""
+    ``boundary_ap``: both also score the ``boundary`` task (engine/coco_eval.py: Boundary AP), behind ``segm``.  ``lvis``:
+    both score under LVIS-style federated rules and write ``lvis_results*.json`` instead."""
+    if lvis and not evaluate:
+        raise ValueError("train(lvis=True) changes the rules of what evaluate=True scores")
     if boundary_ap and not evaluate:
         raise ValueError("train(boundary_ap=True) adds a task to what evaluate=True scores")
     if boundary_ap and not cfg.MODEL.MASK_ON:
@@ -134,7 +141,8 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
         if not cfg.SOLVER.SKIP_VAL_LOSS:
             logger.info("SOLVER.SKIP_VAL_LOSS False: the validation loss is not computed, --evaluate scores AP only")
         evaluator = functools.partial(evaluation.evaluate_in_training, cfg, model, catalog, device,
-                                      train_class_embeddings=e_seen, logger=logger, boundary_ap=boundary_ap)
+                                      train_class_embeddings=e_seen, logger=logger, boundary_ap=boundary_ap,
+                                      lvis=lvis)
     try:
         history = trainer.do_train(cfg, model, data, optimizer, scheduler, max_iter, start_iter=start_iter,
                                    checkpointer=checkpointer if save_checkpoints else None,
@@ -145,7 +153,7 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
     if evaluate and not skip_test:  # tools/train_net.py:129-159: the final test, the route of tools/infer_net.py --evaluate
         comm.synchronize()
         evaluation.run_datasets(cfg, model, catalog, device, logging.getLogger("ovis.inference"), evaluate=True,
-                                boundary_ap=boundary_ap)
+                                boundary_ap=boundary_ap, lvis=lvis)
         comm.synchronize()
     return history
 
@@ -164,6 +172,10 @@ def main(argv=None):
     parser.add_argument("--boundary-ap", action="store_true",
                         help="with --evaluate and MODEL.MASK_ON: also score Boundary AP (Cheng et al., CVPR 2021) -- a boundary "
                              "task behind segm in every logged table and coco_results*.json, periodic and final")
+    parser.add_argument("--lvis", action="store_true",
+                        help="with --evaluate: score under LVIS-style federated rules (neg_category_ids, "
+                             "not_exhaustive_category_ids, frequency: AP ... APl, APr, APc, APf; 300 detections per image) and "
+                             "write lvis_results*.json in place of coco_results*.json")
     parser.add_argument("--max-iter", type=int, default=None, help="override SOLVER.MAX_ITER for a short run")
     parser.add_argument("--no-checkpoints", action="store_true",
                         help="do not write model_<iter>.pth / model_final.pth / last_checkpoint under OUTPUT_DIR and do not "
@@ -196,6 +208,8 @@ def main(argv=None):
     if args.evaluate and cfg.MODEL.DEVICE != "cuda":
         parser.error("--evaluate scores on the HIP device (mask IoU and matching have no host implementation): "
                      "set MODEL.DEVICE cuda")
+    if args.lvis and not args.evaluate:
+        parser.error("--lvis changes the rules of what --evaluate scores: it is valid only with --evaluate")
     if args.boundary_ap and not args.evaluate:
         parser.error("--boundary-ap adds the boundary task to what --evaluate scores: give --evaluate too")
     if args.boundary_ap and not cfg.MODEL.MASK_ON:
@@ -225,7 +239,7 @@ def main(argv=None):
     train(cfg, args.local_rank, distributed, args.max_iter or cfg.SOLVER.MAX_ITER, ims_per_gpu,
           save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input,
           dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed, evaluate=args.evaluate,
-          skip_test=args.skip_test, boundary_ap=args.boundary_ap)
+          skip_test=args.skip_test, boundary_ap=args.boundary_ap, lvis=args.lvis)
     if distributed:
         dist.destroy_process_group()
 
