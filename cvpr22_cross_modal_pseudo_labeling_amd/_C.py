@@ -2137,6 +2137,46 @@ def lvis_match(iou, problems, det_areas, gt_areas, gt_ignore_in, problem_not_exh
     return dt_match, dt_ignore, gt_ignore
 
 
+ERROR_TYPES = ("none", "Cls", "Loc", "Both", "Dupe", "Bkg")  # the codes of err_type (include/ovis_hip.h, "Error analysis")
+
+
+def error_types(iou, images, det_category, det_match, det_ignore, gt_category, gt_crowd, fg_threshold=0.5, bg_threshold=0.1):
+    """The error type of every detection and the missed ground truths of a chunk of images (``ovis_error_types``; the rules:
+    "Error analysis" in include/ovis_hip.h).  images: a ``CocoProblems`` with ONE ROW PER IMAGE; iou: the flat fp64 buffer
+    ``coco_box_iou`` / ``coco_mask_iou`` return for that table -- every detection of an image against every ground truth of
+    it; det_category int32 [D]; det_match int32 [D], the chunk-global row of the ground truth the base matching gave the
+    detection or -1; det_ignore uint8 [D]; gt_category int32 [G]; gt_crowd uint8 [G]; all on the device.  -> (err_type uint8
+    [D]: the index into ``ERROR_TYPES``, err_gt int32 [D]: the chunk-global row of the target or -1, gt_missed uint8 [G]).
+    Rows no image of the table covers come back as 0 / -1 / 0."""
+    iou = _dev(iou, "iou", torch.float64)
+    det_category, det_match = _dev(det_category, "det_category", torch.int32), _dev(det_match, "det_match", torch.int32)
+    det_ignore = _dev(det_ignore, "det_ignore", torch.uint8)
+    gt_category, gt_crowd = _dev(gt_category, "gt_category", torch.int32), _dev(gt_crowd, "gt_crowd", torch.uint8)
+    if det_category.dim() != 1 or det_match.shape != det_category.shape or det_ignore.shape != det_category.shape \
+            or gt_category.dim() != 1 or gt_crowd.shape != gt_category.shape:
+        raise RuntimeError("error_types: expected det_category / det_match / det_ignore [D] and gt_category / gt_crowd [G]")
+    d, g = det_category.numel(), gt_category.numel()
+    images.check("error_types", d, g, iou_numel=iou.numel())
+    host = images.host
+    if len(images) > 1 and (bool((host[1:, 0] < host[:-1, 0] + host[:-1, 1]).any())
+                            or bool((host[1:, 2] < host[:-1, 2] + host[:-1, 3]).any())):
+        raise RuntimeError("error_types: the images of the table must hold disjoint, ascending row ranges")
+    err_type = torch.zeros((d,), dtype=torch.uint8, device=iou.device)
+    err_gt = torch.full((d,), -1, dtype=torch.int32, device=iou.device)
+    gt_missed = torch.zeros((g,), dtype=torch.uint8, device=iou.device)
+    if len(images) == 0 or (d == 0 and g == 0):
+        return err_type, err_gt, gt_missed
+    with _on(iou.device):
+        rc = _L.ovis_error_types(iou.data_ptr() if iou.numel() else 0, images.dev.data_ptr(), len(images),
+                                 int(host[:, 1].max()), images.max_gts, det_category.data_ptr() if d else 0,
+                                 det_match.data_ptr() if d else 0, det_ignore.data_ptr() if d else 0,
+                                 gt_category.data_ptr() if g else 0, gt_crowd.data_ptr() if g else 0, float(fg_threshold),
+                                 float(bg_threshold), d, g, err_type.data_ptr() if d else 0, err_gt.data_ptr() if d else 0,
+                                 gt_missed.data_ptr() if g else 0, _stream())
+    _lib.check(rc, "error_types")
+    return err_type, err_gt, gt_missed
+
+
 COCO_RLE_STATUS = {_lib.OVIS_COCO_RLE_BAD_CHAR: "a character outside '0'..'o'",
                    _lib.OVIS_COCO_RLE_UNTERMINATED: "the last value is not terminated",
                    _lib.OVIS_COCO_RLE_OVERFLOW: "a value does not fit 32 bits",

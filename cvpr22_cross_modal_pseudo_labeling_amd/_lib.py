@@ -13,8 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libovis_hip.so")
 INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 
-_BY_VALUE = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
-             "uint64_t": ctypes.c_uint64}
+_BY_VALUE = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+             "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64}
 _POINTEES = {"void", "float", "double", "int32_t", "int64_t", "uint32_t", "uint64_t", "uint8_t"}
 
 

@@ -53,6 +53,11 @@ truth and ignores the unmatched detections of not-exhaustive categories (``_C.lv
 dimension (``accumulate_lvis``) and APr / APc / APf beside the COCO keys (``summarize_lvis``).  Every iou_type takes the
 keyword, boundary included; everything image-sized is shared with COCO scoring.
 
+ERROR ANALYSIS.  ``error_thresholds=(t_f, t_b)`` (default None: nothing changes) on ``score_chunk``, ``match_tables``,
+``results_match_tables``, ``evaluate_coco`` and ``evaluate_coco_results`` adds, for bbox and segm under ``rules="coco"``, one IoU
+call on a table with one row per image and ``_C.error_types`` (csrc/error_types.hip); the tables then carry ``err_type``,
+``err_gt``, ``gt_missed`` and the rows' images, which engine/error_analysis.py turns into dAP50 per error type.
+
 SHARDED.  ``evaluate_coco_sharded`` is ``evaluate_coco`` for a caller that holds one rank's {dataset index: BoxList} instead of
 the gathered list (a training run's periodic evaluation, engine/evaluation.py): an image's matching does not depend on any
 other image, so every rank scores the images it predicted on its own device and only the match tables go to rank 0, where
@@ -528,11 +533,13 @@ def load_coco_results(dataset, results, iou_type, rules="coco", lvis_max_dets=LV
     return rows
 
 
-def _chunks(images, dets, with_masks, budget, max_images=None, boundary=False):
+def _chunks(images, dets, with_masks, budget, max_images=None, boundary=False, errors=False):
     """Lists of consecutive image indices: a chunk closes before the image that would take it over ``budget`` bytes of
     masks, over ``max_images`` (None: MAX_CHUNK_IMAGES) or -- for segm -- over MAX_CALL_MASKS detections, ground truths or
     polygons.  An image that breaks a limit alone still gets its own chunk.  ``boundary``: a mask costs 11 / 8 byte per
-    pixel instead of 9 / 8 -- its boundary words (10 / 8), and as much again for ``_C.coco_boundary_words``' scratch."""
+    pixel instead of 9 / 8 -- its boundary words (10 / 8), and as much again for ``_C.coco_boundary_words``' scratch.
+    ``errors`` (error analysis, engine/error_analysis.py): the image-level IoU block of an image, 8 bytes per (detection,
+    ground truth) pair over ALL its categories, is planned on top, for box scoring too."""
     max_images = MAX_CHUNK_IMAGES if max_images is None else max_images
     chunk, used = [], np.zeros(4, dtype=np.int64)
     limits = np.asarray([budget, MAX_CALL_MASKS, MAX_CALL_MASKS, MAX_CALL_MASKS], dtype=np.float64)
@@ -540,6 +547,8 @@ def _chunks(images, dets, with_masks, budget, max_images=None, boundary=False):
         n_det, n_gt = len(det["cats"]), len(image["cats"])
         cost = np.asarray([(n_det + n_gt) * image["height"] * image["width"] * (11 if boundary else 9) // 8, n_det, n_gt,
                            image["polygons"]], dtype=np.int64) * (1 if with_masks else 0)
+        if errors:
+            cost[0] += n_det * n_gt * 8
         if chunk and (np.any(used + cost > limits) or len(chunk) >= max_images):
             yield chunk
             chunk, used = [], np.zeros(4, dtype=np.int64)
@@ -597,7 +606,20 @@ def _boundary_group(words_parts, bwords_parts, bareas_out, group_rows, height, w
     bareas_out[group_rows] = bareas
 
 
-def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco"):
+def _image_problems(images, dets, det_image_base, gt_image_base, image_words, device):
+    """The chunk's image-level table (error analysis): ``CocoProblems`` with one row per image -- all its detection rows
+    against all its ground-truth rows; ``image_words``: image -> (first det word, first gt word, words per mask), or None
+    for boxes."""
+    rows, off = [], 0
+    for i, (image, det) in enumerate(zip(images, dets)):
+        nd, ng = len(det["cats"]), len(image["cats"])
+        rows.append([det_image_base[i], nd, gt_image_base[i], ng, off] + list(image_words[i] if image_words else (0, 0, 0)))
+        off += nd * ng
+    return _C.CocoProblems(np.asarray(rows, dtype=np.int64).reshape(-1, 8), device)
+
+
+def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco",
+                error_thresholds=None):
     """The match tables of one chunk of images (the NumPy form ``accumulate`` takes): a constant number of launches --
     box or mask IoU and the matching -- plus, for segm, the paste, rasterise and pack calls of every image size; detections
     that carry ``rle`` (``load_coco_results``) and RLE ground truth take one ``_C.coco_rle_words`` call per image size
@@ -610,7 +632,16 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
 
     ``rules="lvis"`` (``images`` / ``dets`` from ``_ground_truth`` / ``_detections`` under the same rules): the IoU entries
     get all-zero crowd flags, and ``_C.lvis_match`` takes the place of ``_C.coco_match`` -- with the annotations' ignore
-    flags and one not-exhaustive flag per problem (rules 7 and 8 of include/ovis_hip.h)."""
+    flags and one not-exhaustive flag per problem (rules 7 and 8 of include/ovis_hip.h).
+
+    ``error_thresholds=(t_f, t_b)`` (default None: nothing changes, not a key, not a launch): the error analysis of
+    include/ovis_hip.h for bbox and segm.  One more IoU call on a table with ONE ROW PER IMAGE fills the image-level buffer
+    -- every detection of an image against every ground truth of it, from the box rows or the mask words that are already
+    there -- and ``_C.error_types`` reads it beside the base matching ``dt_match[0, 0]``.  Their tables gain ``err_type`` uint8
+    [D], ``err_gt`` int32 [D] (the chunk's ground-truth row or -1), ``gt_missed`` uint8 [G], ``det_image`` / ``gt_image`` (the
+    row's image, counted inside the chunk) and ``num_images``.  boundary's tables are not analysed."""
+    if error_thresholds is not None and rules != "coco":
+        raise ValueError("evaluate_coco: the error analysis follows COCO's rules only (rules='coco')")
     types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type)
     with_masks, boundary = types[0] != "bbox", "boundary" in types
     rows, det_base, gt_base, iou_off = [], 0, 0, 0
@@ -641,6 +672,10 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
         with _stage(timer, "iou"):
             iou = _C.coco_box_iou(det_xywh, gt_xywh, crowd, problems)
             det_areas = det_xywh[:, 2] * det_xywh[:, 3]
+        if error_thresholds is not None:
+            image_problems = _image_problems(images, dets, det_image_base, gt_image_base, None, device)
+            with _stage(timer, "image_iou"):
+                image_iou = _C.coco_box_iou(det_xywh, gt_xywh, crowd, image_problems)
     else:
         groups = {}
         for i, image in enumerate(images):
@@ -719,6 +754,10 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
         if "segm" in types:
             with _stage(timer, "iou"):
                 iou = _C.coco_mask_iou(det_words, det_areas_i, gt_words, gt_areas_i, crowd, problems)
+            if error_thresholds is not None:  # the same words once more, addressed image by image
+                image_problems = _image_problems(images, dets, det_image_base, gt_image_base, image_words, device)
+                with _stage(timer, "image_iou"):
+                    image_iou = _C.coco_mask_iou(det_words, det_areas_i, gt_words, gt_areas_i, crowd, image_problems)
         if boundary:
             with _stage(timer, "boundary_iou"):
                 boundary_iou = _C.coco_boundary_iou(det_words, torch.cat(det_bwords) if det_bwords else empty, det_areas_i,
@@ -728,6 +767,12 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
     thresholds = torch.from_numpy(IOU_THRESHOLDS).to(device)
     area_ranges = torch.from_numpy(AREA_RANGES).to(device)
     tables = {}
+    if error_thresholds is not None:
+        det_cat = torch.from_numpy(np.concatenate([d["cats"] for d in dets] + [np.zeros(0, np.int64)]).astype(np.int32)).to(device)
+        gt_cat = torch.from_numpy(np.concatenate([im["cats"] for im in images] + [np.zeros(0, np.int64)]).astype(np.int32)).to(device)
+        det_gt_base = torch.from_numpy(np.repeat(table[:, 2], table[:, 1]).astype(np.int32)).to(device)
+        det_image = np.repeat(np.arange(len(images)), [len(d["cats"]) for d in dets])
+        gt_image = np.repeat(np.arange(len(images)), [len(im["cats"]) for im in images])
     for name in types:
         with _stage(timer, "match"):
             if rules == "lvis":
@@ -741,6 +786,14 @@ def score_chunk(images, dets, iou_type, device, timer=None, boundary_dilation_ra
                         "gt_start": np.concatenate([table[:, 2], [num_gts]]), "scores": scores,
                         "dt_match": dt_match.cpu().numpy(), "dt_ignore": dt_ignore.cpu().numpy(),
                         "gt_ignore": gt_ignore.cpu().numpy()}
+        if error_thresholds is not None and name != "boundary":
+            with _stage(timer, "error_types"):
+                base = dt_match[0, 0]  # the ground truth's index inside its problem -> its row in the chunk
+                err_type, err_gt, gt_missed = _C.error_types(
+                    image_iou, image_problems, det_cat, torch.where(base >= 0, base + det_gt_base, base),
+                    dt_ignore[0, 0].view(torch.uint8), gt_cat, crowd, *error_thresholds)
+            tables[name].update(err_type=err_type.cpu().numpy(), err_gt=err_gt.cpu().numpy(), gt_missed=gt_missed.cpu().numpy(),
+                                det_image=det_image, gt_image=gt_image, num_images=len(images))
     return tables[iou_type] if isinstance(iou_type, str) else tables
 
 
@@ -753,13 +806,24 @@ def concatenate_tables(parts):
         det_off += p["det_start"][-1]
         gt_off += p["gt_start"][-1]
     num_a, num_t = len(AREA_RANGES), len(IOU_THRESHOLDS)
+    errors = {}
+    if parts and all("err_type" in p for p in parts):  # the error analysis' arrays travel with the tables they belong to
+        gt_offs = np.cumsum([0] + [p["gt_start"][-1] for p in parts])
+        image_offs = np.cumsum([0] + [p["num_images"] for p in parts])
+        errors = {"err_type": np.concatenate([p["err_type"] for p in parts]),
+                  "err_gt": np.concatenate([np.where(p["err_gt"] >= 0, p["err_gt"] + off, -1).astype(np.int32)
+                                            for p, off in zip(parts, gt_offs)]),
+                  "gt_missed": np.concatenate([p["gt_missed"] for p in parts]),
+                  "det_image": np.concatenate([p["det_image"] + off for p, off in zip(parts, image_offs)]),
+                  "gt_image": np.concatenate([p["gt_image"] + off for p, off in zip(parts, image_offs)]),
+                  "num_images": int(image_offs[-1])}
     return {"category": np.concatenate([p["category"] for p in parts] + [np.zeros(0, np.int64)]),
             "det_start": np.concatenate(det_start + [np.asarray([det_off], dtype=np.int64)]),
             "gt_start": np.concatenate(gt_start + [np.asarray([gt_off], dtype=np.int64)]),
             "scores": np.concatenate([p["scores"] for p in parts] + [np.zeros(0)]),
             "dt_match": np.concatenate([p["dt_match"] for p in parts] + [np.zeros((num_a, num_t, 0), np.int32)], axis=2),
             "dt_ignore": np.concatenate([p["dt_ignore"] for p in parts] + [np.zeros((num_a, num_t, 0), bool)], axis=2),
-            "gt_ignore": np.concatenate([p["gt_ignore"] for p in parts] + [np.zeros((num_a, 0), bool)], axis=1)}
+            "gt_ignore": np.concatenate([p["gt_ignore"] for p in parts] + [np.zeros((num_a, 0), bool)], axis=1), **errors}
 
 
 def _job_types(iou_type, who):
@@ -773,13 +837,15 @@ def _job_types(iou_type, who):
 
 
 def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None,
-                 boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
+                 boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS,
+                 error_thresholds=None):
     """-> (the match tables of every (image, category) problem of the annotation file, in image-id order; the sorted
     category ids).  ``budget``: the bytes of device memory a chunk may plan with (None: a quarter of what is free);
     ``max_images``: the most images of a chunk (None: MAX_CHUNK_IMAGES); ``ground_truth``: ``_ground_truth(dataset, rules)``
     when the caller already has it.  ``iou_type``: bbox, segm, boundary, or the tuple ("segm", "boundary") -- then the first
     item is {name: tables}, both from one set of mask words per chunk.  ``rules="lvis"``: LVIS-style federated scoring
-    (include/ovis_hip.h), at most ``lvis_max_dets`` detections per image."""
+    (include/ovis_hip.h), at most ``lvis_max_dets`` detections per image.  ``error_thresholds=(t_f, t_b)``: the tables of
+    bbox and segm also carry the error analysis' arrays (``score_chunk``)."""
     types = _job_types(iou_type, "evaluate_coco")
     _check_rules(rules, "evaluate_coco")
     if len(predictions) > len(dataset):
@@ -791,33 +857,39 @@ def match_tables(dataset, predictions, iou_type, device, budget=None, timer=None
     by_image = {dataset.id_to_img_map[idx]: pred for idx, pred in enumerate(predictions)}
     dets = [_detections(by_image.get(image["id"]), image, label_to_cat, types[0] != "bbox", rules, lvis_max_dets)
             for image in images]
-    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio, rules), cat_ids
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio, rules,
+                       error_thresholds), cat_ids
 
 
 def _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio=BOUNDARY_DILATION_RATIO,
-                rules="coco"):
+                rules="coco", error_thresholds=None):
     """The match tables of the images' ground truth and detection rows, chunk by chunk ({name: tables} for a tuple)."""
     if budget is None:
         budget = torch.cuda.mem_get_info(device)[0] // 4
     types = (iou_type,) if isinstance(iou_type, str) else tuple(iou_type)
     extra = {} if rules == "coco" else {"rules": rules}
+    if error_thresholds is not None:
+        extra["error_thresholds"] = tuple(float(t) for t in error_thresholds)
     parts = [score_chunk([images[i] for i in chunk], [dets[i] for i in chunk], iou_type, device, timer, boundary_dilation_ratio,
                          **extra)
-             for chunk in _chunks(images, dets, types[0] != "bbox", budget, max_images, "boundary" in types)]
+             for chunk in _chunks(images, dets, types[0] != "bbox", budget, max_images, "boundary" in types,
+                                  error_thresholds is not None)]
     if isinstance(iou_type, str):
         return concatenate_tables(parts)
     return {name: concatenate_tables([part[name] for part in parts]) for name in types}
 
 
 def results_match_tables(dataset, results, iou_type, device, budget=None, timer=None, max_images=None, ground_truth=None,
-                         boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
+                         boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS,
+                         error_thresholds=None):
     """``match_tables`` for the detections of a results file (``results``: what ``load_coco_results`` takes)."""
     types = _job_types(iou_type, "evaluate_coco_results")
     _check_rules(rules, "evaluate_coco_results")
     device = torch.device(device)
     cat_ids, images = ground_truth if ground_truth is not None else _ground_truth(dataset, rules)
     dets = load_coco_results(dataset, results, types[0], rules, lvis_max_dets, images)
-    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio, rules), cat_ids
+    return _score_rows(images, dets, iou_type, device, budget, timer, max_images, boundary_dilation_ratio, rules,
+                       error_thresholds), cat_ids
 
 
 def _scoring_device(device, who):
@@ -827,7 +899,7 @@ def _scoring_device(device, who):
     return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
 
 
-def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth=None, rules="coco"):
+def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth=None, rules="coco", tables_out=None):
     """{iou_type: ``summarize`` of ``accumulate`` of ``tables_of(iou_type, ground truth)``} with the dataset's names,
     splits and class order; ``recall``: followed by ``summarize_recall`` of ``accumulate_recall`` of the same tables.
     When segm and boundary are both asked for, ``tables_of`` is called ONCE for the two, with the tuple ("segm",
@@ -843,6 +915,8 @@ def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth
         for job in _jobs(iou_types):
             tables, _ = tables_of(job, ground_truth)
             scored.update({job: tables} if isinstance(job, str) else tables)
+        if tables_out is not None:  # the caller goes on with the match tables themselves (engine/error_analysis.py)
+            tables_out.update(scored, cat_ids=cat_ids)
         for iou_type in iou_types:
             tables = scored[iou_type]
             if rules == "lvis":
@@ -859,7 +933,8 @@ def _summaries(dataset, iou_types, device, tables_of, recall=False, ground_truth
 
 
 def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda", recall=False,
-                  boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
+                  boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS,
+                  error_thresholds=None, tables_out=None):
     """{iou_type: OrderedDict of AP, AP50, AP75, APs, APm, APl, AP50_class_<name> per category (in the order of
     ``dataset.categories``, as ``COCOResults.update`` iterates) and AP50_split_<split> per key of ``dataset.class_splits``}
     for ``predictions``: the list ``inference()`` returns or ``torch.load`` gives from ``predictions.pth`` (BoxLists in
@@ -876,11 +951,22 @@ def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda
     every iou_type, boundary included: at most ``lvis_max_dets`` detections per image over all categories (negative: no
     cap), detections of categories nobody looked for in the image are not judged, and the keys are AP ... APl, APr, APc,
     APf, AP50_class_<name>, AP50_split_<split>, with ``recall`` AR@300, ARs@300, ARm@300, ARl@300, AR@300_split_<split>.
-    The rules are restated, not imported: the numbers have not been compared with lvis-api's output."""
+    The rules are restated, not imported: the numbers have not been compared with lvis-api's output.
+
+    ``error_thresholds=(t_f, t_b)`` with ``tables_out={}`` (``rules="coco"`` only): the same pass also types the errors
+    (``score_chunk``), and ``tables_out`` receives {iou_type: match tables} and ``cat_ids`` for
+    ``engine.error_analysis.analyze_scored``; the returned numbers are those of a call without the two, bit for bit."""
     device = _scoring_device(device, "evaluate_coco")
     for iou_type in iou_types:
         _check_iou_type(iou_type, "evaluate_coco")
     _check_rules(rules, "evaluate_coco")
+    if error_thresholds is not None:
+        if rules != "coco":
+            raise ValueError("evaluate_coco: the error analysis follows COCO's rules only (rules='coco')")
+        return _summaries(dataset, iou_types, device,
+                          lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt,
+                                                            boundary_dilation_ratio=boundary_dilation_ratio,
+                                                            error_thresholds=error_thresholds), recall, tables_out=tables_out)
     if rules == "coco":
         return _summaries(dataset, iou_types, device,
                           lambda iou_type, gt: match_tables(dataset, predictions, iou_type, device, ground_truth=gt,
@@ -892,12 +978,14 @@ def evaluate_coco(dataset, predictions, iou_types=("bbox", "segm"), device="cuda
 
 
 def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="cuda", recall=False,
-                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS):
+                          boundary_dilation_ratio=BOUNDARY_DILATION_RATIO, rules="coco", lvis_max_dets=LVIS_MAX_DETS,
+                          error_thresholds=None, tables_out=None):
     """``evaluate_coco``'s numbers, in the same structure, for detections that come from COCO results files: ``results`` is
     {iou_type: a path or the parsed list} (``load_coco_results``); an iou_type it does not have is skipped -- but boundary
     reads the ``"boundary"`` entry when there is one and else the ``"segm"`` one: it scores the same ``segm.json``.  Whatever
     wrote the files -- ``export_coco_results``, the reference, another tool -- nothing but the annotation file is needed
-    beside them.  ``recall``, ``boundary_dilation_ratio``, ``rules``, ``lvis_max_dets``: as in ``evaluate_coco``.  ``device``:
+    beside them.  ``recall``, ``boundary_dilation_ratio``, ``rules``, ``lvis_max_dets``, ``error_thresholds`` / ``tables_out`` (one
+    file for segm and boundary): as in ``evaluate_coco``.  ``device``:
     the HIP device that decodes the masks and scores; there is no host-only scoring."""
     device = _scoring_device(device, "evaluate_coco_results")
     _check_rules(rules, "evaluate_coco_results")
@@ -907,6 +995,13 @@ def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="
     if "boundary" not in files and "segm" in files:
         files["boundary"] = files["segm"]
     iou_types = [t for t in iou_types if t in files]
+    errors = {}
+    if error_thresholds is not None:
+        if rules != "coco":
+            raise ValueError("evaluate_coco_results: the error analysis follows COCO's rules only (rules='coco')")
+        if "boundary" in files and files["boundary"] is not files["segm"]:
+            raise ValueError("evaluate_coco_results: the error analysis scores segm and boundary from one results file")
+        errors = {"error_thresholds": error_thresholds}
     if all(t in iou_types for t in MASK_IOU_TYPES) and files["boundary"] is not files["segm"]:  # two files: two passes
         return OrderedDict((t, evaluate_coco_results(dataset, {t: files[t]}, (t,), device, recall, boundary_dilation_ratio,
                                                      rules, lvis_max_dets)[t])
@@ -914,8 +1009,9 @@ def evaluate_coco_results(dataset, results, iou_types=("bbox", "segm"), device="
 
     def tables_of(job, gt):
         return results_match_tables(dataset, files[job if isinstance(job, str) else job[0]], job, device, ground_truth=gt,
-                                    boundary_dilation_ratio=boundary_dilation_ratio, rules=rules, lvis_max_dets=lvis_max_dets)
-    return _summaries(dataset, iou_types, device, tables_of, recall, rules=rules)
+                                    boundary_dilation_ratio=boundary_dilation_ratio, rules=rules, lvis_max_dets=lvis_max_dets,
+                                    **errors)
+    return _summaries(dataset, iou_types, device, tables_of, recall, rules=rules, tables_out=tables_out)
 
 
 # ---- every rank scores what it predicted: only match tables travel --------------------------------------------------------

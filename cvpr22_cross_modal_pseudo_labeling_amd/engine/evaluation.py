@@ -23,7 +23,7 @@ from collections import OrderedDict
 
 import torch
 
-from . import coco_eval, coco_results, comm, inference, proposal_recall, visualize
+from . import coco_eval, coco_results, comm, error_analysis, inference, proposal_recall, visualize
 from ..data.build import build_dataset, make_data_loader
 from ..data.prefetch import DevicePrefetcher
 from ..data.transforms import build_transforms
@@ -50,15 +50,22 @@ def results_file_name(lvis=False, iteration=None):
     return stem + ".json" if iteration is None else "{}_{:07d}.json".format(stem, iteration)
 
 
-def save_evaluation(dataset, predictions, folder, iou_types, device, logger, recall=False, lvis=False):
+def save_evaluation(dataset, predictions, folder, iou_types, device, logger, recall=False, lvis=False, errors=False):
     """COCO scoring of one test set (engine/coco_eval.py): the table goes to the log, the numbers to
     ``folder``/coco_results.json as {iou_type: {metric: value}}.  ``recall``: the reference's whole table -- a
     ``box_proposal`` task first (engine/proposal_recall.py: the detections scored as proposals by their ``scores``, which is
     what the reference's table shows, its post-processor copying ``scores`` into ``objectness``), and the AR keys behind the
     AP keys of every iou_type.  ``lvis``: every iou_type under LVIS-style federated rules (``evaluate_coco(rules="lvis")``:
     APr / APc / APf, AR@300; the annotation file must be federatedly annotated), written to ``lvis_results.json``; the
-    ``box_proposal`` task keeps its own rules."""
+    ``box_proposal`` task keeps its own rules.  ``errors``: the error analysis of engine/error_analysis.py for bbox and segm
+    from the SAME scoring pass -- an ``errors_bbox`` / ``errors_segm`` table behind the others in the log and
+    ``folder``/error_analysis.json; ``coco_results.json`` is byte for byte what it is without it."""
+    if errors and lvis:
+        raise ValueError("save_evaluation: the error analysis follows COCO's rules only; it does not go with lvis=True")
     rules = {"rules": "lvis"} if lvis else {}
+    scored = {}
+    if errors:
+        rules = {"error_thresholds": (error_analysis.FG_THRESHOLD, error_analysis.BG_THRESHOLD), "tables_out": scored}
     if recall:
         results = OrderedDict(box_proposal=proposal_recall.evaluate_box_proposals(dataset, predictions, device, "scores"))
         results.update(coco_eval.evaluate_coco(dataset, predictions, iou_types, device, recall=True, **rules))
@@ -67,6 +74,11 @@ def save_evaluation(dataset, predictions, folder, iou_types, device, logger, rec
     logger.info(coco_eval.format_results(results))
     with open(os.path.join(folder, results_file_name(lvis)), "w") as f:
         json.dump(results, f, indent=1)
+    if errors:
+        analysis = error_analysis.analyze_scored(dataset, scored, scored["cat_ids"])
+        logger.info(coco_eval.format_results(error_analysis.task_tables(analysis)))
+        with open(os.path.join(folder, "error_analysis.json"), "w") as f:
+            json.dump(analysis, f, indent=1)
     return results
 
 
@@ -109,13 +121,17 @@ def scored_iou_types(cfg, boundary_ap=False):
 
 
 def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
-                 export_results=False, recall=False, vote_thresh=None, average_masks=False, boundary_ap=False, lvis=False):
+                 export_results=False, recall=False, vote_thresh=None, average_masks=False, boundary_ap=False, lvis=False,
+                 error_analysis=False):
     """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}.  ``vote_thresh`` /
     ``average_masks``: box voting and view-averaged masks of multi-scale / flip testing (engine/bbox_aug.py);
     ``boundary_ap``: with ``evaluate``, a ``boundary`` task behind ``segm`` (engine/coco_eval.py: Boundary AP); ``lvis``: with
-    ``evaluate``, LVIS-style federated rules and ``lvis_results.json`` (``save_evaluation``)."""
+    ``evaluate``, LVIS-style federated rules and ``lvis_results.json`` (``save_evaluation``); ``error_analysis``: with
+    ``evaluate`` and without ``lvis``, the error tables and ``error_analysis.json`` (``save_evaluation(errors=True)``)."""
     if lvis and not evaluate:
         raise ValueError("run_datasets: lvis=True changes the rules of what evaluate=True scores")
+    if error_analysis and (lvis or not evaluate):
+        raise ValueError("run_datasets: error_analysis=True analyses what evaluate=True scores under COCO's rules")
     iou_types = scored_iou_types(cfg, boundary_ap and evaluate)
     transform = build_transforms(cfg, is_train=False)
     results = {}
@@ -139,7 +155,7 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
                              "set OUTPUT_DIR")
         if evaluate and results[name] is not None:
             save_evaluation(dataset, results[name], out, iou_types, device, logger or logging.getLogger("ovis.inference"),
-                            recall, lvis)
+                            recall, lvis, *((True,) if error_analysis else ()))
         if export_results and results[name] is not None:
             coco_results.export_coco_results(dataset, results[name], out, ("bbox", "segm") if cfg.MODEL.MASK_ON else ("bbox",),
                                              device)

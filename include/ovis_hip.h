@@ -1016,6 +1016,73 @@ int ovis_lvis_match(const double* iou, const int64_t* problems, int num_problems
                     const double* area_ranges, int num_areas, const double* thresholds, int num_thresholds, long num_dets,
                     long num_gts, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore, void* stream);
 
+/* Error analysis -- AP50 broken down by error type (csrc/error_types.hip, engine/error_analysis.py; Bolya et al., "TIDE: A
+ * General Toolbox for Identifying Object Detection Errors", ECCV 2020 -- the reference does not do it).  tidecv is not a
+ * dependency: the rules are restated and THIS TEXT is the contract; the numbers follow it and have NOT been compared with
+ * tidecv's own output.
+ *   SCOPE.  COCO rules only: area range "all", 100 detections per category and image, bbox and segm.  Thresholds t_f = 0.5
+ *     (foreground) and t_b = 0.1 (background), compared in fp64; keywords of the Python functions, no command-line switch.
+ *   BASE.  The existing matching at (area all, IoU 0.5): dt_match[0, 0], dt_ignore[0, 0] and gt_ignore[0].  A detection is
+ *     a false positive when it is unmatched; under area "all" an unmatched detection is never ignored.  A detection
+ *     matched to a crowd is ignored and is not an error.  Crowd ground truths take no part in what follows.
+ *   IMAGE IOU.  For every image the IoU of all its detection rows against all its ground-truth rows: box IoU for bbox,
+ *     mask IoU on the packed words for segm.  Only entries against non-crowd ground truths are read, so the non-crowd form
+ *     is all that matters.  For a false positive d of category c, s is the largest IoU over the non-crowd ground truths
+ *     of category c and g_s that ground truth; o and g_o are the same over the non-crowd ground truths of every other
+ *     category.  A maximum over an empty set is 0 with target -1.  An equal IoU goes to the later ground-truth row (the
+ *     project's tie rule everywhere else).
+ *   TYPES.  The first rule that holds applies:
+ *     1. Loc:  t_b <= s < t_f, target g_s.  Right class, badly localised.
+ *     2. Cls:  o >= t_f, target g_o.  Well localised, wrong class.
+ *     3. Dupe: s >= t_f, target g_s.  Every such ground truth was taken by a better-scoring detection.
+ *     4. Bkg:  max(s, o) <= t_b.
+ *     5. Both: everything else.  Wrong class and badly localised.
+ *   MISSED.  A non-crowd ground truth is Miss when no detection is matched to it in the base and it is the target of no
+ *     Loc or Cls error.
+ *   FIXES, each applied alone.  Dupe, Bkg, Both: those detections are deleted.  Loc: the detection becomes a true positive
+ *     of its target if the target is free, otherwise it is deleted.  Cls: the detection moves, with its score, into the
+ *     target's category; it becomes a true positive there if the target is free, otherwise it is deleted.  Free means
+ *     unmatched in the base and not yet claimed in this pass; among fixed detections with the same target the one with
+ *     the highest score claims it, ties going to the earlier detection row.  Miss: the missed ground truths are removed,
+ *     with their count.  FalsePos: every false positive is deleted.  FalseNeg: every unmatched non-crowd ground truth is
+ *     removed.
+ *   DAP.  dAP50_<T> is the AP50 after fix T minus the base AP50.  AP50 is the scorer's own: descending score, stable,
+ *     merged in image-id order (the detection rows' order: image, category index, descending score; a moved detection
+ *     keeps its row), tp / (tp + fp + spacing(1)), the envelope from the right, 101 recall samples, the mean over the
+ *     categories with at least one ground truth left.  A category left without ground truth by a fix drops out of that
+ *     mean.  If no category remains, or the base is -1, the dAP is -1.  dAP50_<T>_split_<split> is the same with both means
+ *     restricted to the categories of a split.
+ * Out of scope: LVIS rules, Boundary IoU, other thresholds from the command line, TIDE's plots, host-only analysis.
+ *
+ * ovis_error_types (IMAGE IOU's maxima, TYPES and MISSED for one chunk of images):
+ *   iou           fp64, the image-level IoU buffer: ovis_coco_box_iou_f64 / ovis_coco_mask_iou_f64 called on `images`.  May
+ *                 be NULL when no image has both a detection and a ground truth (nothing reads it).
+ *   images        int64 [num_images, 8], the problem-table layout with ONE ROW PER IMAGE: (first detection row, detections,
+ *                 first ground-truth row, ground truths, offset of the image's [detections, ground truths] block in `iou`,
+ *                 first detection word, first ground-truth word, words per mask).  The last three are not read here.  The
+ *                 rows of the images are disjoint; the kernels trust the table (the Python shim checks it on the host).
+ *   max_dets, max_gts   the largest detection / ground-truth count of a row of `images`: they size the grids only.
+ *   det_category  int32 [num_dets]: the detection's category index.
+ *   det_match     int32 [num_dets]: the CHUNK-GLOBAL row of the ground truth the base matched the detection to, or -1.
+ *   det_ignore    u8 [num_dets]: the base's ignore flag (a detection matched to a crowd).
+ *   gt_category   int32 [num_gts]; gt_crowd u8 [num_gts].
+ *   fg_threshold, bg_threshold   t_f and t_b.
+ *   err_type      OUT u8 [num_dets]: 0 none (matched or ignored), 1 Cls, 2 Loc, 3 Both, 4 Dupe, 5 Bkg.
+ *   err_gt        OUT int32 [num_dets]: the chunk-global row of the target (Cls, Loc, Dupe) or -1.
+ *   gt_missed     OUT u8 [num_gts]: 1 for Miss.
+ *   Every row an image of the table covers is written.  One wave per detection: lanes stride over the image's ground
+ *   truths 64 apart and keep an (IoU, row) maximum for "same" and for "other", two lexicographic butterfly maxima over the
+ *   64 lanes follow, lane 0 classifies and stores; a second kernel with one lane per ground truth derives gt_missed from
+ *   the finished per-detection arrays.  No atomics, no LDS, no dependence on scheduling: the same bytes on every call.
+ *   num_images == 0, or num_dets == 0 and num_gts == 0: OVIS_OK without a launch.  A negative count, or a NULL pointer to
+ *   an array whose count is not 0 (images with num_images > 0): OVIS_EINVAL.  More than 2^31 - 1 rows: OVIS_ERANGE.
+ *   Python: `_C.error_types(iou, images, det_category, det_match, det_ignore, gt_category, gt_crowd, fg_threshold=0.5,
+ *   bg_threshold=0.1) -> (err_type, err_gt, gt_missed)` with `images` a `CocoProblems`. */
+int ovis_error_types(const double* iou, const int64_t* images, int num_images, long max_dets, long max_gts,
+                     const int32_t* det_category, const int32_t* det_match, const uint8_t* det_ignore,
+                     const int32_t* gt_category, const uint8_t* gt_crowd, double fg_threshold, double bg_threshold,
+                     long num_dets, long num_gts, uint8_t* err_type, int32_t* err_gt, uint8_t* gt_missed, void* stream);
+
 /* ovis_coco_rle_* / ovis_coco_runs_to_words (csrc/coco_rle_decode.hip): COCO run-length encodings -- the `segmentation` of a
  * results file (what mb/data/datasets/evaluation/coco/coco_eval.py:139-144 writes and COCOeval reads back through
  * pycocotools' rleFrString / rleDecode) or of an RLE annotation -- as the bit words of ovis_coco_pack_masks_u64, for `num`

@@ -1,7 +1,7 @@
 """Time of COCO scoring (engine/coco_eval.py) for one chunk of synthetic images, split by stage:
 
     python tools/bench_coco_eval.py [--images 32] [--height 480] [--width 640] [--detections 100] [--ground-truths 20]
-        [--boundary] [--repeats 1] [--lvis]
+        [--boundary] [--repeats 1] [--lvis] [--errors]
 
 Seeded, no model: every image gets ``--detections`` random boxes with 28 x 28 mask maps over 10 categories and
 ``--ground-truths`` random hexagons.  The whole set is scored as ONE chunk, once to warm up (code objects, allocator) and
@@ -18,6 +18,13 @@ chunk's own problem table: ``_C.lvis_match`` against ``_C.coco_match`` with all-
 identical, which is asserted -- and both again on the sub-table of the problems WITHOUT ground truth, where ``lvis_match``
 reads no IoU and shuffles nothing.  ``--repeats`` runs of 50 launches each of the C entries into outputs allocated once, device events around the 50; one JSON line
 (``"match"``) with every run's time per launch in microseconds.
+
+``--errors`` (not with ``--lvis``) times bbox and segm a second time with the error analysis (engine/error_analysis.py) in the
+same alternation: those lines say ``"errors": true``, carry two more stages -- ``image_iou``, the IoU of every detection of an
+image against every ground truth of it, and ``error_types``, the typing and missed-ground-truth kernels with the few tensor ops
+that hand them the base matching -- and ``host_analysis_ms``, the fixes and their AP50s on the host.  What the analysis costs
+is such a line minus the line without it.  A last line, ``"error_types"``, times the C entry alone -- its two kernels into
+outputs allocated once, 50 calls per run -- on the inputs of the bbox pass.
 """
 import argparse
 import json
@@ -34,7 +41,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from cvpr22_cross_modal_pseudo_labeling_amd.data.datasets import COCODataset  # noqa: E402
-from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, error_analysis  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import BoxList  # noqa: E402
 
 CATEGORIES = 10
@@ -175,6 +182,54 @@ def time_matching(dataset, predictions, device, budget, repeats, launches=50):
             "launches_per_run": launches, "us": times, "identical_tables": True}
 
 
+def time_typing(dataset, predictions, device, budget, repeats, launches=50):
+    """``ovis_error_types`` alone on the inputs the chunk's bbox pass hands it: the C entry (its two kernels) into outputs
+    allocated once, ``repeats`` runs of ``launches`` calls, device events around them -> the ``"error_types"`` line, per call in
+    microseconds.  The ``error_types`` STAGE of the lines above also holds the tensor ops that make the entry's inputs."""
+    from cvpr22_cross_modal_pseudo_labeling_amd import _C
+
+    seen = {}
+    real = _C.error_types
+
+    def capture(*args):
+        seen["args"] = args
+        return real(*args)
+    _C.error_types = capture
+    try:
+        coco_eval.match_tables(dataset, predictions, "bbox", device, budget,
+                               error_thresholds=(error_analysis.FG_THRESHOLD, error_analysis.BG_THRESHOLD))
+    finally:
+        _C.error_types = real
+    iou, images, det_cat, det_match, det_ignore, gt_cat, crowd, t_f, t_b = seen["args"]
+    det_match, det_ignore = det_match.contiguous(), det_ignore.contiguous()
+    d, g = det_cat.numel(), gt_cat.numel()
+    err_type = torch.empty(d, dtype=torch.uint8, device=device)
+    err_gt = torch.empty(d, dtype=torch.int32, device=device)
+    gt_missed = torch.empty(g, dtype=torch.uint8, device=device)
+
+    def call():
+        rc = _C._L.ovis_error_types(iou.data_ptr(), images.dev.data_ptr(), len(images), int(images.host[:, 1].max()), images.max_gts,
+                                    det_cat.data_ptr(), det_match.data_ptr(), det_ignore.data_ptr(), gt_cat.data_ptr(),
+                                    crowd.data_ptr(), t_f, t_b, d, g, err_type.data_ptr(), err_gt.data_ptr(), gt_missed.data_ptr(),
+                                    _C._stream())
+        assert rc == 0, rc
+    times = []
+    for _ in range(repeats):
+        call()
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        start.record()
+        for _ in range(launches):
+            call()
+        end.record()
+        torch.cuda.synchronize()
+        times.append(round(start.elapsed_time(end) / launches * 1e3, 2))
+    for a, b in zip(real(*seen["args"]), (err_type, err_gt, gt_missed)):
+        assert torch.equal(a, b), "the timed entry and _C.error_types differ"
+    return {"error_types": "per call (two kernels) in us", "images": len(images), "detections": d, "ground_truths": g,
+            "pairs": int(iou.numel()), "launches_per_run": launches, "us": times}
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     parser.add_argument("--images", type=int, default=32)
@@ -187,7 +242,12 @@ def main():
     parser.add_argument("--lvis", action="store_true",
                         help="an LVIS-shaped chunk (300 detections per image over 150 of 1203 categories, 12 ground truths, 20 "
                              "negatives) under rules='lvis', and lvis_match against coco_match on its problem table")
+    parser.add_argument("--errors", action="store_true",
+                        help="also time bbox and segm with the error analysis: stages image_iou and error_types, and the "
+                             "host's fixes")
     args = parser.parse_args()
+    if args.errors and args.lvis:
+        parser.error("--errors follows COCO's rules: it does not go with --lvis")
     device = torch.device("cuda", torch.cuda.current_device())
     with tempfile.TemporaryDirectory() as folder:
         if args.lvis:
@@ -197,15 +257,18 @@ def main():
     rules = {"rules": "lvis"} if args.lvis else {}
     frequencies = coco_eval.category_frequencies(dataset) if args.lvis else None
     budget = 1 << 62   # one chunk
-    passes = ["bbox", "segm"] + ([("segm", "boundary")] if args.boundary else [])
-    for iou_type in passes:
-        coco_eval.match_tables(dataset, predictions, iou_type, device, budget, **rules)   # warm-up
+    passes = [("bbox", {}), ("segm", {})] + ([(("segm", "boundary"), {})] if args.boundary else [])
+    if args.errors:
+        thresholds = {"error_thresholds": (error_analysis.FG_THRESHOLD, error_analysis.BG_THRESHOLD)}
+        passes += [("bbox", thresholds), ("segm", thresholds)]
+    for iou_type, errors in passes:
+        coco_eval.match_tables(dataset, predictions, iou_type, device, budget, **rules, **errors)   # warm-up
     for _ in range(args.repeats):   # the passes alternate, so a drift of the machine meets all of them
-        for iou_type in passes:
+        for iou_type, errors in passes:
             torch.cuda.synchronize()
             timer = {}
             t0 = time.perf_counter()
-            tables, cat_ids = coco_eval.match_tables(dataset, predictions, iou_type, device, budget, timer, **rules)
+            tables, cat_ids = coco_eval.match_tables(dataset, predictions, iou_type, device, budget, timer, **rules, **errors)
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             tables = {iou_type: tables} if isinstance(iou_type, str) else tables
@@ -223,7 +286,13 @@ def main():
                     "problems": len(first["category"]), "device_ms": stages, "device_ms_total": round(sum(stages.values()), 3),
                     "chunk_wall_ms": round((t1 - t0) * 1e3, 2), "host_accumulate_ms": round((t2 - t1) * 1e3, 2)}
             line.update({"AP" if isinstance(iou_type, str) else f"AP_{name}": r["AP"] for name, r in results.items()})
+            if errors:
+                analysis = error_analysis.analyze_tables(tables[iou_type], len(cat_ids), {})
+                line.update(errors=True, host_analysis_ms=round((time.perf_counter() - t2) * 1e3, 2), counts=analysis["counts"]["all"],
+                            dAP50={k[6:]: round(v, 4) for k, v in analysis.items() if k.startswith("dAP50_")})
             print(json.dumps(line), flush=True)
+    if args.errors:
+        print(json.dumps(time_typing(dataset, predictions, device, budget, max(args.repeats, 1))), flush=True)
     if args.lvis:
         print(json.dumps(time_matching(dataset, predictions, device, budget, max(args.repeats, 1))), flush=True)
 

@@ -23,7 +23,13 @@ CVPR 2021; engine/coco_eval.py), segm's keys from a matching on min(mask IoU, bo
 ``neg_category_ids``, ``not_exhaustive_category_ids`` and ``frequency``; AP ... APl, APr, APc, APf, 300 detections per image
 (engine/coco_eval.py ``rules="lvis"``; the rules are restated in include/ovis_hip.h and have not been compared with
 lvis-api's output) -- and writes ``lvis_results.json`` in place of ``coco_results.json``; it combines with ``--boundary-ap``
-and ``--recall``, whose ``box_proposal`` task keeps its own rules.  ``--rpn-recall``
+and ``--recall``, whose ``box_proposal`` task keeps its own rules.  ``--error-analysis`` (with ``--evaluate``, not with ``--lvis``)
+says WHY an AP50 is low: every false positive of the matching at IoU 0.5 is typed Cls, Loc, Both, Dupe or Bkg on the device
+and every ground truth nobody found or aimed at is Miss (engine/error_analysis.py, csrc/error_types.hip; TIDE's decomposition
+as include/ovis_hip.h restates it, not compared with tidecv's output); ``dAP50_<type>`` -- what AP50 would gain with that type
+fixed, overall and per split -- goes to the log as ``errors_bbox`` / ``errors_segm`` tables and, with the error counts and the
+split-by-split class confusion, to ``error_analysis.json``; ``coco_results.json`` is byte for byte what it is without the
+flag, and a ``boundary`` task is scored as before and not analysed.  ``--rpn-recall``
 is a run of its own: backbone + RPN alone (``model.propose``), the proposals gathered like detections into
 ``<OUTPUT_DIR>/inference/<name>/proposals.pth`` and scored by ``objectness`` as an ``rpn_proposal`` task, written to
 ``rpn_recall.json`` -- whether the RPN proposes the unseen classes at all.  ``--export-results`` (rank 0, after the gather, independent of ``--evaluate``) writes the detections as COCO results
@@ -92,6 +98,10 @@ def main(argv=None):
                         help="with --evaluate: score under LVIS-style federated rules (neg_category_ids, "
                              "not_exhaustive_category_ids, frequency: AP ... APl, APr, APc, APf; 300 detections per image) and "
                              "write lvis_results.json in place of coco_results.json; box_proposal keeps its own rules")
+    parser.add_argument("--error-analysis", action="store_true",
+                        help="with --evaluate (not with --lvis): break AP50 down by error type from the same scoring pass -- "
+                             "Cls, Loc, Both, Dupe, Bkg, Miss and the AP50 each would give back, per seen / unseen split -- as "
+                             "errors_bbox / errors_segm tables in the log and OUTPUT_DIR/inference/<name>/error_analysis.json")
     parser.add_argument("--rpn-recall", action="store_true",
                         help="run backbone + RPN alone over every test set, save the proposals as "
                              "OUTPUT_DIR/inference/<name>/proposals.pth and score their recall by objectness on the device: an "
@@ -122,6 +132,11 @@ def main(argv=None):
         parser.error("--recall adds the recall numbers to what --evaluate scores: give --evaluate too")
     if args.lvis and not args.evaluate:
         parser.error("--lvis changes the rules of what --evaluate scores: it is valid only with --evaluate")
+    if args.error_analysis and not args.evaluate:
+        parser.error("--error-analysis analyses what --evaluate scores: it is valid only with --evaluate")
+    if args.error_analysis and args.lvis:
+        parser.error("--error-analysis follows COCO's rules: it does not go with --lvis (under federated annotation an "
+                     "unannotated object makes the background error meaningless)")
     if args.boundary_ap and not args.evaluate:
         parser.error("--boundary-ap adds the boundary task to what --evaluate scores: give --evaluate too")
     if args.boundary_ap and not cfg.MODEL.MASK_ON:
@@ -175,7 +190,8 @@ def main(argv=None):
     else:
         for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
                                         args.evaluate, args.export_results, args.recall, args.bbox_vote,
-                                        args.mask_aug, args.boundary_ap, args.lvis).items():
+                                        args.mask_aug, args.boundary_ap, args.lvis,
+                                        **({"error_analysis": True} if args.error_analysis else {})).items():
             if preds is not None:
                 logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:

@@ -15,7 +15,10 @@ behind ``segm``: Boundary AP (Cheng et al., CVPR 2021) of the same ``segm.json``
 boundary IoU), the rule as include/ovis_hip.h states it (not compared with boundary-iou-api's output); the masks are decoded
 once for both.  ``--lvis`` scores every task under LVIS-style federated rules instead -- AP ... APl, APr, APc, APf, with
 ``--recall`` AR@300 ...; the annotation file must carry ``neg_category_ids``, ``not_exhaustive_category_ids`` and ``frequency``
-(the ten rules of include/ovis_hip.h; not compared with lvis-api's output).  There is no host-only scoring: the device must be a HIP device.
+(the ten rules of include/ovis_hip.h; not compared with lvis-api's output).  ``--error-analysis`` (not with ``--lvis``) breaks AP50
+down by error type from the same scoring pass (engine/error_analysis.py: Cls, Loc, Both, Dupe, Bkg, Miss and the AP50 each
+would give back, per split; the rules of include/ovis_hip.h, not compared with tidecv's output): ``errors_bbox`` /
+``errors_segm`` tables behind the others and, with the counts, under those names in ``--output``.  There is no host-only scoring: the device must be a HIP device.
 """
 import argparse
 import json
@@ -47,6 +50,9 @@ def main(argv=None):
                         help="LVIS-style federated rules: the annotation file's neg_category_ids / "
                              "not_exhaustive_category_ids / frequency decide what is judged; 300 detections per image; adds "
                              "APr / APc / APf (with --recall: AR@300, ARs@300, ARm@300, ARl@300)")
+    parser.add_argument("--error-analysis", action="store_true",
+                        help="break AP50 down by error type (Cls, Loc, Both, Dupe, Bkg, Miss; dAP50 per type and split): "
+                             "errors_bbox / errors_segm tasks behind the others, in --output too; not with --lvis")
     parser.add_argument("--device", default="cuda", help="the HIP device that scores (cuda, cuda:1, ...)")
     args = parser.parse_args(argv)
     files = {}
@@ -58,6 +64,9 @@ def main(argv=None):
             files[iou_type] = path
     if not files:
         parser.error("no results file: give --bbox, --segm or a --results-dir that holds bbox.json or segm.json")
+    if args.error_analysis and args.lvis:
+        parser.error("--error-analysis follows COCO's rules: it does not go with --lvis (under federated annotation an "
+                     "unannotated object makes the background error meaningless)")
     if args.boundary_ap and "segm" not in files:
         parser.error("--boundary-ap scores the masks of a segm results file: give --segm or a --results-dir that holds "
                      "segm.json")
@@ -72,13 +81,20 @@ def main(argv=None):
         parser.error("results are scored on the HIP device (mask decoding, IoU and matching have no host implementation): "
                      "--device cuda on a machine that has one")
 
-    from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval
+    from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, error_analysis
 
     dataset = coco_eval.annotation_dataset(args.ann_file)
     iou_types = IOU_TYPES + (("boundary",) if args.boundary_ap else ())
-    results = coco_eval.evaluate_coco_results(dataset, files, iou_types, device, recall=args.recall,
-                                              **({"rules": "lvis"} if args.lvis else {}))
+    scored = {}
+    extra = {"rules": "lvis"} if args.lvis else {}
+    if args.error_analysis:
+        extra = {"error_thresholds": (error_analysis.FG_THRESHOLD, error_analysis.BG_THRESHOLD), "tables_out": scored}
+    results = coco_eval.evaluate_coco_results(dataset, files, iou_types, device, recall=args.recall, **extra)
     print(coco_eval.format_results(results))
+    if args.error_analysis:
+        analysis = error_analysis.analyze_scored(dataset, scored, scored["cat_ids"])
+        print(coco_eval.format_results(error_analysis.task_tables(analysis)))
+        results.update((f"errors_{t}", numbers) for t, numbers in analysis.items())
     if args.output:
         with open(args.output, "w") as f:
             json.dump(results, f, indent=1)
