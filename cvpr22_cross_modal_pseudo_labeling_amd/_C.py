@@ -549,6 +549,56 @@ def vote_boxes(cand_boxes, cand_scores, offsets, cand_group, kept, vote_thresh):
     return out
 
 
+SOFT_NMS_METHODS = {"linear": _lib.OVIS_SOFT_NMS_LINEAR, "gaussian": _lib.OVIS_SOFT_NMS_GAUSSIAN,
+                    "hard": _lib.OVIS_SOFT_NMS_HARD}
+
+
+def soft_nms(cand_boxes, cand_scores, offsets, method="linear", nms_thresh=0.5, sigma=0.5, min_score=0.0):
+    """Soft-NMS (Bodla et al., ICCV 2017; not in the reference) over the runs of a candidate list, ``ovis_soft_nms_f32``:
+    cand_boxes [K, 4] / cand_scores [K] float32 and offsets [G + 1] int32 as ``merge_view_detections`` returns them (run g =
+    candidates offsets[g] .. offsets[g + 1], back to back from 0 to K) -> soft_scores [K] float32.  Per run, while a candidate
+    is alive the one with the largest working score (ties: the lower index) is selected with that score, and every other
+    alive candidate's score is multiplied by a weight of its IoU with it (the NMS's float32 IoU): ``linear`` 1 - IoU above
+    ``nms_thresh``, ``gaussian`` exp(-IoU^2 / sigma) (a float64 exponential rounded once), ``hard`` 0 above ``nms_thresh``; a
+    score that falls below ``min_score`` (strictly; or to exactly 0) discards its candidate.  soft_scores[k] = the final score
+    of a selected candidate (> 0), 0 for a discarded one; ``hard`` with min_score 0 keeps what ``nms`` keeps.  The rule in
+    full: include/ovis_hip.h.  One launch whatever the run lengths, the same bits on every call; malformed offsets raise
+    (the kernel reads nothing through them; the status costs ONE host read).  K == 0: an empty result, nothing launched.
+    Host tensors: ``libovis_cpu.so``, the same operations, the same bits."""
+    tensors = (cand_boxes, cand_scores, offsets)
+    if len({t.is_cuda for t in tensors}) != 1:
+        raise RuntimeError("soft_nms: host and device tensors mixed in one call")
+    if method not in SOFT_NMS_METHODS:
+        raise ValueError(f"soft_nms: method must be one of {sorted(SOFT_NMS_METHODS)}, got {method!r}")
+    if not float(sigma) > 0.0 or not float(min_score) >= 0.0:
+        raise ValueError(f"soft_nms: sigma must be > 0 and min_score >= 0, got {sigma} and {min_score}")
+    k = cand_boxes.shape[0] if cand_boxes.dim() == 2 else -1
+    if (k < 0 or cand_boxes.shape[1] != 4 or tuple(cand_scores.shape) != (k,) or offsets.dim() != 1 or offsets.numel() < 1
+            or cand_boxes.dtype != torch.float32 or cand_scores.dtype != torch.float32 or offsets.dtype != torch.int32):
+        raise RuntimeError("soft_nms: expected float32 cand_boxes [K, 4] and cand_scores [K] and int32 offsets [G + 1]; got "
+                           f"{[(str(t.dtype), tuple(t.shape)) for t in tensors]}")
+    code = SOFT_NMS_METHODS[method]
+    if k and offsets.numel() == 1:
+        raise RuntimeError(f"soft_nms: {k} candidates and no run (offsets must end at the number of candidates)")
+    if not cand_boxes.is_cuda:
+        return _cpu.soft_nms(*(t.contiguous() for t in tensors), code, nms_thresh, sigma, min_score)
+    dev = cand_boxes.device
+    out = torch.empty((k,), dtype=torch.float32, device=dev)
+    if k == 0:
+        return out
+    cand_boxes = _dev(cand_boxes, "cand_boxes")
+    cand_scores, offsets = cand_scores.contiguous(), offsets.contiguous()
+    status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.check(_L.ovis_soft_nms_f32(cand_boxes.data_ptr(), cand_scores.data_ptr(), offsets.data_ptr(), k,
+                                        offsets.numel() - 1, code, float(nms_thresh), float(sigma), float(min_score),
+                                        out.data_ptr(), status.data_ptr(), _stream()), "soft_nms")
+    if int(status.item()):
+        raise RuntimeError("soft_nms: OVIS_ERANGE (malformed offsets: not 0 first, decreasing, negative, or not ending at the "
+                           "number of candidates)")
+    return out
+
+
 def average_view_masks(maps, flips):
     """The mean of the views' mask maps (``ovis_average_view_masks_f32``; not in the reference): maps [V, D, 1, M, M]
     float32, ``flips``: V booleans -> [D, 1, M, M] = (((m_0 + m_1) + m_2) + ...) / float(V) in float32, the columns of a

@@ -270,3 +270,17 @@ def average_view_masks(maps, flip_bits):
         _check(load().ovis_cpu_average_view_masks_f32(maps.data_ptr(), v, d, m, flip_bits, out.data_ptr()),
                "average_view_masks")
     return out
+
+
+# ---- Soft-NMS over the runs of a candidate list (not in the reference; Bodla et al., ICCV 2017: include/ovis_hip.h) ---------
+def soft_nms(cand_boxes, cand_scores, offsets, method, nms_thresh, sigma, min_score):
+    """[K] (``ovis_cpu_soft_nms_f32``); the operands as ``_C.soft_nms`` checked them, ``method`` an OVIS_SOFT_NMS_* value."""
+    k = cand_boxes.shape[0]
+    out = torch.empty((k,), dtype=torch.float32)
+    if k:
+        _check(load().ovis_cpu_soft_nms_f32(cand_boxes.data_ptr(), cand_scores.data_ptr(), offsets.data_ptr(), k,
+                                            offsets.numel() - 1, int(method), float(nms_thresh), float(sigma), float(min_score),
+                                            out.data_ptr()),
+               "soft_nms: malformed offsets (not 0 first, decreasing, negative, or not ending at the number of candidates)",
+               "OVIS_EINVAL (an unknown method, sigma <= 0 or min_score < 0)")
+    return out

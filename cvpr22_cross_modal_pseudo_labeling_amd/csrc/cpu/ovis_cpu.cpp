@@ -542,4 +542,70 @@ extern "C" int ovis_cpu_average_view_masks_f32(const float* maps, int num_views,
   return OVIS_CPU_OK;
 }
 
-extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 6 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets, input transform, prediction compositor, box voting and view-averaged masks; fp32, OpenMP)"; }
+// ---- Soft-NMS over the (image, class) runs of a candidate list (not in the reference; the rule: include/ovis_hip.h) ------------
+// Twin of csrc/soft_nms.hip as a plain loop: per round the alive candidate with the largest working score (ascending scan
+// and a strict >: the lower index wins a tie), then the decay of the others.  The same float32 operations on the same operands
+// (the IoU is nms.hip's expression, the Gaussian weight a float64 exponential rounded once), so the bits agree.
+constexpr int kSoftNmsLinear = 0, kSoftNmsGaussian = 1, kSoftNmsHard = 2;   // the values of OVIS_SOFT_NMS_* (include/ovis_hip.h)
+
+extern "C" int ovis_cpu_soft_nms_f32(const float* cand_boxes, const float* cand_scores, const int32_t* offsets,
+                                     long num_candidates, int num_groups, int method, float nms_thresh, float sigma,
+                                     float min_score, float* soft_scores) {
+  if (num_candidates < 0 || num_groups < 0) return OVIS_CPU_EINVAL;
+  if (method != kSoftNmsLinear && method != kSoftNmsGaussian && method != kSoftNmsHard)
+    return OVIS_CPU_EINVAL;
+  if (!(sigma > 0.f) || !(min_score >= 0.f)) return OVIS_CPU_EINVAL;
+  if (num_candidates == 0 || num_groups == 0) return OVIS_CPU_OK;
+  if (!cand_boxes || !cand_scores || !offsets || !soft_scores) return OVIS_CPU_EINVAL;
+  // the runs in front of the first pair that is not well-formed; every candidate behind them gets 0
+  int good = 0;
+  while (good < num_groups && (good == 0 ? offsets[0] == 0 : offsets[good] >= 0) && offsets[good] <= offsets[good + 1] &&
+         (long)offsets[good + 1] <= num_candidates)
+    ++good;
+  const long covered = good == 0 ? 0 : (long)offsets[good];
+  for (long k = covered; k < num_candidates; ++k) soft_scores[k] = 0.f;
+#pragma omp parallel for schedule(dynamic, 4)
+  for (int g = 0; g < good; ++g) {
+    const long lo = offsets[g];
+    const int n = offsets[g + 1] - offsets[g];
+    const float* boxes = cand_boxes + 4 * lo;
+    float* out = soft_scores + lo;
+    std::vector<float> w(cand_scores + lo, cand_scores + lo + n);
+    for (int k = 0; k < n; ++k)
+      if (!(w[k] > 0.f)) w[k] = out[k] = 0.f;   // w > 0 iff alive
+    for (;;) {
+      int m = -1;
+      float top = 0.f;
+      for (int k = 0; k < n; ++k)
+        if (w[k] > top) { top = w[k]; m = k; }
+      if (m < 0) break;
+      out[m] = top;
+      w[m] = 0.f;
+      const float* a = boxes + 4 * m;
+      const float area_a = (a[2] - a[0] + 1.f) * (a[3] - a[1] + 1.f);
+      for (int k = 0; k < n; ++k) {
+        if (!(w[k] > 0.f)) continue;
+        const float* b = boxes + 4 * k;
+        const float left = std::max(a[0], b[0]), right = std::min(a[2], b[2]);
+        const float up = std::max(a[1], b[1]), bottom = std::min(a[3], b[3]);
+        const float width = std::max(right - left + 1.f, 0.f), height = std::max(bottom - up + 1.f, 0.f);
+        const float inter = width * height;
+        const float area_b = (b[2] - b[0] + 1.f) * (b[3] - b[1] + 1.f);
+        const float ov = inter / (area_a + area_b - inter);
+        float weight = 1.f;
+        if (method == kSoftNmsGaussian) {
+          const float q = (ov * ov) / sigma;
+          weight = (float)std::exp(-(double)q);
+        } else if (ov > nms_thresh) {
+          weight = method == kSoftNmsLinear ? 1.f - ov : 0.f;
+        }
+        const float v = w[k] * weight;
+        if (v >= min_score && v > 0.f) w[k] = v;
+        else w[k] = out[k] = 0.f;
+      }
+    }
+  }
+  return (good < num_groups || covered != num_candidates) ? OVIS_CPU_ERANGE : OVIS_CPU_OK;
+}
+
+extern "C" const char* ovis_cpu_version(void) { return "ovis_cpu 7 (RoIAlign fwd/bwd, NMS, polygon masks and mask targets, input transform, prediction compositor, box voting and view-averaged masks, Soft-NMS; fp32, OpenMP)"; }

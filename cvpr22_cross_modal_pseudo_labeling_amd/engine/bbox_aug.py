@@ -18,6 +18,11 @@ class) run that overlap it by IoU >= vote_thresh (``_C.vote_boxes``); scores, la
 then the flip: the inverse order of the merge), the mask head runs per view and ``mask`` becomes the mean of the views'
 maps (``_C.average_view_masks``, mirrored views' columns reversed).  Only ``mask`` is averaged: every other field the mask
 head writes (the uncertainty maps) stays the first view's.
+
+A third option lives in the post-processor itself (``PostProcessor.soft_nms``, tools/infer_net.py --soft-nms): with it set,
+``filter_merged`` decays the merged candidates' scores with ``_C.soft_nms`` (one call over the whole list) where it runs the
+grouped NMS otherwise; the kept indices it hands to the vote are candidate indices either way, and the vote keeps weighing
+with the candidates' ORIGINAL scores.
 """
 import torch
 
@@ -59,6 +64,14 @@ def _unwrap(model):
 def model_cfg(model):
     """The configuration a detector's heads were built from (None for a module without such heads)."""
     return getattr(getattr(_unwrap(model), "roi_heads", None), "cfg", None)
+
+
+def evaluating_post_processor(model):
+    """The box post-processor that filters a detector's evaluation pass, single view or merged views: the student's when the
+    model has one (its ``soft_nms`` attribute is what tools/infer_net.py --soft-nms sets)."""
+    model = _unwrap(model)
+    heads = model.roi_heads_student if hasattr(model, "roi_heads_student") else model.roi_heads
+    return heads["box"].post_processor
 
 
 def check_options(cfg, vote_thresh=None, average_masks=False):

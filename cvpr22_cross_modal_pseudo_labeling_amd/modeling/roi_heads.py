@@ -20,6 +20,7 @@ images per process.
 """
 import bisect
 from collections import namedtuple
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -342,6 +343,14 @@ def _all_positive(p):
     return isinstance(p, SampledBoxList) and p.all_positive
 
 
+class SoftNMS(NamedTuple):
+    """What ``PostProcessor.soft_nms`` holds: ``_C.soft_nms``'s method ("linear", "gaussian" or "hard"), sigma (> 0) and
+    min_score (>= 0); the IoU threshold is the post-processor's own ``nms``."""
+    method: str = "linear"
+    sigma: float = 0.5
+    min_score: float = 0.0
+
+
 class PostProcessor(nn.Module):
     def __init__(self, cfg, is_teacher=False):
         super().__init__()
@@ -355,6 +364,30 @@ class PostProcessor(nn.Module):
         self.gt_box_eval = cfg.MODEL.GT_BOX_EVAL
         if self.gt_box_eval:
             self.score_thresh = self.nms = 1.0
+        # None: greedy per-class NMS, as the reference.  A ``SoftNMS`` record: ``filter_results`` / ``filter_merged`` decay the
+        # candidates' scores with ``_C.soft_nms`` instead (not in the reference; tools/infer_net.py --soft-nms sets it)
+        self.soft_nms = None
+
+    def _soft_scores(self, cand_boxes, cand_scores, offsets):
+        """``_C.soft_nms`` of a candidate list under the ``soft_nms`` record -> (indices of the candidates with a soft score
+        > 0, in candidate order; the soft scores [K])."""
+        if self.gt_box_eval:
+            raise ValueError("PostProcessor.soft_nms does not go with MODEL.GT_BOX_EVAL: every ground-truth box is kept by "
+                             "definition (no score cut, no suppression), so there is nothing to decay")
+        method, sigma, min_score = self.soft_nms
+        soft = _C.soft_nms(cand_boxes, cand_scores, offsets, method=method, nms_thresh=self.nms, sigma=sigma,
+                           min_score=min_score)
+        return torch.nonzero(soft > 0).squeeze(1), soft
+
+    def _soft_nms_boxlist(self, cls_boxes):
+        """``boxlist_nms``'s place in the per-class loops when ``soft_nms`` is set: the candidates of ONE class with a soft
+        score > 0, in their order, ``scores`` = the soft scores."""
+        n = len(cls_boxes)
+        keep, soft = self._soft_scores(cls_boxes.bbox, cls_boxes.get_field("scores"),
+                                       torch.tensor([0, n], dtype=torch.int32, device=cls_boxes.bbox.device))
+        cls_boxes = cls_boxes[keep]
+        cls_boxes.add_field("scores", soft[keep])
+        return cls_boxes
 
     def forward(self, x, boxes, unfiltered=False):
         """``unfiltered``: hand out every box of every class with its score ([n * C] rows), as the teacher's passes do --
@@ -401,7 +434,10 @@ class PostProcessor(nn.Module):
         pair of its candidates, so two half-size calls do half the work -- and never raises: a larger single run gets a
         slice of its own, up to ``max_candidates``.  Same detections either way.  Host tensors: the reference's per-class
         loop (``filter_results_per_class``) over the runs of the list.  ``return_kept``: -> (results, kept), ``kept[i]`` the
-        int64 indices into the candidate list of image i's detections, in their order (what ``_C.vote_boxes`` is given)."""
+        int64 indices into the candidate list of image i's detections, in their order (what ``_C.vote_boxes`` is given).
+        With ``soft_nms`` set, ONE ``_C.soft_nms`` over the whole list takes the NMS's place (no slices: they exist for the
+        pair test above): the candidates with a soft score > 0 are kept in candidate order, ``scores`` are the soft scores
+        and the cut ranks by them; ``kept`` are candidate indices as before."""
         cand_boxes, cand_scores, cand_group, offsets = merged
         c, b = int(num_classes), len(image_sizes)
         if offsets.numel() != b * c + 1:
@@ -410,7 +446,9 @@ class PostProcessor(nn.Module):
         k = cand_boxes.shape[0]
         if not cand_boxes.is_cuda:
             return self._filter_merged_per_class(merged, image_sizes, c, return_kept)
-        if k == 0:
+        if self.soft_nms is not None:   # one call over the whole list: the slices exist for the grouped NMS's K^2 pair test
+            keep, cand_scores = self._soft_scores(cand_boxes, cand_scores, offsets)
+        elif k == 0:
             keep = torch.zeros((0,), dtype=torch.int64, device=cand_boxes.device)
         elif k <= (limit if slice_candidates is None else min(limit, int(slice_candidates))):
             keep = _C.nms_grouped(cand_boxes, cand_scores, cand_group, self.nms)
@@ -465,7 +503,7 @@ class PostProcessor(nn.Module):
                 cls_boxes.add_field("scores", cand_scores[lo:hi])
                 if return_kept:
                     cls_boxes.add_field("candidate", torch.arange(lo, hi, dtype=torch.int64, device=cand_scores.device))
-                cls_boxes = boxlist_nms(cls_boxes, self.nms)
+                cls_boxes = boxlist_nms(cls_boxes, self.nms) if self.soft_nms is None else self._soft_nms_boxlist(cls_boxes)
                 cls_boxes.add_field("labels", torch.full((len(cls_boxes),), j, dtype=torch.int64, device=cand_scores.device))
                 result.append(cls_boxes)
             if not result:
@@ -491,7 +529,9 @@ class PostProcessor(nn.Module):
         """Score threshold -> per-class NMS -> keep the DETECTIONS_PER_IMG best.  On the device the per-class loop of the
         reference (one ``nonzero`` + one NMS + host syncs per class) is ONE grouped NMS over the candidates of every
         class (``_C.nms_grouped``: a box only suppresses boxes of its class); same detections in the same order
-        (class-major, proposal index ascending inside a class)."""
+        (class-major, proposal index ascending inside a class).  With ``soft_nms`` set, ``_C.soft_nms`` over the same list
+        (its per-class offsets counted on the device) takes the NMS's place: candidates with a soft score > 0, in the same
+        order, ``scores`` = the soft scores, which the cut then ranks by."""
         if not boxlist.bbox.is_cuda:
             return self.filter_results_per_class(boxlist, num_classes)
         boxes = boxlist.bbox.reshape(-1, num_classes, 4)
@@ -499,7 +539,14 @@ class PostProcessor(nn.Module):
         cls, row = (scores.t()[1:] > self.score_thresh).nonzero(as_tuple=True)  # class-major candidate order
         cls = cls + 1
         cand_boxes, cand_scores = boxes[row, cls], scores[row, cls]
-        keep = _C.nms_grouped(cand_boxes, cand_scores, cls, self.nms) if cls.numel() else cls
+        if self.soft_nms is not None:
+            # the runs of the class-major list: class j's candidates end at the running count of classes 1 .. j (class 0, the
+            # background, is an empty run); counted on the device, nothing is read back
+            offsets = torch.zeros((num_classes + 1,), dtype=torch.int32, device=scores.device)
+            offsets[2:] = torch.cumsum((scores.t()[1:] > self.score_thresh).sum(1), 0)
+            keep, cand_scores = self._soft_scores(cand_boxes, cand_scores, offsets)
+        else:
+            keep = _C.nms_grouped(cand_boxes, cand_scores, cls, self.nms) if cls.numel() else cls
         result = BoxList(cand_boxes[keep], boxlist.size)
         result.add_field("scores", cand_scores[keep])
         result.add_field("labels", cls[keep])
@@ -522,7 +569,7 @@ class PostProcessor(nn.Module):
                 continue
             cls_boxes = BoxList(boxes[inds, j * 4:(j + 1) * 4], boxlist.size)
             cls_boxes.add_field("scores", scores[inds, j])
-            cls_boxes = boxlist_nms(cls_boxes, self.nms)
+            cls_boxes = boxlist_nms(cls_boxes, self.nms) if self.soft_nms is None else self._soft_nms_boxlist(cls_boxes)
             cls_boxes.add_field("labels", torch.full((len(cls_boxes),), j, dtype=torch.int64, device=scores.device))
             result.append(cls_boxes)
         if not result:

@@ -82,6 +82,16 @@ int ovis_cpu_vote_boxes_f32(const float* cand_boxes, const float* cand_scores, c
 int ovis_cpu_average_view_masks_f32(const float* maps, int num_views, long num_maps, int resolution, uint64_t flip_bits,
                                     float* out);
 
+/* Soft-NMS on host tensors: twin of ovis_soft_nms_f32 (include/ovis_hip.h states the rule in full: same arguments, the same
+ * float32 operations on the same operands, the Gaussian weight a float64 exponential rounded once -- the same bits), as a
+ * plain loop: per round the alive candidate with the largest working score, ties to the lower index, then the decay of the
+ * others.  Not in the reference; Bodla et al., ICCV 2017.  `method` takes the values of OVIS_SOFT_NMS_* (0 linear, 1 gaussian,
+ * 2 hard).  Malformed offsets (offsets[0] != 0, a negative or decreasing entry, an entry above K, offsets[num_groups] != K):
+ * OVIS_CPU_ERANGE, the runs in front of the first such entry are processed and every candidate from there on gets 0.
+ * `cand_boxes` needs no alignment here. */
+int ovis_cpu_soft_nms_f32(const float* cand_boxes, const float* cand_scores, const int32_t* offsets, long num_candidates,
+                          int num_groups, int method, float nms_thresh, float sigma, float min_score, float* soft_scores);
+
 const char* ovis_cpu_version(void);
 
 #ifdef __cplusplus

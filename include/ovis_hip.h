@@ -269,6 +269,60 @@ int ovis_vote_boxes_f32(const float* cand_boxes, const float* cand_scores, const
 int ovis_average_view_masks_f32(const float* maps, int num_views, long num_maps, int resolution, uint64_t flip_bits,
                                 float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Soft-NMS over the candidate list (linear, Gaussian, hard)                             csrc/soft_nms.hip
+ *   Not in the reference (mb/modeling/roi_heads/box_head/inference.py:121-163 suppresses greedily); the rule is Bodla et al.,
+ *   "Soft-NMS -- Improving Object Detection With One Line of Code" (ICCV 2017) as Detectron's TEST.SOFT_NMS applies it.
+ *   Detectron's cython soft_nms is not a dependency, so the rule is restated here in full.
+ * cand_boxes [K, 4] (16-byte aligned, xyxy), cand_scores [K] and offsets [num_groups + 1] int32 are the outputs of the view
+ * merge above, exactly as ovis_vote_boxes_f32 takes them: run g = the candidates offsets[g] .. offsets[g + 1] of one (image,
+ * class), runs back to back, offsets[0] == 0 and offsets[num_groups] == K.  Every run is processed on its own:
+ *   1. working scores w_k = s_k; every candidate is alive.
+ *   2. while a candidate is alive: SELECT the alive m with the largest w; ties go to the LOWER candidate index.  m's final
+ *      score is w_m, and m leaves the alive set.
+ *   3. for every k still alive: ov = IoU(b_m, b_k), the float32 IoU of ovis_nms_f32 operand for operand (+1 area convention,
+ *      csrc/nms.hip::iou_xyxy, the function ovis_vote_boxes_f32 uses), so a pair is on the same side of a threshold for the
+ *      NMS, the vote and Soft-NMS.
+ *   4. weight:  OVIS_SOFT_NMS_LINEAR    ov > nms_thresh ? 1 - ov : 1
+ *               OVIS_SOFT_NMS_HARD      ov > nms_thresh ? 0 : 1
+ *               OVIS_SOFT_NMS_GAUSSIAN  (float) exp(-(double) q), q = (ov * ov) / sigma: product and division in float32, the
+ *               exponential in float64, rounded ONCE to float32.  (Two correct float64 exponentials agree after that rounding
+ *               unless the exact value lies within a float64 ulp of a float32 midpoint; float32 expf implementations differ
+ *               by an ulp routinely, and such a difference grows multiplicatively round after round.)
+ *   5. w_k = w_k * weight, one float32 multiplication.  If w_k < min_score (strictly), k is DISCARDED and leaves the alive set.
+ *   6. soft_scores[k] = the final score of a selected candidate, 0 for a discarded one.
+ * A selected candidate always has a positive score: a working score that is not > 0 -- a product that underflows to exactly 0
+ * under min_score == 0, a NaN (inf * 0), or an input score that is not > 0 to begin with -- counts as discarded.
+ * sigma > 0 and min_score >= 0 (otherwise OVIS_EINVAL); method other than the three: OVIS_EINVAL.  OVIS_SOFT_NMS_HARD with
+ * min_score == 0 is the greedy NMS of ovis_nms_f32 in `>` mode: soft_scores[k] = s_k for its survivors, 0 elsewhere.
+ * Detectron's defaults are method linear, sigma 0.5, nms_thresh = the NMS threshold and min_score 0.0001; the callers here
+ * pass MODEL.ROI_HEADS.SCORE_THRESH as min_score instead (README).
+ * One launch, no workspace, no atomics.  Lane l of the T lanes that share a run owns candidates l, l + T, ... of it: a round
+ * is one pass of every lane over its own candidates (decay, and the lane's next maximum on the way) and one reduction of the
+ * lanes' (score, index) pairs -- a fixed xor butterfly in a wavefront, whose compare is "larger score, then lower index" and
+ * therefore independent of the lane order, then one LDS slot per wavefront, double-buffered: one barrier per round.  Three
+ * forms of the SAME loop, the same bits from each:
+ *   run length <= OVIS_SOFT_NMS_WAVE_CANDIDATES          one wavefront per run, four runs per workgroup, no barrier; boxes and
+ *                                                        working scores in LDS
+ *   ... <= OVIS_SOFT_NMS_LDS_CANDIDATES                  one 256-lane workgroup per run, boxes and working scores in LDS
+ *   longer                                               the workgroup form over global memory: boxes from cand_boxes, the
+ *                                                        working scores in soft_scores (negated while alive)
+ * OVIS_SOFT_NMS_LDS_CANDIDATES: 20 bytes per candidate (box + working score) and the reduction slots within 40 KiB, a quarter
+ * of gfx950's 160 KiB of LDS per CU: four workgroups (16 wavefronts) stay resident per CU.
+ * Every load is bounded by offsets and K.  offsets[0] != 0, a negative or decreasing entry, an entry above K or
+ * offsets[num_groups] != K stores 1 to *status (device int32, zeroed by the caller): the runs in front of the first such
+ * entry are processed as usual, every candidate from there on gets 0, and no address is formed from a bad value.
+ * num_candidates == 0 or num_groups == 0: nothing is launched.
+ * ---------------------------------------------------------------------------------- */
+#define OVIS_SOFT_NMS_LINEAR 0
+#define OVIS_SOFT_NMS_GAUSSIAN 1
+#define OVIS_SOFT_NMS_HARD 2
+#define OVIS_SOFT_NMS_WAVE_CANDIDATES 256
+#define OVIS_SOFT_NMS_LDS_CANDIDATES 2032
+int ovis_soft_nms_f32(const float* cand_boxes, const float* cand_scores, const int32_t* offsets, long num_candidates,
+                      int num_groups, int method, float nms_thresh, float sigma, float min_score, float* soft_scores,
+                      int32_t* status, void* stream);
+
 /* Pooler.convert_to_roi_format (mb/modeling/poolers.py:73-86): boxes[i] (HOST array of device pointers) holds image i's
  * [boxes_per_image[i], 4] boxes (boxes_per_image: HOST array); rois [sum, 5] receives (id_i, x1, y1, x2, y2) rows in list
  * order, id_i = image_ids[i] (HOST array) or i when image_ids is NULL.  One launch per OVIS_BOX_DECODE_MAX_IMAGES images. */

@@ -40,7 +40,13 @@ OUTPUT_DIR, and MODEL.DEVICE cuda when MODEL.MASK_ON.  ``TEST.BBOX_AUG.ENABLED T
 views' detections; the saved BoxLists are in the first view's frame and keep their masks.  Two options of that mode, neither
 in the reference: ``--bbox-vote THR`` replaces every kept box by the score-weighted mean of the merged candidates of its class
 that overlap it by IoU >= THR (box voting), ``--mask-aug`` runs the mask head on every view and saves the mean of the views'
-maps instead of the first view's (engine/bbox_aug.py).  ``tools/test_net.py`` stays the
+maps instead of the first view's (engine/bbox_aug.py).  ``--soft-nms {linear,gaussian}`` (with or without
+TEST.BBOX_AUG.ENABLED; not in the reference either) replaces the greedy per-class NMS of the box post-processor by Soft-NMS
+(Bodla et al., ICCV 2017; ``_C.soft_nms``, the rule in include/ovis_hip.h): overlapped candidates lose score instead of being
+deleted, those that fall below ``--soft-nms-min-score`` (default MODEL.ROI_HEADS.SCORE_THRESH; Detectron: 0.0001) go, the saved
+``scores`` are the decayed ones and DETECTIONS_PER_IMG ranks by them; ``--soft-nms-sigma`` (default 0.5) is the Gaussian's
+width, the IoU threshold is MODEL.ROI_HEADS.NMS.  It composes with ``--bbox-vote`` (the vote weighs with the candidates'
+original scores) and ``--mask-aug``.  ``tools/test_net.py`` stays the
 synthetic-stream tool; LVIS scoring is outside this build.
 """
 import argparse
@@ -62,10 +68,12 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.catalog import DatasetCatalog  
 from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetcher  # noqa: E402,F401
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem_bn, make_batch, make_embeddings  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402,F401
+from cvpr22_cross_modal_pseudo_labeling_amd.engine.bbox_aug import evaluating_post_processor  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, coco_results, comm, inference, proposal_recall, visualize  # noqa: E402,F401
 from cvpr22_cross_modal_pseudo_labeling_amd.engine.evaluation import (run_datasets, run_rpn_recall, save_evaluation,  # noqa: E402,F401
                                                                        save_visualizations)
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.modeling.roi_heads import SoftNMS  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
 
@@ -113,6 +121,20 @@ def main(argv=None):
                         help="with TEST.BBOX_AUG.ENABLED True and MODEL.MASK_ON: the masks are the mean of every view's "
                              "mask-head pass instead of the first view's")
     parser.add_argument("opts", default=None, nargs=argparse.REMAINDER, help="KEY VALUE overrides")
+    # Soft-NMS's flags have a parser of their own, read first: the namespace of the parser above stays what it was
+    soft_parser = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    soft_parser.add_argument("--soft-nms", choices=("linear", "gaussian"), default=None,
+                             help="Soft-NMS (Bodla et al., ICCV 2017) in place of the greedy per-class NMS: overlapped "
+                                  "candidates lose score (linear: x (1 - IoU) above MODEL.ROI_HEADS.NMS; gaussian: x exp(-IoU^2 "
+                                  "/ sigma)) instead of being deleted; with or without TEST.BBOX_AUG.ENABLED")
+    soft_parser.add_argument("--soft-nms-sigma", type=float, default=None, metavar="S",
+                             help="with --soft-nms: the Gaussian's sigma, > 0 (default 0.5)")
+    soft_parser.add_argument("--soft-nms-min-score", type=float, default=None, metavar="V",
+                             help="with --soft-nms: a candidate whose decayed score falls below V >= 0 is dropped (default "
+                                  "MODEL.ROI_HEADS.SCORE_THRESH; Detectron uses 0.0001)")
+    parser.epilog = "Soft-NMS flags (in front of the KEY VALUE overrides, like every flag) -- " + "; ".join(
+        f"{a.option_strings[0]} {a.metavar or '{' + ','.join(a.choices) + '}'}: {a.help}" for a in soft_parser._actions)
+    soft, argv = soft_parser.parse_known_args(sys.argv[1:] if argv is None else argv)
     args = parser.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -155,6 +177,19 @@ def main(argv=None):
     if args.export_results and cfg.MODEL.MASK_ON and cfg.MODEL.DEVICE != "cuda":
         parser.error("--export-results encodes the masks of segm.json on the HIP device (the run-length encoder has no host "
                      "implementation): set MODEL.DEVICE cuda")
+    if soft.soft_nms is None and (soft.soft_nms_sigma is not None or soft.soft_nms_min_score is not None):
+        parser.error("--soft-nms-sigma / --soft-nms-min-score are parameters of Soft-NMS: they are valid only with --soft-nms")
+    if soft.soft_nms_sigma is not None and not soft.soft_nms_sigma > 0.0:
+        parser.error(f"--soft-nms-sigma takes a width > 0, got {soft.soft_nms_sigma}")
+    if soft.soft_nms_min_score is not None and not soft.soft_nms_min_score >= 0.0:
+        parser.error(f"--soft-nms-min-score takes a score >= 0, got {soft.soft_nms_min_score}")
+    if soft.soft_nms is not None and args.rpn_recall:
+        parser.error("--soft-nms acts on the detections' post-processing and --rpn-recall makes no detections: they do not go "
+                     "together")
+    if soft.soft_nms is not None and cfg.MODEL.DEVICE != "cuda":
+        parser.error("--soft-nms is an option of the HIP device's post-processing: set MODEL.DEVICE cuda")
+    if soft.soft_nms is not None and cfg.MODEL.GT_BOX_EVAL:
+        parser.error("--soft-nms does not go with MODEL.GT_BOX_EVAL True: every ground-truth box is kept by definition")
     if args.bbox_vote is not None and not cfg.TEST.BBOX_AUG.ENABLED:
         parser.error("--bbox-vote votes over the views of multi-scale / flip testing: set TEST.BBOX_AUG.ENABLED True")
     if args.mask_aug and not cfg.TEST.BBOX_AUG.ENABLED:
@@ -173,7 +208,7 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO if comm.get_rank() == 0 else logging.WARNING,
                         format="%(asctime)s %(name)s %(levelname)s: %(message)s")
     logger = logging.getLogger("ovis.inference")
-    logger.info("Using %d GPUs\n%s", world, args)
+    logger.info("Using %d GPUs\n%s %s", world, args, soft)
 
     catalog = DatasetCatalog(args.dataset_catalog, args.data_dir)
     model = build_detection_model(cfg).to(device)
@@ -185,6 +220,11 @@ def main(argv=None):
         calibrate_stem_bn(model, images)  # random init only: give the frozen BN usable statistics
     _, e_seen = make_embeddings(cfg.MODEL.ROI_BOX_HEAD.EMB_DIM, device=device)
     model.set_class_embeddings(e_seen)  # stands until a dataset brings its own (DATASETS.DATASET_ARGS.LOAD_EMBEDDINGS)
+    if soft.soft_nms is not None:
+        post = evaluating_post_processor(model)
+        post.soft_nms = SoftNMS(soft.soft_nms, 0.5 if soft.soft_nms_sigma is None else soft.soft_nms_sigma,
+                                post.score_thresh if soft.soft_nms_min_score is None else soft.soft_nms_min_score)
+        logger.info("Soft-NMS in place of the per-class NMS: %s, Nt %s", post.soft_nms, post.nms)
     if args.rpn_recall:
         run_rpn_recall(cfg, model, catalog, device, logger)
     else:
