@@ -121,7 +121,9 @@ def roi_align_forward_mfma(input, rois, spatial_scale, pooled_height, pooled_wid
     """Matrix-core forward (extension): separable weights as bf16 hi/lo MFMA operands, same values up to ~2^-15 of
     sum |w x|.  Round-1 timing: on par with the exact kernel (0.33-0.36 vs 0.31-0.32 ms on uniform RoIs, 0.44-0.45 vs
     0.46-0.52 ms on RPN-like ones at [2,1024,50,84], R=1024) -- both sit on the 0.8 MB/RoI output write.  Falls back to the exact kernel for maps below
-    16 x 16 or pooled sizes above 16 x 16."""
+    16 x 16 or pooled sizes above 16 x 16.  Finite maps only: a window is read in 16-cell block footprints whose cells outside
+    the window meet zero weights, so a NaN or an infinity anywhere in a block reaches the bins (0 * NaN); the exact kernel
+    reads only the cells its taps touch."""
     return _roi_align_forward(input, rois, spatial_scale, pooled_height, pooled_width, sampling_ratio, False)
 
 

@@ -1,4 +1,4 @@
-"""An independent fp64 reference of the RoIAlign backward, with elementwise error budgets (host only, NumPy).
+"""An independent fp64 reference of the RoIAlign backward and forward, with elementwise error budgets (host only, NumPy).
 
 The operation (the formulas ``csrc/roi_geom.h`` cites: ROIAlign_cuda.cu:16-62 the bilinear set-up, :86-113 the RoI
 geometry, :178-254 the backward): bin (i, j) of RoI r averages ``gh x gw`` bilinear samples at
@@ -46,6 +46,15 @@ The coordinate error d = ``K_ULPS`` float32 ulps of the largest intermediate M o
 6 half-ulps = ``K_ULPS = 3``.  Past the coordinate a kernel's weight arithmetic is exact or relative: l = v - lo is exact
 (Sterbenz), 1 - l and the sums over a bin's samples carry relative roundings of 2^-24 that the kernels' ``mag`` multiples
 absorb.
+
+The forward (``roi_align_forward_ref``) is the same operation read the other way: with the same float32 geometry and the
+same fp64 ``Ay`` / ``Ax``,  out[r, c, i, j] = Ay[i, :] . x[b, c] . Ax[j, :]^T / count.  Its ``Result`` fields are
+[R, C, th, tw]: ``mag`` the same sum with |x|, ``slack`` as above with |x| in place of |g|, ``terms`` the number of
+(sample pair, corner) taps of the bin whose weight is non-zero (the same for every channel).  A RoI with a foreign image
+id gives exact zeros with no bound, and so does a RoI with a non-finite coordinate: the project's rule (``make_geom``'s
+``empty``: a non-finite sample coordinate pools nothing).  ``make_geom`` reaches that verdict for a NaN or an infinity in
+x1 / y1 and for +Inf in x2 / y2; a NaN or -Inf in x2 / y2 alone is, in the kernels as in the reference operation, a RoI of
+size 1 (``fmaxf(NaN, 1) = 1``) -- the GPU case tables use only the former kind and check that on the host (``geom32``).
 """
 import collections
 
@@ -71,6 +80,16 @@ TOL_MFMA = 4e-5
 # weights (Ny roundings with the 1 - l), Ax[j] of Nx, the product, the multiplication, the division, nb - 1 additions over
 # the bins, one atomic per RoI: max(Ny + Nx) + nb + 2 + RoIs <= terms + 4 because sum Ny * Nx >= max(Ny + Nx) - 1 + nb - 1.
 ATOMIC_C = 4
+# Exact forward forms (``fwd_pool`` and its LDS / table / strided variants, roi_align.hip; the reference CPU kernel has the same
+# sequence).  Per tap w * v with w = hy * hx: l = v - lo is exact, 1 - ly and 1 - lx are one rounding each, their product
+# one (the worst of the four corner weights: 3), w * v one: 4 per tap.  The taps of a sample are added left to right and the
+# sample to the accumulator; a tap whose weight is zero contributes an exact zero whose addition is exact, so a bin of
+# ``terms`` non-zero taps sees at most terms - 1 rounded additions on any one path.  The division by ``count`` (or the exact
+# multiplication by 1 / count on power-of-two grids) is one more: 4 + (terms - 1) + 1 = terms + 4 relative roundings of
+# 2^-24 of the tap's |w v|, i.e. of ``mag``.  That is the first-order count k * u; the exact factor (1 + u)^k - 1 <=
+# k u / (1 - k u) exceeds it by about (k u)^2, less than one u while k^2 u <= 1 (k <= 4096; 16 x 16 samples of four taps and
+# the four above are 1028), which one further unit covers: terms + 5.
+FWD_C = 5
 U32 = 2.0 ** -24
 
 Result = collections.namedtuple("Result", "ref mag slack terms clearance")
@@ -164,10 +183,42 @@ def clearance_of(rois, scale, ph, pw, n, h, w, sampling_ratio):
     """``clearance`` alone (every bin, so it covers any ``bin_stride``)."""
     clear = np.inf
     for roi in np.asarray(rois, dtype=_f).reshape(-1, 5):
+        if not np.all(np.isfinite(roi)):
+            continue
         b, ((sy, by, gy), (sx, bx, gx)) = _geometry(roi, scale, ph, pw, sampling_ratio)
         if 0 <= b < n:
             clear = min(clear, _axis(sy, by, gy, range(ph), h)[3], _axis(sx, bx, gx, range(pw), w)[3])
     return clear
+
+
+def _pool(X, Ly, Lx):
+    """sum_yx Ly[i, y] X[c, y, x] Lx[j, x]"""
+    return (Ly @ X) @ Lx.T
+
+
+def roi_align_forward_ref(x, rois, scale, ph, pw, sampling_ratio, bin_stride=1):
+    x = np.asarray(x, dtype=np.float64)
+    rois = np.asarray(rois, dtype=_f).reshape(-1, 5)
+    n, c, h, w = x.shape
+    th, tw = -(-ph // bin_stride), -(-pw // bin_stride)
+    ref, mag, slack, terms = (np.zeros((rois.shape[0], c, th, tw)) for _ in range(4))
+    clearance = np.inf
+    for r in range(rois.shape[0]):
+        if not np.all(np.isfinite(rois[r])):
+            continue
+        b, ((sy, by, gy), (sx, bx, gx)) = _geometry(rois[r], scale, ph, pw, sampling_ratio)
+        if b < 0 or b >= n:
+            continue
+        Ay, Dy, Ny, cy = _axis(sy, by, gy, [bin_stride * i for i in range(th)], h)
+        Ax, Dx, Nx, cx = _axis(sx, bx, gx, [bin_stride * j for j in range(tw)], w)
+        clearance = min(clearance, cy, cx)
+        count = float(gy * gx)
+        X = np.abs(x[b])
+        ref[r] = _pool(x[b], Ay, Ax) / count
+        mag[r] = _pool(X, Ay, Ax) / count
+        slack[r] = _pool(X, Ay + Dy, Ax + Dx) / count - mag[r]
+        terms[r] = np.outer(Ny.sum(1), Nx.sum(1))[None]
+    return Result(ref, mag, np.maximum(slack, 0.0), np.rint(terms).astype(np.int64), clearance)
 
 
 def _bf16(v):
@@ -202,12 +253,45 @@ def split_form_emulation(grad, rois, scale, ph, pw, n, c, h, w, sampling_ratio, 
     return out
 
 
+def split_form_emulation_forward(x, rois, scale, ph, pw, sampling_ratio, bin_stride=1):
+    """The forward's matrix-core algorithm (roi_align_fwd_mfma.hip): V = (Ay / count) . x[b, c] with both operands as bf16
+    hi + lo and three of the hi/lo terms, V rounded to float32 and re-split, out = V . Ax^T the same way -- on this module's
+    weights rounded to float32, sums in fp64."""
+    x = np.asarray(x, dtype=_f)
+    rois = np.asarray(rois, dtype=_f).reshape(-1, 5)
+    n, c, h, w = x.shape
+    th, tw = -(-ph // bin_stride), -(-pw // bin_stride)
+    out = np.zeros((rois.shape[0], c, th, tw))
+    for r in range(rois.shape[0]):
+        if not np.all(np.isfinite(rois[r])):
+            continue
+        b, ((sy, by, gy), (sx, bx, gx)) = _geometry(rois[r], scale, ph, pw, sampling_ratio)
+        if b < 0 or b >= n:
+            continue
+        Ay = _axis(sy, by, gy, [bin_stride * i for i in range(th)], h)[0].astype(_f) / _f(gy * gx)
+        Ax = _axis(sx, bx, gx, [bin_stride * j for j in range(tw)], w)[0].astype(_f)
+        (f_hi, f_lo), (x_hi, x_lo), (y_hi, y_lo) = _split(x[b]), _split(Ax), _split(Ay)
+        V = y_hi @ f_hi + y_hi @ f_lo + y_lo @ f_hi
+        v_hi, v_lo = _split(V.astype(_f))
+        out[r] = v_hi @ x_hi.T + v_hi @ x_lo.T + v_lo @ x_hi.T
+    return out
+
+
 def mfma_bound(res):
+    return TOL_MFMA * res.mag + res.slack
+
+
+def mfma_forward_bound(res):
+    """The forward chains two split products with a re-split in between, as the backward does: the same constant."""
     return TOL_MFMA * res.mag + res.slack
 
 
 def f32_bound(res):
     return (res.terms + ATOMIC_C) * U32 * res.mag + res.slack
+
+
+def f32_forward_bound(res):
+    return (res.terms + FWD_C) * U32 * res.mag + res.slack
 
 
 def worst_ratio(got, res, bound):
@@ -218,6 +302,151 @@ def worst_ratio(got, res, bound):
     if np.any(err[free] != 0.0):
         return np.inf
     return float((err[~free] / bound[~free]).max()) if np.any(~free) else 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The float32 twin of ``make_geom`` (csrc/roi_geom.h) and of the forward kernels' dispatch decisions: which form a RoI
+# reaches is computed on the host, so that a case table can be held to what it claims to cover without a GPU.
+# ---------------------------------------------------------------------------------------------------------------------
+Geom32 = collections.namedtuple("Geom32", "b gh gw pow2 window start bin")
+
+
+def _coord32(start, p, bin_, i, g):
+    """``sample_coord``: start + p * bin + (i + .5) * bin / g, every operation in float32"""
+    return _f(_f(start + _f(_f(p) * bin_)) + _f(_f(_f(i) + _f(0.5)) * bin_) / _f(g))
+
+
+def _low32(v, size):
+    return 0 if v <= 0 else min(int(v), size - 1)
+
+
+def geom32(roi, scale, n_img, h, w, ph, pw, sampling_ratio):
+    """``make_geom`` in float32: grids, the power-of-two flag, (start, bin) per axis (y first) and the inclusive window
+    (wy0, wy1, wx0, wx1) -- None when the RoI is ``empty`` (foreign image id, non-finite sample coordinates, every sample
+    outside the map)."""
+    roi = np.asarray(roi, dtype=_f)
+    sc = _f(scale)
+    grids, spans, starts, bins = [], [], [], []
+    with np.errstate(all="ignore"):
+        for lo, hi, p, size in ((roi[2], roi[4], ph, h), (roi[1], roi[3], pw, w)):
+            start = _f(lo * sc)
+            side = _f(_f(hi * sc) - start)
+            side = side if side > 1 else _f(1)      # fmaxf: a NaN gives 1
+            bin_ = _f(side / _f(p))
+            starts.append(start)
+            bins.append(bin_)
+            if sampling_ratio <= 0 and not np.isfinite(bin_):
+                grids.append(0)                      # (int)ceilf of a non-finite value: the coordinates below are not finite either
+                spans.append(None)
+                continue
+            grid = sampling_ratio if sampling_ratio > 0 else int(np.ceil(bin_))
+            grids.append(grid)
+            first, last = _coord32(start, 0, bin_, 0, grid), _coord32(start, p - 1, bin_, grid - 1, grid)
+            if not (np.isfinite(first) and np.isfinite(last)) or last < -1 or first > size:
+                spans.append(None)
+            else:
+                spans.append((_low32(max(first, _f(-1)), size), min(_low32(min(last, _f(size)), size) + 1, size - 1)))
+    gh, gw = grids
+    pow2 = gh > 0 and gw > 0 and gh & (gh - 1) == 0 and gw & (gw - 1) == 0 and gh <= 1024 and gw <= 1024
+    b = int(roi[0]) if np.isfinite(roi[0]) else -1
+    ok = 0 <= b < n_img and spans[0] is not None and spans[1] is not None
+    return Geom32(b, gh, gw, pow2, spans[0] + spans[1] if ok else None, tuple(starts), tuple(bins))
+
+
+def roi_window(roi, scale, n_img, h, w, ph, pw, sampling_ratio):
+    """(wy0, wy1, wx0, wx1) of a RoI's feature-map window, or None for an empty RoI"""
+    return geom32(roi, scale, n_img, h, w, ph, pw, sampling_ratio).window
+
+
+def _window_cells(rois, scale, n_img, h, w, p, sampling_ratio):
+    """Cells of each RoI's feature-map window (0: no sample inside the map) -- the host twin of ``make_geom`` in
+    csrc/roi_geom.h, in float32 like the kernel.  ``p``: the pooler, one number or (ph, pw)."""
+    ph, pw = (p, p) if np.isscalar(p) else p
+    cells = []
+    for roi in np.asarray(rois, dtype=_f).reshape(-1, 5):
+        win = roi_window(roi, scale, n_img, h, w, ph, pw, sampling_ratio)
+        cells.append(0 if win is None else (win[1] - win[0] + 1) * (win[3] - win[2] + 1))
+    return np.array(cells)
+
+
+def block_shape(window):
+    """(nyb, nxb): the 16-cell blocks the matrix-core forward cuts a window into"""
+    wy0, wy1, wx0, wx1 = window
+    return (wy1 - wy0 + 16) // 16, (wx1 - wx0 + 16) // 16
+
+
+def max_grid(rois, scale, ph, pw, sampling_ratio):
+    """The largest sampling grid per axis over the RoIs with finite coordinates (the kernels loop over it)."""
+    worst = 0
+    for roi in np.asarray(rois, dtype=_f).reshape(-1, 5):
+        if np.all(np.isfinite(roi)):
+            _, ((_, _, gy), (_, _, gx)) = _geometry(roi, scale, ph, pw, sampling_ratio)
+            worst = max(worst, gy, gx)
+    return worst
+
+
+def exact_forms(rois, scale, n_img, c, h, w, ph, pw, sampling_ratio):
+    """The forms of ``roi_align_fwd_kernel`` (csrc/roi_align.hip) a RoI list reaches with ``c`` channels, as a set of
+    names: 'empty'; 'tab<16|8|4>' (table-driven batches), 'lane<16|8|4>' (``fwd_batch_lds4``), 'tail<2|1>'
+    (``fwd_batch_lds``), 'global'; 'pow2' / 'div' (the FAST flag of the RoIs that run a 4-channel form); 'budget<16|8|4|2|1|0>'
+    (the channels per batch the window leaves room for: 4352 // cells, capped at 16 and rounded down to a batch size; 0 =
+    the global path); 'grid<g>' per axis grid."""
+    forms = set()
+    for roi in np.asarray(rois, dtype=_f).reshape(-1, 5):
+        g = geom32(roi, scale, n_img, h, w, ph, pw, sampling_ratio)
+        if g.window is None:
+            forms.add("empty")
+            continue
+        cells = (g.window[1] - g.window[0] + 1) * (g.window[3] - g.window[2] + 1)
+        cs_max = min(16, 4352 // cells)
+        forms.add("budget%d" % max([k for k in (16, 8, 4, 2, 1, 0) if k <= cs_max]))
+        forms.update(("grid%d" % g.gh, "grid%d" % g.gw))
+        tables = ph * g.gh <= 64 and pw * g.gw <= 64 and ph * pw <= 256 and cells <= 4352
+        for c0 in range(0, c, 32):
+            left = min(c, c0 + 32) - c0
+            while left > 0:
+                k = min(left, cs_max)
+                if k >= 4:
+                    k = 16 if k >= 16 else 8 if k >= 8 else 4
+                    forms.update((("tab%d" if tables else "lane%d") % k, "pow2" if g.pow2 else "div"))
+                elif k >= 1:
+                    k = 2 if k >= 2 else 1
+                    forms.add("tail%d" % k)
+                else:
+                    k = 1
+                    forms.add("global")
+                left -= k
+    return forms
+
+
+def _axis_state32(start, bin_, p, size):
+    """The shared-tap path's view of one axis of a bin at a 2-sample grid: 'none' (both samples invalid), 'first' / 'last'
+    (only that sample valid), 'same' (both in one cell pair), 'diff'."""
+    taps = []
+    for i in range(2):
+        v = _coord32(start, p, bin_, i, 2)
+        if v < -1 or v > size:
+            taps.append(None)
+            continue
+        lo = _low32(v, size)
+        taps.append((lo, min(lo + 1, size - 1)))
+    if taps[0] is None or taps[1] is None:
+        return "none" if taps[0] is None and taps[1] is None else "first" if taps[1] is None else "last"
+    return "same" if taps[0] == taps[1] else "diff"
+
+
+def shared_tap_states(rois, scale, n_img, h, w, ph, pw, bin_stride):
+    """The (row state, column state) pairs that the bins (s i, s j) of the RoIs take in the ``gh == gw == 2`` path of
+    ``pool_nhwc_strided`` at sampling ratio 2 (``same_rows`` / ``same_cols`` / ``oky`` / ``okx`` per bin)."""
+    states = set()
+    for roi in np.asarray(rois, dtype=_f).reshape(-1, 5):
+        g = geom32(roi, scale, n_img, h, w, ph, pw, 2)
+        if g.window is None:
+            continue
+        rows = {_axis_state32(g.start[0], g.bin[0], p, h) for p in range(0, ph, bin_stride)}
+        cols = {_axis_state32(g.start[1], g.bin[1], p, w) for p in range(0, pw, bin_stride)}
+        states.update((a, b) for a in rows for b in cols)
+    return states
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -249,14 +478,15 @@ def edge_rois(h, w):
                      [0, 0.5 * iw, 0.5 * ih, 0.5 * iw - 40.0, 0.5 * ih + 33.0]], dtype=_f)  # malformed: x2 < x1
 
 
-def cleared(rois, ph, pw, n, h, w, sampling_ratios=(0,)):
-    """The same RoIs, any whose samples sit within 4 d of a validity boundary shifted by 0.37 px steps until none does."""
+def cleared(rois, ph, pw, n, h, w, sampling_ratios=(0,), scale=SCALE):
+    """The same RoIs, any whose samples sit within 4 d of a validity boundary shifted by 0.37 px steps (at the scale 1/16;
+    the same fraction of a cell at another) until none does."""
     rois = np.array(rois, dtype=_f)
     for r in range(rois.shape[0]):
         for _ in range(8):
-            if all(clearance_of(rois[r], SCALE, ph, pw, n, h, w, sr) >= 4.0 for sr in sampling_ratios):
+            if all(clearance_of(rois[r], scale, ph, pw, n, h, w, sr) >= 4.0 for sr in sampling_ratios):
                 break
-            rois[r, 1:] += _f(0.37)
+            rois[r, 1:] += _f(0.37 * SCALE / scale)
         else:
             raise AssertionError(("no clear placement", r, rois[r]))
     return rois

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.roi_align_reference import _window_cells
+
 pytestmark = pytest.mark.gpu
 
 
@@ -29,29 +31,6 @@ def _rois(g, r, n_img, img_w, img_h, wmin, wmax):
 def _channels_last(x):
     """Same values and shape, NHWC memory: what the trunk hands to the poolers."""
     return x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-
-
-def _window_cells(rois, scale, n_img, h, w, p, sampling_ratio):
-    """Cells of each RoI's feature-map window (0: no sample inside the map) -- the host twin of ``make_geom`` in
-    csrc/roi_geom.h, in float32 like the kernel."""
-    f = np.float32
-    cells = []
-    for b, x1, y1, x2, y2 in rois.numpy().astype(f):
-        size = []
-        for lo, hi, n in ((y1, y2, h), (x1, x2, w)):
-            start = f(lo * f(scale))
-            roi = max(f(f(hi * f(scale)) - start), f(1))
-            bin_ = f(roi / f(p))
-            grid = sampling_ratio if sampling_ratio > 0 else int(np.ceil(bin_))
-            first = f(start + f(f(0.5) * bin_) / f(grid))
-            last = f(f(start + f(f(p - 1) * bin_)) + f(f(f(grid - 1) + f(0.5)) * bin_) / f(grid))
-            if not (np.isfinite(first) and np.isfinite(last)) or last < -1 or first > n:
-                size.append(0)
-                continue
-            low = lambda v: 0 if v <= 0 else min(int(v), n - 1)
-            size.append(min(low(min(last, f(n))) + 1, n - 1) - low(max(first, f(-1))) + 1)
-        cells.append(size[0] * size[1] if 0 <= int(b) < n_img else 0)
-    return np.array(cells)
 
 
 # ---------------------------------------------------------------- RoIAlign forward
