@@ -11,7 +11,7 @@ output.  COCO rules only, bbox and segm only.
   ``_C.error_types`` (csrc/error_types.hip), which types every detection and flags the missed ground truths.  Three more
   flat arrays come back beside the match tables.
 * on the HOST, here, in NumPy over those flat arrays: the eight fixes and the AP50 of every fixed table (``analyze_tables``),
-  O(detections) each, as ``coco_eval.accumulate`` is -- whose ``_sampled_precision`` makes every precision column, so the base
+  O(detections) each, as ``coco_tables.accumulate`` is -- whose ``_sampled_precision`` makes every precision column, so the base
   AP50 is ``evaluate_coco``'s own, bit for bit, overall and per split.
 
 In a category the order of equal scores is the order of the detection rows (image id, category index, descending score); a
@@ -24,6 +24,7 @@ import torch
 
 from . import coco_eval
 from .. import _C
+from .coco_tables import RECALL_THRESHOLDS, _mean, _sampled_precision
 
 ERROR_TYPES = _C.ERROR_TYPES[1:]  # Cls, Loc, Both, Dupe, Bkg: err_type 1 .. 5
 MAIN_TYPES = ERROR_TYPES + ("Miss",)
@@ -35,14 +36,14 @@ def _precision_columns(det_cat, scores, tp, fp, alive, npig):
     """fp64 [1, R, K]: the precision of every category at the 101 recall samples (area all, IoU 0.5) -- -1 where ``npig[k]``
     (the category's non-ignored ground truths) is 0 -- from the detections ``alive`` keeps: ``tp`` / ``fp`` bool [D] (an
     ignored detection is neither), merged per category by descending score, stably in row order."""
-    columns = -np.ones((1, len(coco_eval.RECALL_THRESHOLDS), len(npig)))
+    columns = -np.ones((1, len(RECALL_THRESHOLDS), len(npig)))
     rows = np.flatnonzero(alive)
     rows = rows[np.lexsort((-scores[rows], det_cat[rows]))]  # stable: equal scores of a category stay in row order
     cuts = np.searchsorted(det_cat[rows], np.arange(len(npig) + 1))
     for k in np.flatnonzero(npig > 0):
         sel = rows[cuts[k]:cuts[k + 1]]
-        columns[0, :, k] = coco_eval._sampled_precision(np.cumsum(tp[sel]).astype(np.float64),
-                                                        np.cumsum(fp[sel]).astype(np.float64), npig[k])
+        columns[0, :, k] = _sampled_precision(np.cumsum(tp[sel]).astype(np.float64), np.cumsum(fp[sel]).astype(np.float64),
+                                              npig[k])
     return columns
 
 
@@ -57,11 +58,11 @@ def _claims(fixed, target, scores, free):
 
 
 def analyze_tables(tables, num_categories, class_splits):
-    """The analysis of one iou type from its match tables with the arrays ``score_chunk(error_thresholds=...)`` adds
-    (``err_type``, ``err_gt``, ``gt_missed``) -> OrderedDict: ``AP50`` and ``AP50_split_<split>`` (the base), ``dAP50_<T>`` for
-    Cls, Loc, Both, Dupe, Bkg, Miss, FalsePos, FalseNeg, ``dAP50_<T>_split_<split>`` for the first six, ``counts`` {"all" or
-    split: {T: errors}} (by the detection's category; Miss by the ground truth's) and ``cls_confusion_by_split`` {split of
-    the target ground truth: {split of the detection: Cls errors}}.  ``class_splits``: {split: [category indices]}."""
+    """The analysis of one iou type from match tables scored with ``error_thresholds`` (the structure: engine/coco_tables.py)
+    -> OrderedDict: ``AP50`` and ``AP50_split_<split>`` (the base), ``dAP50_<T>`` for Cls, Loc, Both, Dupe, Bkg, Miss, FalsePos,
+    FalseNeg, ``dAP50_<T>_split_<split>`` for the first six, ``counts`` {"all" or split: {T: errors}} (by the detection's
+    category; Miss by the ground truth's) and ``cls_confusion_by_split`` {split of the target ground truth: {split of the
+    detection: Cls errors}}.  ``class_splits``: {split: [category indices]}."""
     if "err_type" not in tables:
         if len(tables["det_start"]) > 1 or tables["det_start"][-1] or tables["gt_start"][-1]:
             raise ValueError("analyze_tables: match tables without err_type: score them with error_thresholds=(t_f, t_b)")
@@ -101,7 +102,7 @@ def analyze_tables(tables, num_categories, class_splits):
         return _precision_columns(det_cat, scores, tp, fp, alive, np.bincount(gt_cat[taken & ~crowd], minlength=num_categories))
 
     def means(columns):
-        return [coco_eval._mean(columns)] + [coco_eval._mean(columns[:, :, list(cats)]) for cats in class_splits.values()]
+        return [_mean(columns)] + [_mean(columns[:, :, list(cats)]) for cats in class_splits.values()]
 
     base = means(_precision_columns(det_cat, scores, tp, fp, alive, npig))
     res = OrderedDict(AP50=base[0])
@@ -148,33 +149,34 @@ def _check(iou_types, fg_threshold, bg_threshold, who):
     return float(fg_threshold), float(bg_threshold)
 
 
+def _analyze(who, match_tables, dataset, detections, iou_types, device, fg_threshold, bg_threshold, max_images):
+    """What ``analyze_errors`` and ``analyze_errors_results`` share.  ``match_tables``: ``coco_eval``'s entry for their kind of
+    detections; ``detections``: {iou_type: what it scores} -- a requested iou_type it does not have is checked and skipped."""
+    device = coco_eval._scoring_device(device, who)
+    thresholds = _check(iou_types, fg_threshold, bg_threshold, who)
+    ground_truth = coco_eval._ground_truth(dataset)
+    with torch.cuda.device(device):
+        scored = OrderedDict((t, match_tables(dataset, detections[t], t, device, ground_truth=ground_truth,
+                                              max_images=max_images, error_thresholds=thresholds)[0])
+                             for t in iou_types if t in detections)
+    return analyze_scored(dataset, scored, ground_truth[0])
+
+
 def analyze_errors(dataset, predictions, iou_types=("bbox", "segm"), device="cuda", fg_threshold=FG_THRESHOLD,
                    bg_threshold=BG_THRESHOLD, max_images=None):
     """{iou_type: ``analyze_tables``' numbers} for ``predictions`` (what ``evaluate_coco`` takes): the base ``AP50`` and
     ``AP50_split_<split>`` are ``evaluate_coco``'s, bit for bit.  ``fg_threshold`` / ``bg_threshold``: t_f and t_b of the rules
     in include/ovis_hip.h; ``max_images``: the most images of a chunk (``match_tables``).  Scores on the HIP device."""
-    device = coco_eval._scoring_device(device, "analyze_errors")
-    thresholds = _check(iou_types, fg_threshold, bg_threshold, "analyze_errors")
-    ground_truth = coco_eval._ground_truth(dataset)
-    with torch.cuda.device(device):
-        scored = OrderedDict((t, coco_eval.match_tables(dataset, predictions, t, device, ground_truth=ground_truth,
-                                                        max_images=max_images, error_thresholds=thresholds)[0])
-                             for t in iou_types)
-    return analyze_scored(dataset, scored, ground_truth[0])
+    return _analyze("analyze_errors", coco_eval.match_tables, dataset, dict.fromkeys(iou_types, predictions), iou_types, device,
+                    fg_threshold, bg_threshold, max_images)
 
 
 def analyze_errors_results(dataset, results, iou_types=("bbox", "segm"), device="cuda", fg_threshold=FG_THRESHOLD,
                            bg_threshold=BG_THRESHOLD, max_images=None):
     """``analyze_errors`` for detections from COCO results files: ``results`` is {iou_type: a path or the parsed list}
     (``coco_eval.load_coco_results``); an iou_type it does not have is skipped."""
-    device = coco_eval._scoring_device(device, "analyze_errors_results")
-    thresholds = _check(iou_types, fg_threshold, bg_threshold, "analyze_errors_results")
-    ground_truth = coco_eval._ground_truth(dataset)
-    with torch.cuda.device(device):
-        scored = OrderedDict((t, coco_eval.results_match_tables(dataset, results[t], t, device, ground_truth=ground_truth,
-                                                                max_images=max_images, error_thresholds=thresholds)[0])
-                             for t in iou_types if t in results)
-    return analyze_scored(dataset, scored, ground_truth[0])
+    return _analyze("analyze_errors_results", coco_eval.results_match_tables, dataset, results, iou_types, device,
+                    fg_threshold, bg_threshold, max_images)
 
 
 def task_tables(analysis):

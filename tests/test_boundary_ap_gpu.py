@@ -230,13 +230,11 @@ def test_sharded_equals_unsharded(cases):
     assert list(alone) == ["boundary"] and all(alone["boundary"][k] == want["boundary"][k] for k in alone["boundary"])
     # two shards' tables, merged as rank 0 merges them, are the unsharded tables
     cat_ids, images = coco_eval._ground_truth(dataset)
-    cat_index = {c: i for i, c in enumerate(cat_ids)}
-    label_to_cat = {label: cat_index[j] for label, j in dataset.contiguous_category_id_to_json_id.items()}
     by_image = {dataset.id_to_img_map[i]: p for i, p in local.items()}
     parts = {"segm": [], "boundary": []}
     for shard in (images[4:], images[:4]):
-        dets = [coco_eval._detections(by_image.get(im["id"]), im, label_to_cat, True) for im in shard]
-        scored = coco_eval._score_rows(shard, dets, ("segm", "boundary"), torch.device(DEV, 0), None, None, None)
+        dets = coco_eval._detection_rows(dataset, by_image, (cat_ids, shard), True)
+        scored = coco_eval._score_rows(shard, dets, ("segm", "boundary"), torch.device(DEV, 0))
         problems = [len(np.union1d(d["cats"], im["cats"])) for im, d in zip(shard, dets)]
         for task in parts:
             scored[task]["image"] = np.repeat(np.asarray([im["id"] for im in shard], dtype=np.int64), problems)

@@ -295,16 +295,14 @@ def test_sharded_equals_unsharded(case):
     for task in TYPES:
         assert list(got[task].items()) == list(want[task].items()), task
     # the images split over two owner lists: the tables, merged as rank 0 merges them, are the unsharded tables
-    cat_ids, images = coco_eval._ground_truth(dataset, "lvis")
-    cat_index = {c: i for i, c in enumerate(cat_ids)}
-    label_to_cat = {label: cat_index[j] for label, j in dataset.contiguous_category_id_to_json_id.items()}
+    options = coco_eval.ScoringOptions(rules="lvis")
+    cat_ids, images = coco_eval._ground_truth(dataset, options)
     by_image = {dataset.id_to_img_map[i]: p for i, p in local.items()}
-    for job, tasks in (("bbox", ("bbox",)), (("segm", "boundary"), ("segm", "boundary"))):
+    for tasks in (("bbox",), ("segm", "boundary")):
         parts = {task: [] for task in tasks}
         for shard in (images[4:], images[:4]):
-            dets = [coco_eval._detections(by_image.get(im["id"]), im, label_to_cat, job != "bbox", "lvis") for im in shard]
-            scored = coco_eval._score_rows(shard, dets, job, torch.device(DEV, 0), None, None, None, rules="lvis")
-            scored = {job: scored} if isinstance(job, str) else scored
+            dets = coco_eval._detection_rows(dataset, by_image, (cat_ids, shard), tasks[0] != "bbox", options)
+            scored = coco_eval._score_rows(shard, dets, tasks, torch.device(DEV, 0), options)
             problems = [len(np.union1d(d["cats"], im["cats"])) for im, d in zip(shard, dets)]
             for task in tasks:
                 scored[task]["image"] = np.repeat(np.asarray([im["id"] for im in shard], dtype=np.int64), problems)
