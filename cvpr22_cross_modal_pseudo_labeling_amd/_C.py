@@ -1623,6 +1623,35 @@ def transform_images(data, desc, mean, std, to_bgr255, pad_hw, max_in_hw=None):
     return out
 
 
+def color_jitter(data, desc, ops, params, max_in_hw=None, contrast=True):
+    """uint8 [bytes]: the packed raw images of ``transform_images`` after ColorJitter (``ovis_color_jitter_u8``;
+    data/transforms/transforms.py:88-102), with the bytes PIL produces; a new tensor, ``data`` is left as it is.  ops int32
+    [B, 4]: per image the operations in application order (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 unused trailing
+    slot); params float32 [B, 4]: the factor of each slot, for hue the shift 0..255.  Device tensors: max_in_hw as for
+    ``transform_images``; at most two launches, the tables are never read back.  ``contrast=False`` is the caller's
+    statement that no row holds contrast: the grey-sum launch and its workspace are skipped.  Host tensors:
+    ``libovis_cpu.so``, same bytes."""
+    if not data.is_cuda:
+        return _cpu.color_jitter(data, desc, ops, params)
+    data, desc = _dev(data, "data", torch.uint8), _dev(desc, "desc", torch.int32)
+    ops, params = _dev(ops, "ops", torch.int32), _dev(params, "params")
+    b = desc.shape[0] if desc.dim() == 2 else -1
+    if (data.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 7 or tuple(ops.shape) != (b, 4) or tuple(params.shape) != (b, 4)
+            or max_in_hw is None):
+        raise RuntimeError("color_jitter: expected data [bytes] uint8, desc [B,7] int32, ops [B,4] int32, params [B,4] float32 "
+                           "and max_in_hw")
+    max_h, max_w = int(max_in_hw[0]), int(max_in_hw[1])
+    with _on(data.device):
+        out = torch.empty_like(data)
+        if b:
+            nbytes = _L.ovis_color_jitter_workspace_bytes(b) if contrast else 0
+            ws = _workspace(nbytes, data.device)
+            rc = _L.ovis_color_jitter_u8(data.data_ptr(), data.numel(), desc.data_ptr(), ops.data_ptr(), params.data_ptr(), b,
+                                         max_h, max_w, _ptr(ws), nbytes, out.data_ptr(), _stream())
+            _lib.check(rc, "color_jitter")
+    return out
+
+
 def weighted_ce_fwd_bwd(logits, labels, bg_weight, need_grad=True):
     """-> (loss scalar tensor, dlogits or None)"""
     if not logits.is_cuda:

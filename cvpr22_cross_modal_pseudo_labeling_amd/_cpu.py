@@ -185,6 +185,22 @@ def transform_images(data, desc, mean, std, to_bgr255, pad_hw):
     return out
 
 
+# ---- data/transforms/transforms.py:88-102 (ColorJitter) on packed uint8 images ------------------------------------------------
+def color_jitter(data, desc, ops, params):
+    """uint8 [bytes]: the packed images jittered (``ovis_cpu_color_jitter_u8``), the layout of ``data``."""
+    data, desc = _host(data, "data", torch.uint8), _host(desc, "desc", torch.int32)
+    ops, params = _host(ops, "ops", torch.int32), _host(params, "params")
+    b = desc.shape[0] if desc.dim() == 2 else -1
+    if data.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 7 or tuple(ops.shape) != (b, 4) or tuple(params.shape) != (b, 4):
+        raise RuntimeError("color_jitter: expected data [bytes] uint8, desc [B,7] int32, ops [B,4] int32 and params [B,4] float32")
+    out = torch.empty_like(data)
+    if b:
+        _check(load().ovis_cpu_color_jitter_u8(data.data_ptr(), data.numel(), desc.data_ptr(), ops.data_ptr(), params.data_ptr(),
+                                               b, out.data_ptr(), 0), "color_jitter",
+               "OVIS_EINVAL (a descriptor that leaves the byte buffer)")
+    return out
+
+
 # ---- engine/inference.py:519-589 (overlay_boxes, overlay_filled_mask, overlay_uncertainty_mask) over the Masker paste ----------
 def render_instances(image, maps, boxes, colors, kinds, params, alpha, outline_colors, outline_thickness):
     """uint8 [H, W, 3] (``ovis_cpu_render_instances_u8``); the operands as ``_C.render_instances`` prepared them."""

@@ -19,6 +19,7 @@
 #endif
 
 #define OVIS_HD static inline
+#include "../color_jitter_chain.h"
 #include "../pasted_value.h"
 #include "../render_geom.h"
 #include "../resample_geom.h"
@@ -402,6 +403,52 @@ extern "C" int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes
         }
         for (int c = 0; c < 3; ++c) px[c * plane] = normalized_channel(u, c, to_bgr255, mean, std);
       }
+    }
+  }
+  return OVIS_CPU_OK;
+}
+
+// ---- colour jitter: host twin of ovis_color_jitter_u8 (csrc/color_jitter.hip), the arithmetic of color_jitter_chain.h ------------
+extern "C" int ovis_cpu_color_jitter_u8(const uint8_t* data, long data_bytes, const int32_t* desc, const int32_t* ops,
+                                        const float* params, int batch, uint8_t* out, int threads) {
+  if (batch < 0 || data_bytes < 0) return OVIS_CPU_EINVAL;
+  if (batch == 0) return OVIS_CPU_OK;
+  if (!data || !desc || !ops || !params || !out) return OVIS_CPU_EINVAL;
+  if ((uintptr_t)data < (uintptr_t)out + (uintptr_t)data_bytes && (uintptr_t)out < (uintptr_t)data + (uintptr_t)data_bytes)
+    return OVIS_CPU_EINVAL;
+  if (batch > 65535) return OVIS_CPU_ERANGE;
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* d = desc + (long)b * kImageDescInts;
+    if (d[1] > kResampleMaxDim || d[2] > kResampleMaxDim) return OVIS_CPU_ERANGE;
+    if (!jitter_desc_in_buffer(d[0], d[1], d[2], data_bytes, kResampleMaxDim, kResampleMaxDim)) return OVIS_CPU_EINVAL;
+  }
+  const int nt = thread_count(threads);
+  for (int b = 0; b < batch; ++b) {
+    const int32_t* d = desc + (long)b * kImageDescInts;
+    const uint8_t* src = data + d[0];
+    uint8_t* dst = out + d[0];
+    const long pixels = (long)d[1] * d[2];
+    const JitterChain c = jitter_chain(ops + (long)b * kJitterSlots, params + (long)b * kJitterSlots);
+    if (c.n <= 0) {  // no operation, or a malformed row: a copy
+      std::memcpy(dst, src, 3 * (size_t)pixels);
+      continue;
+    }
+    int mean = 0;
+    if (c.contrast < c.n) {
+      long sum = 0;
+#pragma omp parallel for schedule(static) num_threads(nt) reduction(+ : sum)
+      for (long p = 0; p < pixels; ++p) {
+        int rgb[3] = {src[3 * p], src[3 * p + 1], src[3 * p + 2]};
+        jitter_apply(c, c.contrast, 0, rgb);
+        sum += jitter_grey(rgb);
+      }
+      mean = jitter_contrast_mean(sum, pixels);
+    }
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (long p = 0; p < pixels; ++p) {
+      int rgb[3] = {src[3 * p], src[3 * p + 1], src[3 * p + 2]};
+      jitter_apply(c, c.n, mean, rgb);
+      for (int k = 0; k < 3; ++k) dst[3 * p + k] = (uint8_t)rgb[k];
     }
   }
   return OVIS_CPU_OK;

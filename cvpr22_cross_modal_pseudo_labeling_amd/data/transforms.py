@@ -7,8 +7,12 @@ flips, the targets' geometry) and packs the raw uint8 images with a seven-int de
 the device (``device``: ``_C.transform_images``, two launches per batch) with the values PIL would have produced, bit for
 bit.  A raw 480 x 640 image is 0.9 MB against 12.8 MB of float32 at 800 x 1066.
 
-Colour jitter (INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE) is not implemented: non-zero values raise where the
-transform is built.
+Colour jitter (INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE; transforms.py:88-102, first in the training Compose) is split
+the same way: ``host`` draws each image's factors and the order of its operations, ``device`` runs them on the packed bytes
+in front of the resize (``_C.color_jitter``, at most two launches per batch), with the bytes PIL produces.  The draw rule
+(``jitter_draws``) and the composition of the PIL calls are torchvision 0.4-0.7's ``ColorJitter`` written out, not run
+against torchvision.  It is an opt-in of ``build_transforms(..., color_jitter=True)`` (tools/train_net.py --color-jitter);
+without it non-zero values raise where the transform is built, and evaluation transforms never jitter.
 """
 import random
 
@@ -40,12 +44,46 @@ def get_size(w, h, min_size, max_size):
     return (oh, ow)
 
 
+JITTER_KEYS = ("BRIGHTNESS", "CONTRAST", "SATURATION", "HUE")  # their positions are the operation codes of _C.color_jitter
+
+
+def check_color_jitter(values):
+    """(brightness, contrast, saturation, hue) as floats; a value below 0, or HUE above 0.5, is a ValueError naming the key."""
+    values = tuple(float(v) for v in values)
+    if len(values) != 4:
+        raise ValueError("color_jitter: expected (brightness, contrast, saturation, hue)")
+    for key, v in zip(JITTER_KEYS, values):
+        if not 0 <= v <= (0.5 if key == "HUE" else float("inf")):
+            raise ValueError(f"INPUT.{key} = {v}: expected a value " + ("in [0, 0.5]" if key == "HUE" else ">= 0"))
+    return values
+
+
+def jitter_draws(rng, values):
+    """One image's ([4 operation codes], [4 parameters]) of ``_C.color_jitter``, drawn as torchvision 0.4-0.7's
+    ``ColorJitter.get_params`` draws on Python's ``random`` (our rule: not run against torchvision).  The keys in the order
+    brightness, contrast, saturation, hue: one ``rng.uniform`` per key whose value is non-zero -- [max(0, 1 - v), 1 + v],
+    for hue [-v, v] -- then ONE ``rng.shuffle`` of the active operations.  The hue parameter is the shift PIL's uint8
+    addition makes, ``int(hue_factor * 255) % 256`` in Python doubles (truncation toward zero, then the wrap)."""
+    active = []
+    for code, v in enumerate(values):
+        if v != 0:
+            f = rng.uniform(-v, v) if code == 3 else rng.uniform(max(0.0, 1.0 - v), 1.0 + v)
+            active.append((code, float(int(f * 255) % 256) if code == 3 else f))
+    rng.shuffle(active)
+    pad = 4 - len(active)
+    return [code for code, _ in active] + [-1] * pad, [p for _, p in active] + [0.0] * pad
+
+
 class InputTransform:
     """``host(images, targets)`` in the loader worker, ``device(raw)`` on the training process' stream; calling the object
-    with a staged batch ``(raw, targets, ...)`` applies the device half -- the form ``DevicePrefetcher(transform=)`` takes."""
+    with a staged batch ``(raw, targets, ...)`` applies the device half -- the form ``DevicePrefetcher(transform=)`` takes.
+    ``color_jitter``: (brightness, contrast, saturation, hue) of ColorJitter, None or all zero for none."""
 
     def __init__(self, min_size, max_size, flip_horizontal_prob, flip_vertical_prob, mean, std, to_bgr255, size_divisible=0,
-                 seed=0):
+                 seed=0, color_jitter=None):
+        self.color_jitter = check_color_jitter(color_jitter) if color_jitter is not None else (0.0,) * 4
+        if not any(self.color_jitter):
+            self.color_jitter = None
         self.min_size = tuple(min_size) if isinstance(min_size, (list, tuple)) else (min_size,)
         self.max_size = max_size
         self.flip_horizontal_prob, self.flip_vertical_prob = float(flip_horizontal_prob), float(flip_vertical_prob)
@@ -58,17 +96,20 @@ class InputTransform:
     def host(self, images, targets=None, rng=None):
         """images: uint8 [h, w, 3] RGB arrays / host tensors of any sizes; targets: their BoxLists (or None).
         -> (raw, targets): ``raw`` holds the packed bytes, the descriptors and the sizes the device half needs as python
-        ints; the targets are resized and flipped copies.  The random draws are the reference's, in its order (the size,
-        then one draw per flip), from ``rng`` or the transform's own seeded generator."""
+        ints; the targets are resized and flipped copies.  The random draws are the reference's, in its order (the colour
+        jitter's when it is on -- ``jitter_draws``, then ``raw`` also holds ``jitter_ops`` / ``jitter_params`` [B, 4] -- the
+        size, then one draw per flip), from ``rng`` or the transform's own seeded generator."""
         rng = rng or self.rng
         if len(images) == 0:
             raise ValueError("InputTransform.host: an empty batch has no padded size")
-        desc, chunks, sizes, out_targets, offset = [], [], [], [], 0
+        desc, chunks, sizes, out_targets, offset, jitter = [], [], [], [], 0, []
         for i, img in enumerate(images):
             img = torch.as_tensor(np.ascontiguousarray(img) if isinstance(img, np.ndarray) else img)
             if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
                 raise ValueError(f"image {i}: expected uint8 [h, w, 3], got {img.dtype} {tuple(img.shape)}")
             h, w = int(img.shape[0]), int(img.shape[1])
+            if self.color_jitter is not None:  # ColorJitter is first in the Compose
+                jitter.append(jitter_draws(rng, self.color_jitter))
             oh, ow = get_size(w, h, rng.choice(self.min_size), self.max_size)
             flip_h = rng.random() < self.flip_horizontal_prob
             flip_v = rng.random() < self.flip_vertical_prob
@@ -91,12 +132,19 @@ class InputTransform:
             pad_h, pad_w = -(-pad_h // d) * d, -(-pad_w // d) * d
         raw = {"data": torch.cat(chunks), "desc": torch.tensor(desc, dtype=torch.int32), "image_sizes": sizes,
                "pad_hw": (pad_h, pad_w), "max_in_hw": (max(d[1] for d in desc), max(d[2] for d in desc))}
+        if jitter:
+            raw["jitter_ops"] = torch.tensor([ops for ops, _ in jitter], dtype=torch.int32)
+            raw["jitter_params"] = torch.tensor([params for _, params in jitter], dtype=torch.float32)
         return raw, (out_targets if targets is not None else None)
 
     # -- device half --------------------------------------------------------------------------------------------------
     def device(self, raw):
         """-> ImageList [B, 3, pad_h, pad_w] with the per-image (h, w), on the device ``raw``'s tensors live on."""
-        tensors = _C.transform_images(raw["data"], raw["desc"], self.mean, self.std, self.to_bgr255, raw["pad_hw"],
+        data = raw["data"]
+        if "jitter_ops" in raw:  # the host half knows whether contrast can occur: its grey-sum launch is skipped otherwise
+            data = _C.color_jitter(data, raw["desc"], raw["jitter_ops"], raw["jitter_params"], raw["max_in_hw"],
+                                   contrast=self.color_jitter is None or self.color_jitter[1] != 0)
+        tensors = _C.transform_images(data, raw["desc"], self.mean, self.std, self.to_bgr255, raw["pad_hw"],
                                       raw["max_in_hw"])
         return ImageList(tensors, [tuple(s) for s in raw["image_sizes"]])
 
@@ -223,15 +271,20 @@ def view_plan(cfg):
     return plan
 
 
-def build_transforms(cfg, is_train=True, seed=0):
+def build_transforms(cfg, is_train=True, seed=0, color_jitter=False):
     """build.py:5-46 for this package's split transform; the evaluation transform of TEST.BBOX_AUG.ENABLED makes every
-    view (``ViewTransform``)."""
+    view (``ViewTransform``).  ``color_jitter=True`` honours INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE in the training
+    transform; without the switch a non-zero key raises, and evaluation transforms never jitter."""
+    jitter = None
     if is_train:
         min_size, max_size = cfg.INPUT.MIN_SIZE_TRAIN, cfg.INPUT.MAX_SIZE_TRAIN
         flip_h, flip_v = cfg.INPUT.HORIZONTAL_FLIP_PROB_TRAIN, cfg.INPUT.VERTICAL_FLIP_PROB_TRAIN
-        jitter = {k: getattr(cfg.INPUT, k) for k in ("BRIGHTNESS", "CONTRAST", "SATURATION", "HUE")}
-        if any(v != 0 for v in jitter.values()):
-            raise NotImplementedError(f"colour jitter is not implemented in the device input transform: INPUT {jitter}")
+        values = {k: getattr(cfg.INPUT, k) for k in JITTER_KEYS}
+        if color_jitter:
+            jitter = check_color_jitter(values[k] for k in JITTER_KEYS)
+        elif any(v != 0 for v in values.values()):
+            raise NotImplementedError(f"colour jitter is an opt-in of the device input transform: build_transforms(..., "
+                                      f"color_jitter=True) / tools/train_net.py --color-jitter honour INPUT {values}")
     else:
         if cfg.TEST.BBOX_AUG.ENABLED:
             return ViewTransform(view_plan(cfg), cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD, cfg.INPUT.TO_BGR255,
@@ -239,4 +292,4 @@ def build_transforms(cfg, is_train=True, seed=0):
         min_size, max_size = cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST
         flip_h = flip_v = 0.0
     return InputTransform(min_size, max_size, flip_h, flip_v, cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD, cfg.INPUT.TO_BGR255,
-                          cfg.DATALOADER.SIZE_DIVISIBILITY, seed=seed)
+                          cfg.DATALOADER.SIZE_DIVISIBILITY, seed=seed, color_jitter=jitter)

@@ -61,6 +61,14 @@ int ovis_cpu_polygons_to_masks_u8(const float* coords, const int32_t* polygon_st
 int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch, const float* mean,
                                  const float* std, int to_bgr255, int pad_h, int pad_w, float* out, int threads);
 
+/* Colour jitter on host tensors: twin of ovis_color_jitter_u8 (include/ovis_hip.h states the rule in full: same layout of
+ * `data`, `desc`, `ops`, `params` and `out`, same bytes -- PIL's) -- ColorJitter of mb/data/transforms/transforms.py:88-102.
+ * A malformed row of `ops` copies its image unchanged, as on the device.  A descriptor that leaves `data`, or `out`
+ * overlapping `data`: OVIS_CPU_EINVAL, nothing is written.  An image dimension above 16384 or batch above 65535:
+ * OVIS_CPU_ERANGE. */
+int ovis_cpu_color_jitter_u8(const uint8_t* data, long data_bytes, const int32_t* desc, const int32_t* ops, const float* params,
+                             int batch, uint8_t* out, int threads);
+
 /* The prediction compositor on host tensors: twin of ovis_render_instances_u8 (include/ovis_hip.h: same arguments, same
  * layer kinds, blends and outline rule, same bytes) -- overlay_boxes, overlay_filled_mask and overlay_uncertainty_mask
  * (mb/engine/inference.py:519-589) over the Masker paste (mb/modeling/roi_heads/mask_head/inference.py:124-165).  `boxes`

@@ -869,6 +869,49 @@ int ovis_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t
                              int max_in_w, const float* mean, const float* std, int to_bgr255, int pad_h, int pad_w,
                              void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* Colour jitter in front of the input transform: ColorJitter, first in the reference's training Compose
+ * (mb/data/transforms/build.py:29-45, transforms.py:88-102 = torchvision's, which composes PIL calls), on the packed bytes
+ * of ovis_transform_images_u8, with the bytes PIL 12 produces (csrc/color_jitter_chain.h, shared with the host twin
+ * ovis_cpu_color_jitter_u8).  The arithmetic was compared with PIL byte for byte; the COMPOSITION of the PIL calls is
+ * torchvision 0.4-0.7's functional_pil written out here, not run against torchvision.
+ *
+ * Per image, on the original RGB image before the resize, the operations of its row of `ops` run in that order, each on
+ * the previous one's 8-bit result:
+ *   blend(d, x, a), d the degenerate value and x the pixel, 0..255, a the float32 factor:
+ *     t = (float)d + a * ((float)x - (float)d), three separate float32 operations, never a fused multiply-add;
+ *     0 <= a <= 1: (uint8)t, truncated; otherwise 0 if t <= 0 (or NaN), 255 if t >= 255, else (uint8)t.
+ *   grey(r, g, b) = (r*19595 + g*38470 + b*7471 + 0x8000) >> 16.
+ *   0 brightness f: every channel blend(0, x, f).
+ *   1 contrast f:   m = (int)(S / N + 0.5), S the exact integer sum of grey over the image AS IT IS AT THIS POINT of the
+ *                   chain, N its pixels, division and addition in fp64 (greys 10 and 11: m = 11); every channel blend(m, x, f).
+ *   2 saturation f: every channel blend(grey(r, g, b), x, f).
+ *   3 hue shift s (an integer 0..255 held exactly in the float; anything else shifts by 0): RGB -> HSV, h = (h + s) & 255,
+ *                   HSV -> RGB.  The round trip is NOT the identity, so it runs for s == 0 too.
+ *     RGB -> HSV: v = max; max == min: h = s = 0.  Otherwise in float32 cr = max - min, sat = cr / max, rc, gc, bc =
+ *       (max - r|g|b) / cr; hf = (float)(bc - gc) if r == max, else (float)(2.0 + (double)rc - (double)bc) if g == max, else
+ *       (float)(4.0 + (double)gc - (double)rc); hf = (float)fmod((double)hf / 6.0 + 1.0, 1.0);
+ *       h = clip8((int)((double)hf * 255.0)); s = clip8((int)(sat * 255.f)).
+ *     HSV -> RGB in fp64: s == 0: (v, v, v).  Otherwise hh = h * 6.0 / 255.0, i = floor(hh), f = hh - i, fs = s / 255.0,
+ *       p = rnd(v * (1 - fs)), q = rnd(v * (1 - fs * f)), t = rnd(v * (1 - fs * (1 - f))), rnd(x) = clip8(floor(x + 0.5));
+ *       (r, g, b) by i % 6: (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q).
+ *
+ * data, data_bytes, desc: as ovis_transform_images_u8; only offset, in_h and in_w of a descriptor are read.  ops [batch, 4]
+ * int32: the codes above in application order, -1 for an unused trailing slot; params [batch, 4] f32, slot-aligned: the
+ * factor, for hue the shift.  Both ON THE DEVICE, never read back.  out: a second buffer of data_bytes bytes with the same
+ * layout; the bytes of every valid image are written, nothing else.  out overlapping data: OVIS_EINVAL (contrast reads the
+ * whole image).  An image whose descriptor leaves the byte buffer or max_in_h / max_in_w writes nothing (the transform
+ * behind it turns it into NaN); a malformed row of ops (a code outside -1..3, a repeated code, a code behind an unused
+ * slot) copies its image unchanged; no table content makes a kernel leave data, out or the workspace.
+ * workspace: ovis_color_jitter_workspace_bytes(batch) bytes, 8-byte aligned: one 64-bit grey sum per image, zeroed on the
+ * stream; too small: OVIS_ENOSPC.  workspace NULL: the caller states that no row holds contrast -- the sum launch is
+ * skipped, and a row that holds contrast anyway copies its image unchanged.  At most two launches whatever the batch,
+ * enqueue only; integer sums, so two runs give the same bytes.  max_in_h or max_in_w above 16384, batch above 65535:
+ * OVIS_ERANGE. */
+size_t ovis_color_jitter_workspace_bytes(int batch);
+int ovis_color_jitter_u8(const uint8_t* data, long data_bytes, const int32_t* desc, const int32_t* ops, const float* params,
+                         int batch, int max_in_h, int max_in_w, void* workspace, size_t workspace_bytes, uint8_t* out,
+                         void* stream);
+
 /* Deformable convolution BACKWARD on NHWC rows (csrc/deform_conv_rows.hip; mb/csrc/cuda/deform_conv_cuda.cu:271-497,
  * 580-694): rows m = (image, h_out, w_out), k = (tap, channel), the layout of ovis_deform_conv_implicit_f32.
  * ovis_deform_im2col_pair_rows_f32: the sampled (x mask) rows col[m, (t, c)] written ONCE, in pair layout (row stride

@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
+Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, color_jitter, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -363,6 +363,22 @@ def main():
         res.append({"op": "transform_images (2 launches)", "shape": "2 x (480x640 -> 800x1066) uint8 -> f32", "ms": ms,
                     "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6, "frac_hbm_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS,
                     "host_twin_ms": ms_host, "host_over_device": ms_host / ms, "outputs_equal": equal})
+    if "color_jitter" in ops:  # opt-in: the colour jitter in front of the input transform, 2 x 480 x 640, three chains
+        b_, ih, iw = 2, 480, 640
+        data = torch.randint(0, 256, (b_ * ih * iw * 3,), dtype=torch.uint8, generator=g)
+        desc = torch.tensor([[i * ih * iw * 3, ih, iw, ih, iw, 0, 0] for i in range(b_)], dtype=torch.int32)
+        dd, dc = data.to(dev), desc.to(dev)
+        for name, codes, factors in (("brightness only", [0, -1, -1, -1], [1.3, 0.0, 0.0, 0.0]),
+                                     ("all four, contrast last", [0, 2, 3, 1], [1.3, 0.7, 37.0, 1.2]),
+                                     ("hue only", [3, -1, -1, -1], [37.0, 0.0, 0.0, 0.0])):
+            jo, jp = torch.tensor([codes] * b_, dtype=torch.int32), torch.tensor([factors] * b_, dtype=torch.float32)
+            jod, jpd, contrast = jo.to(dev), jp.to(dev), 1 in codes
+            ms = timeit(lambda: _C.color_jitter(dd, dc, jod, jpd, (ih, iw), contrast=contrast), args.iters)
+            equal = torch.equal(_C.color_jitter(dd, dc, jod, jpd, (ih, iw), contrast=contrast).cpu(), _C.color_jitter(data, desc, jo, jp))
+            nbytes = 2 * data.numel()  # the apply kernel's traffic: the raw bytes read and written once
+            res.append({"op": f"color_jitter ({'memset + 2 launches' if contrast else '1 launch'}): {name}",
+                        "shape": "2 x 480x640 uint8", "ms": ms, "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6,
+                        "frac_hbm_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS, "outputs_equal": equal})
     if "render" in ops:  # opt-in: the prediction compositor, 100 fill layers on one 480 x 640 image, M = 14
         k_, m_, h_, w_ = 100, 14, 480, 640
         probs = torch.rand(k_, m_, m_, generator=g).to(dev)

@@ -1,14 +1,16 @@
 """Training entry point with the reference's command line (tools/train_net.py:162-234):
 
     python -m torch.distributed.run --nproc-per-node N tools/train_net.py --config-file CFG [--dataset-catalog FILE]
-        [--evaluate] [--boundary-ap] [--lvis] [--skip-test] KEY VALUE ...
+        [--color-jitter] [--evaluate] [--boundary-ap] [--lvis] [--skip-test] KEY VALUE ...
 
 One process per GPU (RCCL via torch.distributed, env:// rendezvous), config = defaults <- yaml <- trailing overrides,
 frozen before use.  Without ``--dataset-catalog`` the data stream is the synthetic COCO-shaped generator
 (cvpr22_cross_modal_pseudo_labeling_amd/data/synthetic.py); with it, DATASETS.TRAIN is read from the user's COCO-format
 files (data/catalog.py, data/datasets.py, data/build.py) through the raw input path.  MODEL.WEIGHT (a ``.pth`` in the reference's wire format),
 OUTPUT_DIR resume and SOLVER.CHECKPOINT_PERIOD behave as in the reference (utils/checkpoint.py: checkpoints are written and
-resumed from whenever OUTPUT_DIR is set; ``--no-checkpoints`` opts out).
+resumed from whenever OUTPUT_DIR is set; ``--no-checkpoints`` opts out).  ``--color-jitter`` (with ``--raw-input`` or
+``--dataset-catalog``) makes the training transform honour INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE: the reference's
+ColorJitter in front of the resize, drawn in the loader and run on the device (data/transforms.py); off by default.
 
 ``--evaluate`` (with ``--dataset-catalog``, OUTPUT_DIR and MODEL.DEVICE cuda) is the reference's evaluation while training:
 behind every SOLVER.TEST_PERIOD-th iteration -- counted over the whole run, after that iteration's checkpoint -- every
@@ -55,17 +57,20 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetche
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (LVIS_VOCAB, RawSyntheticBatches,  # noqa: E402
                                                                        SyntheticBatches, calibrate_stem_bn, make_batch,
                                                                        make_embeddings)
-from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import JITTER_KEYS, build_transforms, check_color_jitter  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, evaluation, solver, trainer  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
 
-def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter=0, max_iter=None, seed=0):
+def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter=0, max_iter=None, seed=0, color_jitter=False):
     """-> (loader of host batches, the input transform or None).  ``dataset`` (``--dataset-catalog``): the reference's
     batching over the user's files (data/build.py), counted from ``start_iter``, its size and flip draws seeded by ``seed``;
-    otherwise the endless synthetic streams."""
-    transform = build_transforms(cfg, is_train=True) if (raw_input or dataset is not None) else None
+    otherwise the endless synthetic streams.  ``color_jitter``: the transform honours INPUT.BRIGHTNESS / CONTRAST /
+    SATURATION / HUE (data/transforms.py)."""
+    if color_jitter and not (raw_input or dataset is not None):
+        raise ValueError("color_jitter acts on raw uint8 images: it needs raw_input or a dataset")
+    transform = build_transforms(cfg, is_train=True, color_jitter=color_jitter) if (raw_input or dataset is not None) else None
     if dataset is not None:
         return make_data_loader(cfg, dataset, transform, True, comm.get_rank(), comm.get_world_size(), start_iter=start_iter,
                                 seed=seed, max_iter=max_iter), transform
@@ -79,12 +84,13 @@ def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter
 
 
 def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False, dataset_catalog=None,
-          data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False, lvis=False):
+          data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False, lvis=False, color_jitter=False):
     """``evaluate``: score every DATASETS.TEST set behind every SOLVER.TEST_PERIOD-th iteration
     (engine/evaluation.py::evaluate_in_training) and, unless ``skip_test``, run the final test behind the last one
     (``evaluation.run_datasets``: predictions.pth and coco_results.json under OUTPUT_DIR/inference/<name>/).
     ``boundary_ap``: both also score the ``boundary`` task (engine/coco_eval.py: Boundary AP), behind ``segm``.  ``lvis``:
-    both score under LVIS-style federated rules and write ``lvis_results*.json`` instead."""
+    both score under LVIS-style federated rules and write ``lvis_results*.json`` instead.  ``color_jitter``: the raw input
+    path jitters the training images as INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE say."""
     if lvis and not evaluate:
         raise ValueError("train(lvis=True) changes the rules of what evaluate=True scores")
     if boundary_ap and not evaluate:
@@ -130,7 +136,7 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
     # two HIP streams) and are staged through pinned memory on a copy stream, two batches ahead
     # --raw-input: the workers hand over raw uint8 images at their own sizes with polygon ground truth and only decide the
     # size and the flips (data/transforms.py); resize, flip, normalisation and padding run on the device behind the copy
-    loader, transform = make_data_source(cfg, ims_per_gpu, raw_input, dataset, start_iter, max_iter, seed)
+    loader, transform = make_data_source(cfg, ims_per_gpu, raw_input, dataset, start_iter, max_iter, seed, color_jitter)
     data = DevicePrefetcher(loader, device, depth=2, transform=transform)
     if not cfg.MODEL.WEIGHT and not checkpointer.has_checkpoint():  # random init only: give the frozen BN usable statistics
         images, _ = make_batch(1, device=device, seed=7)
@@ -188,6 +194,10 @@ def main(argv=None):
     parser.add_argument("--dataset-catalog", default=None, metavar="FILE",
                         help="JSON catalog {name: {img_dir, ann_file, ann_file_cap?, vocab_file?}}: train on DATASETS.TRAIN read "
                              "from these COCO-format files instead of the synthetic stream (implies --raw-input)")
+    parser.add_argument("--color-jitter", action="store_true",
+                        help="with --raw-input or --dataset-catalog: honour INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE -- "
+                             "ColorJitter in front of the resize, drawn per image in the loader and run on the device (on the "
+                             "host with MODEL.DEVICE cpu) with the bytes PIL produces; without the flag non-zero keys raise")
     parser.add_argument("--data-dir", default="", help="where the catalog's relative paths are taken from")
     parser.add_argument("--seed", type=int, default=0,
                         help="with --dataset-catalog: the run's seed of the input transform's random draws (sizes, flips)")
@@ -217,6 +227,14 @@ def main(argv=None):
     if args.evaluate and cfg.TEST.BBOX_AUG.ENABLED:
         parser.error("--evaluate scores one view per image while training: set TEST.BBOX_AUG.ENABLED False "
                      "(tools/infer_net.py runs multi-scale / flip testing on a checkpoint)")
+    if args.color_jitter and not (args.raw_input or args.dataset_catalog):
+        parser.error("--color-jitter acts on raw uint8 images in front of the device input transform: give --raw-input or "
+                     "--dataset-catalog (the float32 synthetic stream has no bytes to jitter)")
+    if args.color_jitter:
+        try:
+            check_color_jitter(getattr(cfg.INPUT, k) for k in JITTER_KEYS)
+        except ValueError as e:
+            parser.error(f"--color-jitter: {e}")
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
         # The training process does almost no CPU math, but every multi-threaded host op (a staging memcpy, a reduction over a
@@ -239,7 +257,7 @@ def main(argv=None):
     train(cfg, args.local_rank, distributed, args.max_iter or cfg.SOLVER.MAX_ITER, ims_per_gpu,
           save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input,
           dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed, evaluate=args.evaluate,
-          skip_test=args.skip_test, boundary_ap=args.boundary_ap, lvis=args.lvis)
+          skip_test=args.skip_test, boundary_ap=args.boundary_ap, lvis=args.lvis, color_jitter=args.color_jitter)
     if distributed:
         dist.destroy_process_group()
 
