@@ -1623,6 +1623,32 @@ def transform_images(data, desc, mean, std, to_bgr255, pad_hw, max_in_hw=None):
     return out
 
 
+def transform_images_window(data, desc, mean, std, to_bgr255, pad_hw, max_in_hw=None):
+    """float32 [B, 3, pad_h, pad_w]: ``transform_images`` through a crop window (``ovis_transform_images_window_u8``: scale
+    jitter + fixed-size crop; include/ovis_hip.h states the rule).  desc int32 [B, 11] = the seven of ``transform_images``
+    followed by (win_y, win_x, win_h, win_w), the window in the frame of the resized, flipped image; out_h / out_w are the
+    full resized size, never materialised.  Element (Y, X) inside win_h x win_w is pixel (win_y + Y, win_x + X) of that
+    image, with the bits of the same slice of ``transform_images``' output; zero elsewhere.  Two launches, no host read.
+    Host tensors: ``libovis_cpu.so``, same bits."""
+    if not data.is_cuda:
+        return _cpu.transform_images_window(data, desc, mean, std, to_bgr255, pad_hw)
+    data, desc = _dev(data, "data", torch.uint8), _dev(desc, "desc", torch.int32)
+    if data.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 11 or max_in_hw is None:
+        raise RuntimeError("transform_images_window: expected data [bytes] uint8, desc [B,11] int32 and max_in_hw")
+    b, (pad_h, pad_w), (max_h, max_w) = desc.shape[0], (int(pad_hw[0]), int(pad_hw[1])), (int(max_in_hw[0]), int(max_in_hw[1]))
+    m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+    with _on(data.device):
+        nbytes = _L.ovis_transform_images_window_workspace_bytes(b, max_h, pad_w)
+        out = torch.empty((b, 3, pad_h, pad_w), dtype=torch.float32, device=data.device)
+        if b:
+            ws = _workspace(nbytes, data.device, at_least=1)
+            rc = _L.ovis_transform_images_window_u8(data.data_ptr(), data.numel(), desc.data_ptr(), b, max_h, max_w, m3, s3,
+                                                    int(bool(to_bgr255)), pad_h, pad_w, ws.data_ptr(), nbytes, out.data_ptr(),
+                                                    _stream())
+            _lib.check(rc, "transform_images_window")
+    return out
+
+
 def color_jitter(data, desc, ops, params, max_in_hw=None, contrast=True):
     """uint8 [bytes]: the packed raw images of ``transform_images`` after ColorJitter (``ovis_color_jitter_u8``;
     data/transforms/transforms.py:88-102), with the bytes PIL produces; a new tensor, ``data`` is left as it is.  ops int32
@@ -2403,12 +2429,21 @@ def project_rle_masks(rle_masks, gt_index, boxes, resolution):
         raise RuntimeError("project_rle_masks: positives but no ground-truth mask")
     words, word_offsets = _dev(m.words, "words", torch.int64), _dev(m.word_offsets, "word_offsets", torch.int64)
     instance = _dev(m.instance, "instance", torch.int64)
-    (h0, w0), (w1, h1) = m.source_hw, m.size
+    window = getattr(m, "window", None)
+    (h0, w0), (w1, h1) = m.source_hw, (m.size if window is None else m.frame_size)
     with _on(boxes.device):
-        rc = _L.ovis_project_rle_masks_f32(words.data_ptr(), word_offsets.data_ptr(), word_offsets.numel() - 1,
-                                           m.decoded_words_per_mask, instance.data_ptr() if instance.numel() else 0, instance.numel(),
-                                           gt_index.data_ptr(), boxes.data_ptr(), p, h0, w0, h1, w1, int(m.flip_h),
-                                           int(m.flip_v), int(resolution), out.data_ptr(), _stream())
+        if window is None:
+            rc = _L.ovis_project_rle_masks_f32(words.data_ptr(), word_offsets.data_ptr(), word_offsets.numel() - 1,
+                                               m.decoded_words_per_mask, instance.data_ptr() if instance.numel() else 0, instance.numel(),
+                                               gt_index.data_ptr(), boxes.data_ptr(), p, h0, w0, h1, w1, int(m.flip_h),
+                                               int(m.flip_v), int(resolution), out.data_ptr(), _stream())
+        else:  # RleMasks.crop: (win_x, win_y, win_w, win_h) of the resized, flipped frame; the boxes are in the window's frame
+            win_x, win_y, win_w, win_h = window
+            rc = _L.ovis_project_rle_masks_window_f32(words.data_ptr(), word_offsets.data_ptr(), word_offsets.numel() - 1,
+                                                      m.decoded_words_per_mask, instance.data_ptr() if instance.numel() else 0,
+                                                      instance.numel(), gt_index.data_ptr(), boxes.data_ptr(), p, h0, w0, h1, w1,
+                                                      int(m.flip_h), int(m.flip_v), win_y, win_x, win_h, win_w, int(resolution),
+                                                      out.data_ptr(), _stream())
     _lib.check(rc, "project_rle_masks")
     return out
 

@@ -185,6 +185,23 @@ def transform_images(data, desc, mean, std, to_bgr255, pad_hw):
     return out
 
 
+def transform_images_window(data, desc, mean, std, to_bgr255, pad_hw):
+    """float32 [B, 3, pad_h, pad_w]: the crop window of every resized, flipped image (``ovis_cpu_transform_images_window_u8``;
+    desc [B, 11] as ``_C.transform_images_window`` takes it)."""
+    data, desc = _host(data, "data", torch.uint8), _host(desc, "desc", torch.int32)
+    if data.dim() != 1 or desc.dim() != 2 or desc.shape[1] != 11:
+        raise RuntimeError("transform_images_window: expected data [bytes] uint8 and desc [B,11] int32")
+    b, (pad_h, pad_w) = desc.shape[0], (int(pad_hw[0]), int(pad_hw[1]))
+    out = torch.empty((b, 3, pad_h, pad_w), dtype=torch.float32)
+    if b:
+        m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
+        _check(load().ovis_cpu_transform_images_window_u8(data.data_ptr(), data.numel(), desc.data_ptr(), b, m3, s3,
+                                                          int(bool(to_bgr255)), pad_h, pad_w, out.data_ptr(), 0),
+               "transform_images_window", "OVIS_EINVAL (a descriptor that leaves the byte buffer, or a window that leaves the "
+               "resized image or the canvas)")
+    return out
+
+
 # ---- data/transforms/transforms.py:88-102 (ColorJitter) on packed uint8 images ------------------------------------------------
 def color_jitter(data, desc, ops, params):
     """uint8 [bytes]: the packed images jittered (``ovis_cpu_color_jitter_u8``), the layout of ``data``."""

@@ -408,7 +408,84 @@ extern "C" int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes
   return OVIS_CPU_OK;
 }
 
-// ---- colour jitter: host twin of ovis_color_jitter_u8 (csrc/color_jitter.hip), the arithmetic of color_jitter_chain.h ------------
+// ---- the windowed input transform: host twin of ovis_transform_images_window_u8 (csrc/image_transform.hip).  The horizontal
+// pass runs over the columns the window shows and the input rows its rows read, at the positions of the full resize.
+extern "C" int ovis_cpu_transform_images_window_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch,
+                                                   const float* mean, const float* std, int to_bgr255, int pad_h, int pad_w,
+                                                   float* out, int threads) {
+  if (batch < 0 || pad_h <= 0 || pad_w <= 0 || data_bytes < 0) return OVIS_CPU_EINVAL;
+  if (batch == 0) return OVIS_CPU_OK;
+  if (!data || !desc || !mean || !std || !out) return OVIS_CPU_EINVAL;
+  if (pad_h > kResampleMaxDim || pad_w > kResampleMaxDim || batch > 65535) return OVIS_CPU_ERANGE;
+  auto load = [&](int b) {
+    const int32_t* d = desc + (long)b * kWindowDescInts;
+    return WindowDesc{ImageDesc{d[0], d[1], d[2], d[3], d[4], d[5], d[6]}, d[7], d[8], d[9], d[10]};
+  };
+  for (int b = 0; b < batch; ++b) {
+    const WindowDesc w = load(b);
+    if (w.im.in_h > kResampleMaxDim || w.im.in_w > kResampleMaxDim || w.im.out_h > kResampleMaxDim ||
+        w.im.out_w > kResampleMaxDim)
+      return OVIS_CPU_ERANGE;
+    if (!window_desc_valid(w, data_bytes, kResampleMaxDim, kResampleMaxDim, pad_h, pad_w)) return OVIS_CPU_EINVAL;
+  }
+  const long plane = (long)pad_h * pad_w;
+  const int nt = thread_count(threads);
+  for (int b = 0; b < batch; ++b) {
+    const WindowDesc w = load(b);
+    const ImageDesc d = w.im;
+    const uint8_t* src = data + d.offset;
+    const int x0 = window_first_col(w);
+    int lo, hi;
+    window_input_rows(w, &lo, &hi);
+    // horizontal pass -> uint8 [in_h, win_w, 3], rows [lo, hi) only; skipped when the width does not change
+    std::vector<uint8_t> rows;
+    long stride = 3L * d.in_w;
+    long first = 3L * x0;  // of the window's first column in a row of `src`
+    if (d.out_w != d.in_w) {
+      rows.resize(3UL * d.in_h * w.win_w);
+      stride = 3L * w.win_w;
+      first = 0;
+      const ResampleAxis ax = resample_axis(d.in_w, d.out_w);
+#pragma omp parallel for schedule(static) num_threads(nt)
+      for (int j = 0; j < w.win_w; ++j) {
+        for (int y = lo; y < hi; ++y) {
+          const uint8_t* row = src + 3L * y * d.in_w;
+          int u[3];
+          resample_position([&](int i, int c) { return (int)row[3 * i + c]; }, ax, d.in_w, x0 + j, u);
+          for (int c = 0; c < 3; ++c) rows[y * stride + 3L * j + c] = (uint8_t)u[c];
+        }
+      }
+      src = rows.data();
+    }
+    const ResampleAxis ay = resample_axis(d.in_h, d.out_h);
+    float* o = out + (long)b * 3 * plane;
+#pragma omp parallel for schedule(static) num_threads(nt)
+    for (int Y = 0; Y < pad_h; ++Y) {
+      const int fy = w.win_y + Y;
+      const int yy = d.flip_v ? d.out_h - 1 - fy : fy;
+      for (int X = 0; X < pad_w; ++X) {
+        float* px = o + (long)Y * pad_w + X;
+        if (Y >= w.win_h || X >= w.win_w) {
+          px[0] = px[plane] = px[2 * plane] = 0.f;
+          continue;
+        }
+        const int fx = w.win_x + X;
+        const int xx = d.flip_h ? d.out_w - 1 - fx : fx;
+        const uint8_t* col = src + first + 3L * (xx - x0);
+        int u[3];
+        if (d.out_h != d.in_h) {
+          resample_position([&](int i, int c) { return (int)col[i * stride + c]; }, ay, d.in_h, yy, u);
+        } else {
+          for (int c = 0; c < 3; ++c) u[c] = col[yy * stride + c];
+        }
+        for (int c = 0; c < 3; ++c) px[c * plane] = normalized_channel(u, c, to_bgr255, mean, std);
+      }
+    }
+  }
+  return OVIS_CPU_OK;
+}
+
+// ---- colour jitter: host twin of ovis_color_jitter_u8(csrc/color_jitter.hip), the arithmetic of color_jitter_chain.h ------------
 extern "C" int ovis_cpu_color_jitter_u8(const uint8_t* data, long data_bytes, const int32_t* desc, const int32_t* ops,
                                         const float* params, int batch, uint8_t* out, int threads) {
   if (batch < 0 || data_bytes < 0) return OVIS_CPU_EINVAL;

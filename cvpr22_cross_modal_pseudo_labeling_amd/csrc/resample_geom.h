@@ -79,3 +79,58 @@ OVIS_HD bool image_desc_valid(const ImageDesc d, long data_bytes, int max_in_h, 
   return d.in_h >= 1 && d.in_w >= 1 && d.out_h >= 1 && d.out_w >= 1 && d.in_h <= max_in_h && d.in_w <= max_in_w &&
          d.out_h <= pad_h && d.out_w <= pad_w && d.offset >= 0 && (long)d.offset + 3L * d.in_h * d.in_w <= data_bytes;
 }
+
+// The input positions [lo, hi) output position xx of one axis reads: the xmin / xmax of resample_position, the same
+// expressions.  Both ends are non-decreasing in xx, so outputs [a, b] read no position outside [lo(a), hi(b)).
+OVIS_HD void resample_span(const ResampleAxis a, int in_size, int xx, int* lo, int* hi) {
+  const double center = 0.0 + (xx + 0.5) * a.scale;
+  int xmin = (int)(center - a.support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(center + a.support + 0.5);
+  if (xmax > in_size) xmax = in_size;
+  *lo = xmin;
+  *hi = xmax;
+}
+
+// One image of a windowed batch (scale jitter + fixed-size crop): 11 int32, an ImageDesc followed by the window
+// [win_y, win_y + win_h) x [win_x, win_x + win_w) in the frame of the resized, FLIPPED image.  out_h x out_w is the full
+// resized size, which is never materialised.
+struct WindowDesc {
+  ImageDesc im;
+  int win_y, win_x, win_h, win_w;
+};
+constexpr int kWindowDescInts = 11;
+
+// The window in the frame of the resized image BEFORE the flips: first row / column.
+OVIS_HD int window_first_row(const WindowDesc d) { return d.im.flip_v ? d.im.out_h - d.win_y - d.win_h : d.win_y; }
+OVIS_HD int window_first_col(const WindowDesc d) { return d.im.flip_h ? d.im.out_w - d.win_x - d.win_w : d.win_x; }
+
+// The input rows [lo, hi) the window's rows read in the vertical pass (the rows themselves when that pass is skipped).  A
+// window that shows every row (no crop on this axis: every scale at or below 1) takes every input row without the fp64 spans.
+OVIS_HD void window_input_rows(const WindowDesc d, int* lo, int* hi) {
+  if (d.win_h == d.im.out_h) {
+    *lo = 0;
+    *hi = d.im.in_h;
+    return;
+  }
+  const int y0 = window_first_row(d);
+  if (d.im.out_h == d.im.in_h) {
+    *lo = y0;
+    *hi = y0 + d.win_h;
+    return;
+  }
+  const ResampleAxis a = resample_axis(d.im.in_h, d.im.out_h);
+  int unused;
+  resample_span(a, d.im.in_h, y0, lo, &unused);
+  resample_span(a, d.im.in_h, y0 + d.win_h - 1, &unused, hi);
+}
+
+// A windowed descriptor the kernels may follow without leaving the buffers they were given: the image inside the byte
+// buffer and the bounds, the window inside [0, out_h) x [0, out_w) and no larger than the canvas.
+OVIS_HD bool window_desc_valid(const WindowDesc d, long data_bytes, int max_in_h, int max_in_w, int pad_h, int pad_w) {
+  return d.im.in_h >= 1 && d.im.in_w >= 1 && d.im.out_h >= 1 && d.im.out_w >= 1 && d.im.in_h <= max_in_h &&
+         d.im.in_w <= max_in_w && d.im.out_h <= kResampleMaxDim && d.im.out_w <= kResampleMaxDim && d.win_y >= 0 &&
+         d.win_x >= 0 && d.win_h >= 1 && d.win_w >= 1 && d.win_h <= d.im.out_h - d.win_y && d.win_w <= d.im.out_w - d.win_x &&
+         d.win_h <= pad_h && d.win_w <= pad_w && d.im.offset >= 0 &&
+         (long)d.im.offset + 3L * d.im.in_h * d.im.in_w <= data_bytes;
+}

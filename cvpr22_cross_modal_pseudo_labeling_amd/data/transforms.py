@@ -13,6 +13,12 @@ in front of the resize (``_C.color_jitter``, at most two launches per batch), wi
 (``jitter_draws``) and the composition of the PIL calls are torchvision 0.4-0.7's ``ColorJitter`` written out, not run
 against torchvision.  It is an opt-in of ``build_transforms(..., color_jitter=True)`` (tools/train_net.py --color-jitter);
 without it non-zero values raise where the transform is built, and evaluation transforms never jitter.
+
+Scale jitter with a fixed-size crop (large-scale jitter; Detectron2's ResizeScale + FixedSizeCrop restated, not run against
+Detectron2) is a third opt-in, ``build_transforms(..., scale_jitter=(lo, hi), crop_size=(h, w))`` (tools/train_net.py
+--scale-jitter LO HI [--crop-size H W]).  ``host`` draws a scale in place of the size and a crop window behind the flips
+(``scale_crop_draws``; include/ovis_hip.h states the rule in full), crops the targets to the window and emits 11-column
+descriptors; ``device`` makes only the window's pixels (``_C.transform_images_window``).  Every batch is [B, 3, canvas].
 """
 import random
 
@@ -74,13 +80,78 @@ def jitter_draws(rng, values):
     return [code for code, _ in active] + [-1] * pad, [p for _, p in active] + [0.0] * pad
 
 
+CROP_SIZE = (1024, 1024)   # the default canvas of scale jitter
+MAX_REDRAWS = 8            # of a crop window that leaves an annotated image without a box
+MAX_DIM = 16384            # kResampleMaxDim of csrc/resample_geom.h: every image, resized and canvas dimension
+
+
+def check_scale_jitter(scale_jitter, crop_size=None):
+    """((lo, hi), (crop_h, crop_w)) checked: 0 < lo <= hi, canvas sides >= 1, hi * side <= 16384 (the largest resized
+    dimension the kernels take).  A ValueError names what is off."""
+    try:
+        lo, hi = (float(v) for v in scale_jitter)
+        crop_h, crop_w = (int(v) for v in (crop_size if crop_size is not None else CROP_SIZE))
+    except (TypeError, ValueError):
+        raise ValueError(f"scale_jitter = {scale_jitter}, crop_size = {crop_size}: expected (lo, hi) and (height, width)")
+    if not 0 < lo <= hi or hi == float("inf"):
+        raise ValueError(f"scale_jitter = ({lo}, {hi}): expected 0 < lo <= hi")
+    if crop_h < 1 or crop_w < 1:
+        raise ValueError(f"crop_size = ({crop_h}, {crop_w}): a canvas side is at least 1")
+    if hi * max(crop_h, crop_w) > MAX_DIM:
+        raise ValueError(f"scale_jitter hi = {hi} times crop_size = ({crop_h}, {crop_w}) is above {MAX_DIM}, the largest "
+                         "resized dimension the transform takes")
+    return (lo, hi), (crop_h, crop_w)
+
+
+def jittered_size(h, w, s, crop_size):
+    """(out_h, out_w) of an h x w image at scale ``s`` of the canvas: ResizeScale -- the canvas times s, the image fitted
+    inside it with its aspect ratio; Python doubles and Python's round."""
+    crop_h, crop_w = crop_size
+    r = min(crop_h * s / h, crop_w * s / w)
+    return max(1, round(h * r)), max(1, round(w * r))
+
+
+def crop_window(rng, out_hw, crop_size):
+    """(win_y, win_x, win_h, win_w) of FixedSizeCrop in an out_h x out_w image: two draws, whatever the sizes."""
+    (out_h, out_w), (crop_h, crop_w) = out_hw, crop_size
+    fy, fx = rng.random(), rng.random()
+    win_y, win_x = round(fy * max(out_h - crop_h, 0)), round(fx * max(out_w - crop_w, 0))
+    return win_y, win_x, min(crop_h, out_h - win_y), min(crop_w, out_w - win_x)
+
+
+def crop_target(target, window):
+    """``target`` (in the frame of the resized, flipped image) through the window: BoxList.crop, fields through their own
+    ``crop``, then clip_to_image(remove_empty=True).  Its size is (win_w, win_h)."""
+    win_y, win_x, win_h, win_w = window
+    return target.crop((win_x, win_y, win_x + win_w, win_y + win_h)).clip_to_image(remove_empty=True)
+
+
+def scale_crop_draws(rng, out_hw, crop_size, target=None):
+    """The window of one image, ``target`` its resized and flipped BoxList (or None): a window is drawn; when the image has
+    a box and none survives the crop it is drawn again, at most MAX_REDRAWS times -- the last draw stands.
+    -> (window, the cropped target or None)."""
+    boxes = None
+    if target is not None and len(target):
+        boxes = type(target)(target.bbox, target.size)  # the survival test needs no field
+    for _ in range(1 + MAX_REDRAWS):
+        window = crop_window(rng, out_hw, crop_size)
+        if boxes is None or len(crop_target(boxes, window)):
+            break
+    return window, (crop_target(target, window) if target is not None else None)
+
+
 class InputTransform:
     """``host(images, targets)`` in the loader worker, ``device(raw)`` on the training process' stream; calling the object
     with a staged batch ``(raw, targets, ...)`` applies the device half -- the form ``DevicePrefetcher(transform=)`` takes.
-    ``color_jitter``: (brightness, contrast, saturation, hue) of ColorJitter, None or all zero for none."""
+    ``color_jitter``: (brightness, contrast, saturation, hue) of ColorJitter, None or all zero for none.
+    ``scale_jitter``: (lo, hi), the scale range of large-scale jitter on the canvas ``crop_size`` = (height, width), default
+    1024 x 1024; None for none -- then ``crop_size`` must be None too, and both halves are what they are without it."""
 
     def __init__(self, min_size, max_size, flip_horizontal_prob, flip_vertical_prob, mean, std, to_bgr255, size_divisible=0,
-                 seed=0, color_jitter=None):
+                 seed=0, color_jitter=None, scale_jitter=None, crop_size=None):
+        if scale_jitter is None and crop_size is not None:
+            raise ValueError("crop_size is the canvas of scale_jitter: give scale_jitter too")
+        self.scale_jitter, self.crop_size = check_scale_jitter(scale_jitter, crop_size) if scale_jitter is not None else (None, None)
         self.color_jitter = check_color_jitter(color_jitter) if color_jitter is not None else (0.0,) * 4
         if not any(self.color_jitter):
             self.color_jitter = None
@@ -98,7 +169,9 @@ class InputTransform:
         -> (raw, targets): ``raw`` holds the packed bytes, the descriptors and the sizes the device half needs as python
         ints; the targets are resized and flipped copies.  The random draws are the reference's, in its order (the colour
         jitter's when it is on -- ``jitter_draws``, then ``raw`` also holds ``jitter_ops`` / ``jitter_params`` [B, 4] -- the
-        size, then one draw per flip), from ``rng`` or the transform's own seeded generator."""
+        size, then one draw per flip), from ``rng`` or the transform's own seeded generator.  With ``scale_jitter`` the
+        size draw is the scale's, the window's draws follow the flips (``scale_crop_draws``), the descriptors have 11
+        columns, ``image_sizes`` holds the windows' (win_h, win_w), ``pad_hw`` is the canvas and the targets are cropped."""
         rng = rng or self.rng
         if len(images) == 0:
             raise ValueError("InputTransform.host: an empty batch has no padded size")
@@ -110,7 +183,10 @@ class InputTransform:
             h, w = int(img.shape[0]), int(img.shape[1])
             if self.color_jitter is not None:  # ColorJitter is first in the Compose
                 jitter.append(jitter_draws(rng, self.color_jitter))
-            oh, ow = get_size(w, h, rng.choice(self.min_size), self.max_size)
+            if self.scale_jitter is not None:  # in place of the size draw
+                oh, ow = jittered_size(h, w, rng.uniform(*self.scale_jitter), self.crop_size)
+            else:
+                oh, ow = get_size(w, h, rng.choice(self.min_size), self.max_size)
             flip_h = rng.random() < self.flip_horizontal_prob
             flip_v = rng.random() < self.flip_vertical_prob
             desc.append([offset, h, w, oh, ow, int(flip_h), int(flip_v)])
@@ -118,15 +194,22 @@ class InputTransform:
             offset += h * w * 3
             if offset >= 2 ** 31:
                 raise ValueError("a batch of raw images is limited to 2 GiB")
-            sizes.append((oh, ow))
+            t = None
             if targets is not None:
                 t = targets[i].resize((ow, oh))
                 if flip_h:
                     t = t.transpose(FLIP_LEFT_RIGHT)
                 if flip_v:
                     t = t.transpose(FLIP_TOP_BOTTOM)
+            if self.scale_jitter is not None:  # the window lives in the frame of the resized, flipped image
+                window, t = scale_crop_draws(rng, (oh, ow), self.crop_size, t)
+                desc[-1] += list(window)
+                sizes.append((window[2], window[3]))
+            else:
+                sizes.append((oh, ow))
+            if targets is not None:
                 out_targets.append(t)
-        pad_h, pad_w = max(s[0] for s in sizes), max(s[1] for s in sizes)
+        pad_h, pad_w = self.crop_size or (max(s[0] for s in sizes), max(s[1] for s in sizes))
         if self.size_divisible > 0:  # image_list.py:54-61
             d = self.size_divisible
             pad_h, pad_w = -(-pad_h // d) * d, -(-pad_w // d) * d
@@ -142,10 +225,10 @@ class InputTransform:
         """-> ImageList [B, 3, pad_h, pad_w] with the per-image (h, w), on the device ``raw``'s tensors live on."""
         data = raw["data"]
         if "jitter_ops" in raw:  # the host half knows whether contrast can occur: its grey-sum launch is skipped otherwise
-            data = _C.color_jitter(data, raw["desc"], raw["jitter_ops"], raw["jitter_params"], raw["max_in_hw"],
+            data = _C.color_jitter(data, raw["desc"][:, :7], raw["jitter_ops"], raw["jitter_params"], raw["max_in_hw"],
                                    contrast=self.color_jitter is None or self.color_jitter[1] != 0)
-        tensors = _C.transform_images(data, raw["desc"], self.mean, self.std, self.to_bgr255, raw["pad_hw"],
-                                      raw["max_in_hw"])
+        make = _C.transform_images_window if self.scale_jitter is not None else _C.transform_images
+        tensors = make(data, raw["desc"], self.mean, self.std, self.to_bgr255, raw["pad_hw"], raw["max_in_hw"])
         return ImageList(tensors, [tuple(s) for s in raw["image_sizes"]])
 
     def decode_masks(self, targets):
@@ -271,11 +354,15 @@ def view_plan(cfg):
     return plan
 
 
-def build_transforms(cfg, is_train=True, seed=0, color_jitter=False):
+def build_transforms(cfg, is_train=True, seed=0, color_jitter=False, scale_jitter=None, crop_size=None):
     """build.py:5-46 for this package's split transform; the evaluation transform of TEST.BBOX_AUG.ENABLED makes every
     view (``ViewTransform``).  ``color_jitter=True`` honours INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE in the training
-    transform; without the switch a non-zero key raises, and evaluation transforms never jitter."""
+    transform; without the switch a non-zero key raises, and evaluation transforms never jitter.  ``scale_jitter`` =
+    (lo, hi) with ``crop_size`` = (height, width): large-scale jitter in the training transform (INPUT.MIN_SIZE_TRAIN /
+    MAX_SIZE_TRAIN are then not read); evaluation transforms and ``ViewTransform`` never scale-jitter."""
     jitter = None
+    if scale_jitter is None and crop_size is not None:
+        raise ValueError("crop_size is the canvas of scale_jitter: give scale_jitter too")
     if is_train:
         min_size, max_size = cfg.INPUT.MIN_SIZE_TRAIN, cfg.INPUT.MAX_SIZE_TRAIN
         flip_h, flip_v = cfg.INPUT.HORIZONTAL_FLIP_PROB_TRAIN, cfg.INPUT.VERTICAL_FLIP_PROB_TRAIN
@@ -291,5 +378,7 @@ def build_transforms(cfg, is_train=True, seed=0, color_jitter=False):
                                  cfg.DATALOADER.SIZE_DIVISIBILITY)
         min_size, max_size = cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST
         flip_h = flip_v = 0.0
+        scale_jitter = crop_size = None
     return InputTransform(min_size, max_size, flip_h, flip_v, cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD, cfg.INPUT.TO_BGR255,
-                          cfg.DATALOADER.SIZE_DIVISIBILITY, seed=seed, color_jitter=jitter)
+                          cfg.DATALOADER.SIZE_DIVISIBILITY, seed=seed, color_jitter=jitter, scale_jitter=scale_jitter,
+                          crop_size=crop_size)

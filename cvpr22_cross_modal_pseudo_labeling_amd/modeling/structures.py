@@ -135,8 +135,8 @@ class BoxList(TensorHolder):
         return self
 
     def _fields_follow(self, out, what, *args):
-        """Fields of a resized / flipped copy: per-box tensors (labels, ids) and strings are geometry-free and carried over,
-        as bounding_box.py:105-108 does; an object follows through its own ``resize`` / ``transpose``.  A dense [G, H, W]
+        """Fields of a resized / flipped / cropped copy: per-box tensors (labels, ids) and strings are geometry-free and
+        carried over, as bounding_box.py:105-108 does; an object follows through its own ``resize`` / ``transpose`` / ``crop``.  A dense [G, H, W]
         mask tensor is tied to the old pixel grid and has neither: it raises instead of going stale."""
         for k, v in self.extra_fields.items():
             if torch.is_tensor(v):
@@ -172,6 +172,16 @@ class BoxList(TensorHolder):
         else:
             flipped = torch.cat((xmin, height - ymax, xmax, height - ymin), dim=-1)
         return self._fields_follow(BoxList(flipped, self.size), "transpose", method)
+
+    def crop(self, box):
+        """A copy cropped to ``box`` = (left, upper, right, lower): every coordinate moved into the box's frame and clamped
+        to [0, w] / [0, h], the size (w, h) = (right - left, lower - upper) (bounding_box.py:167-193).  Empty boxes stay:
+        ``clip_to_image`` drops them."""
+        w, h = box[2] - box[0], box[3] - box[1]
+        xmin, ymin, xmax, ymax = self.bbox.split(1, dim=-1)
+        cropped = torch.cat(((xmin - box[0]).clamp(min=0, max=w), (ymin - box[1]).clamp(min=0, max=h),
+                             (xmax - box[0]).clamp(min=0, max=w), (ymax - box[1]).clamp(min=0, max=h)), dim=-1)
+        return self._fields_follow(BoxList(cropped, (w, h)), "crop", box)
 
     def __repr__(self):
         return f"BoxList(num_boxes={len(self)}, image_width={self.size[0]}, image_height={self.size[1]})"
@@ -299,6 +309,24 @@ class PolygonMasks(TensorHolder):
             c[1::2] *= ratios[1]
         return self._with(coords=c, size=size)
 
+    def crop(self, box):
+        """Polygons moved into the frame of ``box`` = (xmin, ymin, xmax, ymax): PolygonInstance.crop
+        (segmentation_mask.py:273-299) -- the box clamped to the current size (at least one pixel), xmin / ymin subtracted
+        in float32, the vertices NOT clamped; the new size is the clamped (w, h)."""
+        current_width, current_height = self.size
+        xmin, ymin, xmax, ymax = map(float, box)
+        if not (xmin <= xmax and ymin <= ymax):
+            raise ValueError(f"PolygonMasks.crop: {tuple(box)}")
+        xmin, ymin = min(max(xmin, 0), current_width - 1), min(max(ymin, 0), current_height - 1)
+        xmax, ymax = min(max(xmax, 0), current_width), min(max(ymax, 0), current_height)
+        xmax, ymax = max(xmax, xmin + 1), max(ymax, ymin + 1)
+        c = self.coords.clone()
+        c[0::2] = c[0::2] - xmin
+        c[1::2] = c[1::2] - ymin
+        # whole numbers as ints: the size goes to the rasteriser as the canvas
+        size = tuple(int(v) if float(v).is_integer() else v for v in (xmax - xmin, ymax - ymin))
+        return self._with(coords=c, size=size)
+
     def convert_to_binarymask(self):
         """uint8 [G, height, width]: every instance rasterised over the whole image (segmentation_mask.py:326-334)."""
         from .. import _C
@@ -321,7 +349,8 @@ class RleMasks(TensorHolder):
     filled by the device decoder), ``sizes`` int32 [N, 2]; the number of values of a string is counted here -- its
     characters c with ((c - 48) & 0x20) == 0 -- so the device decode needs no host read.  ``size`` = (width, height) of the
     frame the masks are asked for in (``resize`` records it, ``transpose`` toggles the flips, both act after the decode,
-    in the reference's order: resize, then flips); ``instance`` int64 [G]: the encoding behind each instance --
+    in the reference's order: resize, then flips; ``crop`` records one integer ``window`` of that frame behind them, and
+    ``size`` becomes the window's); ``instance`` int64 [G]: the encoding behind each instance --
     ``__getitem__`` indexes it and repacks nothing.  ``decoded()`` adds ``words`` / ``word_offsets`` (device) and
     ``decoded_words_per_mask``, the words every slice was given.
     ``image_id`` / ``ann_ids`` name the masks in the error a malformed encoding raises."""
@@ -368,6 +397,7 @@ class RleMasks(TensorHolder):
         self.num_chars, self.num_runs, self.num_items = int(char_offsets[-1]), int(run_offsets[-1]), n
         self.source_hw, self.size = (h0, w0), (w0, h0)
         self.flip_h = self.flip_v = False
+        self.window = self.frame_size = None  # ``crop``: one window behind the resize and the flips
         self.image_id = image_id
         self.ann_ids = list(ann_ids) if ann_ids is not None else list(range(n))
 
@@ -404,6 +434,8 @@ class RleMasks(TensorHolder):
         """Records ``size`` = (width, height) as the frame the masks are resampled to (BinaryMaskList.resize,
         segmentation_mask.py:138-156).  One resize, in front of the flips: that is the chain the kernel evaluates."""
         size = tuple(int(s) for s in size)
+        if self.window is not None:
+            raise NotImplementedError("RleMasks.resize: a resize behind a crop is not the chain the kernel evaluates")
         if size == self.size:
             return self._with()
         if self.size != (self.source_hw[1], self.source_hw[0]):
@@ -419,7 +451,26 @@ class RleMasks(TensorHolder):
         """FLIP_LEFT_RIGHT (0) / FLIP_TOP_BOTTOM (1): segmentation_mask.py:113-116."""
         if method not in (0, 1):
             raise NotImplementedError("Only FLIP_LEFT_RIGHT and FLIP_TOP_BOTTOM implemented")
+        if self.window is not None:
+            raise NotImplementedError("RleMasks.transpose: a flip behind a crop is not the chain the kernel evaluates")
         return self._with(flip_h=not self.flip_h) if method == 0 else self._with(flip_v=not self.flip_v)
+
+    def crop(self, box):
+        """Records ONE integer window, applied behind the recorded resize and flips: ``box`` = (xmin, ymin, xmax, ymax)
+        rounded and clamped as BinaryMaskList.crop does (segmentation_mask.py:118-136: python round, inside the frame, at
+        least one pixel).  ``window`` = (win_x, win_y, win_w, win_h) of ``frame_size``, the (width, height) before the crop;
+        ``size`` becomes (win_w, win_h).  ``project`` then evaluates decode -> resize -> flips -> the window -> the box crop
+        -> resize (``ovis_project_rle_masks_window_f32``).  A second crop raises, as a resize or a flip behind one does."""
+        if self.window is not None:
+            raise NotImplementedError("RleMasks.crop: already cropped; a second crop is not the chain the kernel evaluates")
+        current_width, current_height = self.size
+        xmin, ymin, xmax, ymax = [round(float(b)) for b in box]
+        if not (xmin <= xmax and ymin <= ymax):
+            raise ValueError(f"RleMasks.crop: {tuple(box)}")
+        xmin, ymin = min(max(xmin, 0), current_width - 1), min(max(ymin, 0), current_height - 1)
+        xmax, ymax = min(max(xmax, 0), current_width), min(max(ymax, 0), current_height)
+        xmax, ymax = max(xmax, xmin + 1), max(ymax, ymin + 1)
+        return self._with(window=(xmin, ymin, xmax - xmin, ymax - ymin), frame_size=self.size, size=(xmax - xmin, ymax - ymin))
 
     def names(self):
         """What every encoding is, for an error message."""

@@ -61,6 +61,13 @@ int ovis_cpu_polygons_to_masks_u8(const float* coords, const int32_t* polygon_st
 int ovis_cpu_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch, const float* mean,
                                  const float* std, int to_bgr255, int pad_h, int pad_w, float* out, int threads);
 
+/* The windowed input transform on host tensors (scale jitter + fixed-size crop): twin of ovis_transform_images_window_u8
+ * (include/ovis_hip.h states the rule: desc [batch, 11], same layout of `data` and `out`, same bits).  A descriptor that
+ * leaves `data`, whose window leaves the resized image or is larger than the canvas: OVIS_CPU_EINVAL.  pad_h, pad_w or an
+ * image / resized dimension above 16384, or batch above 65535: OVIS_CPU_ERANGE. */
+int ovis_cpu_transform_images_window_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch, const float* mean,
+                                        const float* std, int to_bgr255, int pad_h, int pad_w, float* out, int threads);
+
 /* Colour jitter on host tensors: twin of ovis_color_jitter_u8 (include/ovis_hip.h states the rule in full: same layout of
  * `data`, `desc`, `ops`, `params` and `out`, same bytes -- PIL's) -- ColorJitter of mb/data/transforms/transforms.py:88-102.
  * A malformed row of `ops` copies its image unchanged, as on the device.  A descriptor that leaves `data`, or `out`

@@ -869,6 +869,42 @@ int ovis_transform_images_u8(const uint8_t* data, long data_bytes, const int32_t
                              int max_in_w, const float* mean, const float* std, int to_bgr255, int pad_h, int pad_w,
                              void* workspace, size_t workspace_bytes, float* out, void* stream);
 
+/* The input transform with scale jitter and a fixed-size crop (large-scale jitter): a random scale, then a crop or pad to a
+ * fixed canvas.  THE RULE is Detectron2's ResizeScale + FixedSizeCrop restated; Detectron2 was not run against it.
+ * Parameters: a scale range (lo, hi), 0 < lo <= hi, and a canvas (crop_h, crop_w), default 1024 x 1024.  Per image, drawn
+ * on Python's random.Random in the loader worker (data/transforms.py::InputTransform.host), behind the colour-jitter draws
+ * when those are on:
+ *   1. s = rng.uniform(lo, hi), IN PLACE OF the choice among INPUT.MIN_SIZE_TRAIN (not read in this mode, nor is
+ *      MAX_SIZE_TRAIN).  r = min(crop_h * s / in_h, crop_w * s / in_w); out_h = max(1, round(in_h * r)),
+ *      out_w = max(1, round(in_w * r)); Python doubles, Python's round (half to even).
+ *   2. the two flip draws, as without the jitter.
+ *   3. the crop window, in the frame of the resized, FLIPPED image: fy = rng.random(), fx = rng.random(), always drawn;
+ *      win_y = round(fy * max(out_h - crop_h, 0)), win_x = round(fx * max(out_w - crop_w, 0));
+ *      win_h = min(crop_h, out_h - win_y), win_w = min(crop_w, out_w - win_x).
+ *   4. if the image had at least one ground-truth box and none survives step 5: fy, fx are drawn again and step 3 redone,
+ *      at most 8 times; the last draw stands (the image may still arrive without targets).
+ *   5. targets: resize and flips as without the jitter, then BoxList.crop((win_x, win_y, win_x + win_w, win_y + win_h))
+ *      (mb/structures/bounding_box.py:167-193; fields through their own crop), then clip_to_image(remove_empty=True).
+ *      The target's size is (win_w, win_h), the image's size (win_h, win_w).
+ * The batch is [batch, 3, pad_h, pad_w], (pad_h, pad_w) the canvas rounded up to DATALOADER.SIZE_DIVISIBILITY, zero outside
+ * win_h x win_w.
+ *
+ * ovis_transform_images_window_u8: the device half.  Everything as ovis_transform_images_u8 except desc [batch, 11] int32 =
+ * its seven followed by (win_y, win_x, win_h, win_w); out_h / out_w stay the FULL resized size, which is never
+ * materialised and may exceed the canvas (up to 16384).  out element (Y, X) with Y < win_h and X < win_w is the normalised
+ * pixel (win_y + Y, win_x + X) of the resized, flipped image -- the arithmetic of csrc/resample_geom.h at the positions of
+ * the full resize, 8-bit rounding between the two passes included, so the bits of that window sliced out of
+ * ovis_transform_images_u8's output -- and zero elsewhere; every element written once.  The horizontal pass computes only
+ * the columns the window shows, over the input rows its rows read.  An image is NaN, every other image untouched, when its
+ * descriptor breaks max_in_h / max_in_w, out_h or out_w is above 16384, its window leaves [0, out_h) x [0, out_w), win_h >
+ * pad_h or win_w > pad_w, or its bytes leave the buffer.  workspace: ovis_transform_images_window_workspace_bytes(batch,
+ * max_in_h, pad_w) = batch * max_in_h * pad_w * 3 bytes, whatever the scale.  Two launches whatever the batch, enqueue only.
+ * Host twin: ovis_cpu_transform_images_window_u8. */
+size_t ovis_transform_images_window_workspace_bytes(int batch, int max_in_h, int pad_w);
+int ovis_transform_images_window_u8(const uint8_t* data, long data_bytes, const int32_t* desc, int batch, int max_in_h,
+                                    int max_in_w, const float* mean, const float* std, int to_bgr255, int pad_h, int pad_w,
+                                    void* workspace, size_t workspace_bytes, float* out, void* stream);
+
 /* Colour jitter in front of the input transform: ColorJitter, first in the reference's training Compose
  * (mb/data/transforms/build.py:29-45, transforms.py:88-102 = torchvision's, which composes PIL calls), on the packed bytes
  * of ovis_transform_images_u8, with the bytes PIL 12 produces (csrc/color_jitter_chain.h, shared with the host twin
@@ -1243,6 +1279,18 @@ int ovis_project_rle_masks_f32(const uint64_t* words, const int64_t* word_offset
                                const int64_t* instance, int num_instances, const int64_t* gt_index, const float* boxes,
                                int num, int h0, int w0, int h1, int w1, int flip_h, int flip_v, int resolution, float* out,
                                void* stream);
+
+/* ovis_project_rle_masks_window_f32: ovis_project_rle_masks_f32 with ONE integer window [win_y, win_y + win_h) x [win_x,
+ * win_x + win_w) of the h1 x w1 frame applied behind the flips (BinaryMaskList.crop, segmentation_mask.py:118-136, of the
+ * fixed-size crop): decode -> the every-tap rule to h1 x w1 -> flips -> the window -> the box crop on the (win_w, win_h)
+ * mask -> the rule again to resolution^2.  boxes are in the WINDOW's frame; a box is rounded and clamped there and the
+ * integer offset added afterwards, as cropping a canvas and cropping it again does (rounding box + offset differs when the
+ * box lands on a .5 and the offset is odd).  A window that leaves the frame or is empty: OVIS_EINVAL.  With the window
+ * equal to the frame the output is bit-equal to ovis_project_rle_masks_f32.  Everything else as there. */
+int ovis_project_rle_masks_window_f32(const uint64_t* words, const int64_t* word_offsets, int num_masks, long words_per_mask,
+                                      const int64_t* instance, int num_instances, const int64_t* gt_index,
+                                      const float* boxes, int num, int h0, int w0, int h1, int w1, int flip_h, int flip_v,
+                                      int win_y, int win_x, int win_h, int win_w, int resolution, float* out, void* stream);
 
 /* ovis_proposal_gt_overlaps (csrc/proposal_recall.hip): the matching of the reference's box-proposal recall,
  * evaluate_box_proposals (mb/data/datasets/evaluation/coco/coco_eval.py:199-312; the greedy loop is :269-290, the area

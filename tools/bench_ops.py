@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, color_jitter, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
+Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, transform_window, color_jitter, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -363,6 +363,30 @@ def main():
         res.append({"op": "transform_images (2 launches)", "shape": "2 x (480x640 -> 800x1066) uint8 -> f32", "ms": ms,
                     "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6, "frac_hbm_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS,
                     "host_twin_ms": ms_host, "host_over_device": ms_host / ms, "outputs_equal": equal})
+    if "transform_window" in ops:  # opt-in: scale jitter + crop on 2 x 480 x 640 with a 1024 x 1024 canvas, against the un-windowed route
+        b_, ih, iw, canvas = 2, 480, 640, 1024
+        data = torch.randint(0, 256, (b_ * ih * iw * 3,), dtype=torch.uint8, generator=g).to(dev)
+        mean, std = (102.9801, 115.9465, 122.7717), (1.0, 1.0, 1.0)
+        for scale, (oh, ow), (wy, wx, wh, ww) in ((2.0, (1536, 2048), (256, 512, 1024, 1024)), (0.5, (384, 512), (0, 0, 384, 512))):
+            full = torch.tensor([[i * ih * iw * 3, ih, iw, oh, ow, i % 2, 0] for i in range(b_)], dtype=torch.int32)
+            win = torch.cat([full, torch.tensor([[wy, wx, wh, ww]] * b_, dtype=torch.int32)], 1).to(dev)
+            full = full.to(dev)
+            pad = (max(oh, canvas), max(ow, canvas))  # the un-windowed route: the full resize, then the slice copy
+
+            def sliced():
+                return _C.transform_images(data, full, mean, std, True, pad, (ih, iw))[:, :, wy:wy + canvas, wx:wx + canvas].contiguous()
+
+            ms_full = timeit(sliced, args.iters)
+            ms = timeit(lambda: _C.transform_images_window(data, win, mean, std, True, (canvas, canvas), (ih, iw)), args.iters)
+            equal = torch.equal(_C.transform_images_window(data, win, mean, std, True, (canvas, canvas), (ih, iw)), sliced())
+            out_bytes = b_ * 3 * canvas * canvas * 4
+            rows = min(ih, -(-wh * ih // oh) + 2)  # the input rows the window's rows read, about
+            nbytes = out_bytes + 2 * b_ * rows * ww * 3 + b_ * rows * iw * 3  # output + intermediate (written, read) + input rows
+            full_bytes = b_ * 3 * pad[0] * pad[1] * 4 + 2 * b_ * ih * ow * 3 + b_ * ih * iw * 3 + (2 * out_bytes if scale > 1 else 0)
+            res.append({"op": "transform_images_window (2 launches)", "shape": f"2 x (480x640 -> {oh}x{ow}, scale {scale}) -> 1024x1024",
+                        "ms": ms, "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6, "frac_hbm_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS,
+                        "transform_images_then_slice_ms": ms_full, "then_slice_bytes_MB": full_bytes / 1e6,
+                        "then_slice_over_window": ms_full / ms, "outputs_equal": equal})
     if "color_jitter" in ops:  # opt-in: the colour jitter in front of the input transform, 2 x 480 x 640, three chains
         b_, ih, iw = 2, 480, 640
         data = torch.randint(0, 256, (b_ * ih * iw * 3,), dtype=torch.uint8, generator=g)

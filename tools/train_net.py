@@ -57,20 +57,28 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.prefetch import DevicePrefetche
 from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (LVIS_VOCAB, RawSyntheticBatches,  # noqa: E402
                                                                        SyntheticBatches, calibrate_stem_bn, make_batch,
                                                                        make_embeddings)
-from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import JITTER_KEYS, build_transforms, check_color_jitter  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import (JITTER_KEYS, build_transforms, check_color_jitter,  # noqa: E402
+                                                                        check_scale_jitter)
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, evaluation, solver, trainer  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
 
-def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter=0, max_iter=None, seed=0, color_jitter=False):
+def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter=0, max_iter=None, seed=0, color_jitter=False,
+                     scale_jitter=None, crop_size=None):
     """-> (loader of host batches, the input transform or None).  ``dataset`` (``--dataset-catalog``): the reference's
     batching over the user's files (data/build.py), counted from ``start_iter``, its size and flip draws seeded by ``seed``;
     otherwise the endless synthetic streams.  ``color_jitter``: the transform honours INPUT.BRIGHTNESS / CONTRAST /
-    SATURATION / HUE (data/transforms.py)."""
+    SATURATION / HUE (data/transforms.py).  ``scale_jitter`` = (lo, hi), ``crop_size`` = (height, width): large-scale jitter
+    on a fixed canvas, behind the colour jitter when both are on."""
     if color_jitter and not (raw_input or dataset is not None):
         raise ValueError("color_jitter acts on raw uint8 images: it needs raw_input or a dataset")
-    transform = build_transforms(cfg, is_train=True, color_jitter=color_jitter) if (raw_input or dataset is not None) else None
+    if scale_jitter is not None and not (raw_input or dataset is not None):
+        raise ValueError("scale_jitter acts in the device input transform: it needs raw_input or a dataset")
+    if crop_size is not None and scale_jitter is None:
+        raise ValueError("crop_size is the canvas of scale_jitter: give scale_jitter too")
+    transform = (build_transforms(cfg, is_train=True, color_jitter=color_jitter, scale_jitter=scale_jitter, crop_size=crop_size)
+                 if (raw_input or dataset is not None) else None)
     if dataset is not None:
         return make_data_loader(cfg, dataset, transform, True, comm.get_rank(), comm.get_world_size(), start_iter=start_iter,
                                 seed=seed, max_iter=max_iter), transform
@@ -84,13 +92,15 @@ def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter
 
 
 def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False, dataset_catalog=None,
-          data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False, lvis=False, color_jitter=False):
+          data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False, lvis=False, color_jitter=False,
+          scale_jitter=None, crop_size=None):
     """``evaluate``: score every DATASETS.TEST set behind every SOLVER.TEST_PERIOD-th iteration
     (engine/evaluation.py::evaluate_in_training) and, unless ``skip_test``, run the final test behind the last one
     (``evaluation.run_datasets``: predictions.pth and coco_results.json under OUTPUT_DIR/inference/<name>/).
     ``boundary_ap``: both also score the ``boundary`` task (engine/coco_eval.py: Boundary AP), behind ``segm``.  ``lvis``:
     both score under LVIS-style federated rules and write ``lvis_results*.json`` instead.  ``color_jitter``: the raw input
-    path jitters the training images as INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE say."""
+    path jitters the training images as INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE say.  ``scale_jitter`` / ``crop_size``:
+    it trains on large-scale-jittered crops of a fixed canvas; the periodic and the final test use the plain test transform."""
     if lvis and not evaluate:
         raise ValueError("train(lvis=True) changes the rules of what evaluate=True scores")
     if boundary_ap and not evaluate:
@@ -136,7 +146,8 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
     # two HIP streams) and are staged through pinned memory on a copy stream, two batches ahead
     # --raw-input: the workers hand over raw uint8 images at their own sizes with polygon ground truth and only decide the
     # size and the flips (data/transforms.py); resize, flip, normalisation and padding run on the device behind the copy
-    loader, transform = make_data_source(cfg, ims_per_gpu, raw_input, dataset, start_iter, max_iter, seed, color_jitter)
+    loader, transform = make_data_source(cfg, ims_per_gpu, raw_input, dataset, start_iter, max_iter, seed, color_jitter,
+                                         scale_jitter, crop_size)
     data = DevicePrefetcher(loader, device, depth=2, transform=transform)
     if not cfg.MODEL.WEIGHT and not checkpointer.has_checkpoint():  # random init only: give the frozen BN usable statistics
         images, _ = make_batch(1, device=device, seed=7)
@@ -198,6 +209,14 @@ def main(argv=None):
                         help="with --raw-input or --dataset-catalog: honour INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE -- "
                              "ColorJitter in front of the resize, drawn per image in the loader and run on the device (on the "
                              "host with MODEL.DEVICE cpu) with the bytes PIL produces; without the flag non-zero keys raise")
+    parser.add_argument("--scale-jitter", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                        help="with --raw-input or --dataset-catalog: large-scale jitter -- per image a scale drawn from [LO, HI] "
+                             "of the canvas in place of INPUT.MIN_SIZE_TRAIN, then a random crop or a zero pad to the canvas "
+                             "(Detectron2's ResizeScale + FixedSizeCrop restated); boxes, polygon and RLE masks follow the crop. "
+                             "Captions are carried unchanged: a crop can remove the object a caption noun names (HI <= 1 never "
+                             "crops an image of the canvas' aspect ratio)")
+    parser.add_argument("--crop-size", type=int, nargs=2, default=None, metavar=("H", "W"),
+                        help="with --scale-jitter: the canvas every training image is cropped or padded to (default 1024 1024)")
     parser.add_argument("--data-dir", default="", help="where the catalog's relative paths are taken from")
     parser.add_argument("--seed", type=int, default=0,
                         help="with --dataset-catalog: the run's seed of the input transform's random draws (sizes, flips)")
@@ -235,6 +254,16 @@ def main(argv=None):
             check_color_jitter(getattr(cfg.INPUT, k) for k in JITTER_KEYS)
         except ValueError as e:
             parser.error(f"--color-jitter: {e}")
+    if args.crop_size is not None and args.scale_jitter is None:
+        parser.error("--crop-size is the canvas of --scale-jitter: give --scale-jitter LO HI too")
+    if args.scale_jitter is not None and not (args.raw_input or args.dataset_catalog):
+        parser.error("--scale-jitter acts in the device input transform: give --raw-input or --dataset-catalog (the float32 "
+                     "synthetic stream has no bytes to resample)")
+    if args.scale_jitter is not None:
+        try:
+            check_scale_jitter(args.scale_jitter, args.crop_size)
+        except ValueError as e:
+            parser.error(f"{'--crop-size' if str(e).startswith('crop_size') else '--scale-jitter'}: {e}")
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
         # The training process does almost no CPU math, but every multi-threaded host op (a staging memcpy, a reduction over a
@@ -257,7 +286,8 @@ def main(argv=None):
     train(cfg, args.local_rank, distributed, args.max_iter or cfg.SOLVER.MAX_ITER, ims_per_gpu,
           save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input,
           dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed, evaluate=args.evaluate,
-          skip_test=args.skip_test, boundary_ap=args.boundary_ap, lvis=args.lvis, color_jitter=args.color_jitter)
+          skip_test=args.skip_test, boundary_ap=args.boundary_ap, lvis=args.lvis, color_jitter=args.color_jitter,
+          scale_jitter=args.scale_jitter, crop_size=args.crop_size)
     if distributed:
         dist.destroy_process_group()
 
