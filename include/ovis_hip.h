@@ -442,6 +442,8 @@ int ovis_split_pair_f32(const float* src, long src_row_stride, void* dst_pair, l
  * g_f32 != NULL, also as dense fp32.  dy [rows, cols] f32 (row stride in elements); gate = the saved forward
  * output y, dense: its pair form (gate_is_pair != 0; only the hi halves are read) or fp32, or NULL (no gate:
  * a plain split).  threshold_backward of mb/modeling/backbone/resnet.py:323-344's relu_ calls.  cols % 32 == 0.
+ * The two gate forms agree for every positive NORMAL y; for 0 < y <= 2^-134 the pair form gates to zero, because hi
+ * rounds to 0, and the fp32 form passes.
  * g_pooled != NULL: [rows / pool_rows, cols] f32, the gradient of the mean over every pool_rows consecutive rows
  * (the 7x7 average pooling of FastRCNNPredictor.forward, roi_box_predictors.py:62-66, behind the res5 head) is
  * added on the fly, g = (dy + g_pooled[row / pool_rows] / pool_rows) * (y > 0); dy may then be NULL.

@@ -504,6 +504,11 @@ def test_stem_gemm_matches_convolution():
     hi, lo = _unpair(rows)
     cols = F.unfold(x, (7, 7), padding=3, stride=2).view(2, 3, 49, ho * wo).permute(0, 3, 2, 1).reshape(2 * ho * wo, 147)
     assert torch.equal(hi[:, :147], cols.to(torch.bfloat16)) and not hi[:, 147:].any() and not lo[:, 147:].any()
+    # both halves, bit for bit, against the host restatement of the split (tests/pair_layout_reference.py)
+    from tests import pair_layout_reference as R
+    want_hi, want_lo = R.split(cols.cpu().numpy())
+    for got, want in ((hi, want_hi), (lo, want_lo)):
+        assert (got[:, :147].contiguous().view(torch.int16).cpu().numpy() == want.view("int16")).all()
 
 
 def test_rpn_head_gemm_matches_convolutions():
