@@ -1678,6 +1678,60 @@ def color_jitter(data, desc, ops, params, max_in_hw=None, contrast=True):
     return out
 
 
+COPY_PASTE_MAX_IMAGES = _lib.OVIS_BOX_DECODE_MAX_IMAGES  # the per-image alphas travel as kernel arguments
+
+
+def copy_paste_masks(masks, num_own):
+    """Copy-paste, the mask half (``ovis_copy_paste_masks_u8``; include/ovis_hip.h states the rule).  masks uint8
+    [G_own + G_paste, h, w], the first ``num_own`` rows the image's own: they become ``mask & ~alpha`` IN PLACE.
+    -> (alpha uint8 [h, w]: the OR of the pasted rows, 0 / 1; stats int32 [num_own, 6] = (pixels before, pixels after, x1,
+    y1, x2, y2): the tight box of what is left, (0, 0, -1, -1) when nothing is).  Two launches on the current stream, no
+    atomics, nothing read back."""
+    _check_dev(masks, "masks", torch.uint8)
+    num_own = int(num_own)
+    if masks.dim() != 3 or not masks.is_contiguous() or not 0 <= num_own <= masks.shape[0]:
+        raise RuntimeError("copy_paste_masks: contiguous [G_own + G_paste, h, w] uint8 masks and 0 <= num_own <= G expected")
+    h, w = masks.shape[1], masks.shape[2]
+    alpha = torch.empty((h, w), dtype=torch.uint8, device=masks.device)
+    stats = torch.empty((num_own, 6), dtype=torch.int32, device=masks.device)
+    with _on(masks.device):
+        rc = _L.ovis_copy_paste_masks_u8(masks.data_ptr() if masks.shape[0] else 0, num_own, masks.shape[0] - num_own, h, w,
+                                         alpha.data_ptr(), stats.data_ptr() if num_own else 0, _stream())
+    _lib.check(rc, "copy_paste_masks")
+    return alpha, stats
+
+
+def copy_paste_images(batch, alphas, paste_src):
+    """Copy-paste, the pixel half (``ovis_copy_paste_images_f32``), IN PLACE on batch float32 [B, C, pad_h, pad_w]:
+    ``batch[i, c, y, x] = batch[paste_src[i], c, y, x]`` (its pre-paste bits) where ``alphas[i][y, x]`` is set.  alphas: per
+    image a uint8 [h, w] device tensor no larger than the canvas (zero outside its frame), or None where paste_src[i] is -1;
+    paste_src: B python ints.  At most COPY_PASTE_MAX_IMAGES images; one launch on the current stream.  -> batch."""
+    _check_dev(batch, "batch")
+    paste_src = [int(s) for s in paste_src]
+    b = batch.shape[0] if batch.dim() == 4 else -1
+    if batch.dim() != 4 or not batch.is_contiguous() or len(paste_src) != b or len(alphas) != b:
+        raise RuntimeError("copy_paste_images: contiguous [B, C, pad_h, pad_w] float32 batch, B alphas and B sources expected")
+    ptrs, hw = [], []
+    for a, s in zip(alphas, paste_src):
+        if s >= 0:
+            if a is None or not a.is_cuda or a.device != batch.device or a.dtype != torch.uint8 or a.dim() != 2 \
+                    or not a.is_contiguous():
+                raise RuntimeError("copy_paste_images: a contiguous [h, w] uint8 alpha on the batch's device for every image "
+                                   "with a source expected")
+            ptrs.append(a.data_ptr())
+            hw += [a.shape[0], a.shape[1]]
+        else:
+            ptrs.append(0)
+            hw += [0, 0]
+    if b:
+        with _on(batch.device):
+            rc = _L.ovis_copy_paste_images_f32(batch.data_ptr(), b, batch.shape[1], batch.shape[2], batch.shape[3],
+                                               (ctypes.c_void_p * b)(*ptrs), (ctypes.c_int32 * (2 * b))(*hw),
+                                               (ctypes.c_int32 * b)(*paste_src), _stream())
+        _lib.check(rc, "copy_paste_images")
+    return batch
+
+
 def weighted_ce_fwd_bwd(logits, labels, bg_weight, need_grad=True):
     """-> (loss scalar tensor, dlogits or None)"""
     if not logits.is_cuda:

@@ -19,6 +19,13 @@ Detectron2) is a third opt-in, ``build_transforms(..., scale_jitter=(lo, hi), cr
 --scale-jitter LO HI [--crop-size H W]).  ``host`` draws a scale in place of the size and a crop window behind the flips
 (``scale_crop_draws``; include/ovis_hip.h states the rule in full), crops the targets to the window and emits 11-column
 descriptors; ``device`` makes only the window's pixels (``_C.transform_images_window``).  Every batch is [B, 3, canvas].
+
+Copy-paste (the other half of Simple Copy-Paste, Ghiasi et al. 2021; this project's own rule, stated in include/ovis_hip.h and
+NOT compared with any other implementation's output) is a fourth opt-in on top of scale jitter,
+``build_transforms(..., copy_paste=P)`` (tools/train_net.py --copy-paste P).  ``host`` decides, behind every per-image draw,
+which image receives which instances of its neighbour in the batch (``copy_paste_draws``, ``paste_target``); calling the
+transform with a staged batch rasterises, covers and re-boxes the masks on the copy stream and composites the pixels in
+place on the training stream (``InputTransform.paste``: ``_C.copy_paste_masks`` / ``_C.copy_paste_images``).
 """
 import random
 
@@ -26,7 +33,8 @@ import numpy as np
 import torch
 
 from .. import _C
-from ..modeling.structures import ImageList, RleMasks, TensorHolder, raise_on_bad_rle
+from ..modeling.structures import BoxList, CopyPasteMasks, ImageList, PolygonMasks, RleMasks, TensorHolder, raise_on_bad_rle
+from .prefetch import copy_stream
 
 FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM = 0, 1
 
@@ -140,17 +148,74 @@ def scale_crop_draws(rng, out_hw, crop_size, target=None):
     return window, (crop_target(target, window) if target is not None else None)
 
 
+def check_copy_paste(p):
+    """P of copy-paste as a float in (0, 1]; anything else is a ValueError."""
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise ValueError(f"copy_paste = {p!r}: expected a probability in (0, 1]")
+    if not 0 < p <= 1:
+        raise ValueError(f"copy_paste = {p}: expected a probability in (0, 1]")
+    return p
+
+
+def copy_paste_draws(rng, p, counts):
+    """What is pasted where in a batch whose cropped targets hold ``counts[i]`` instances: for i = 0 .. B-1 in order the
+    source is j = (i + 1) % B; ``u = rng.random()``, image i receives a paste iff u < p; then one ``rng.random()`` per
+    instance of j, in order, an instance selected iff its draw is < 0.5.  -> per image (j, [selected rows of j]), or None
+    when it receives nothing (u >= p, a source without instances, no instance selected)."""
+    plan = []
+    for i in range(len(counts)):
+        j = (i + 1) % len(counts)
+        picked = []
+        if rng.random() < p:
+            picked = [g for g in range(counts[j]) if rng.random() < 0.5]
+        plan.append((j, picked) if picked else None)
+    return plan
+
+
+def _polygon_masks(target, i, role):
+    masks = target.get_field("masks") if target.has_field("masks") else None
+    if not isinstance(masks, PolygonMasks):
+        what = "RLE masks" if isinstance(masks, RleMasks) else ("no masks" if masks is None else type(masks).__name__)
+        name = f"image {i} of the batch" + (f" (image id {masks.image_id})" if isinstance(masks, RleMasks) else "")
+        raise ValueError(f"{name}, the {role} of a copy-paste, carries {what}: copy-paste needs polygon ground truth")
+    return masks
+
+
+def paste_target(dst, src, picked, i, j):
+    """The target of image i once rows ``picked`` of image j's target are pasted over it, both in the canvas frame (their
+    windows start at its origin): size the element-wise maximum of the two, boxes and labels cat(own, picked), the source's
+    boxes as they are; ``masks`` a ``CopyPasteMasks`` for the device half; every other field the destination's."""
+    own, pasted = _polygon_masks(dst, i, "destination"), _polygon_masks(src, j, "source")
+    size = (max(dst.size[0], src.size[0]), max(dst.size[1], src.size[1]))
+    rows = torch.tensor(picked, dtype=torch.int64)
+    out = BoxList(torch.cat([dst.bbox, src.bbox[rows]]), size)
+    for k, v in dst.extra_fields.items():
+        if k == "labels":
+            v = torch.cat([v, src.get_field("labels")[rows]])
+        elif k == "masks":
+            v = CopyPasteMasks(own, pasted[rows], size, j)
+        out.add_field(k, v)
+    return out
+
+
 class InputTransform:
     """``host(images, targets)`` in the loader worker, ``device(raw)`` on the training process' stream; calling the object
     with a staged batch ``(raw, targets, ...)`` applies the device half -- the form ``DevicePrefetcher(transform=)`` takes.
     ``color_jitter``: (brightness, contrast, saturation, hue) of ColorJitter, None or all zero for none.
     ``scale_jitter``: (lo, hi), the scale range of large-scale jitter on the canvas ``crop_size`` = (height, width), default
-    1024 x 1024; None for none -- then ``crop_size`` must be None too, and both halves are what they are without it."""
+    1024 x 1024; None for none -- then ``crop_size`` must be None too, and both halves are what they are without it.
+    ``copy_paste``: P in (0, 1], the probability that an image receives objects of its neighbour in the batch; needs
+    ``scale_jitter``; None for none -- then no draw, no launch and no field differs."""
 
     def __init__(self, min_size, max_size, flip_horizontal_prob, flip_vertical_prob, mean, std, to_bgr255, size_divisible=0,
-                 seed=0, color_jitter=None, scale_jitter=None, crop_size=None):
+                 seed=0, color_jitter=None, scale_jitter=None, crop_size=None, copy_paste=None):
         if scale_jitter is None and crop_size is not None:
             raise ValueError("crop_size is the canvas of scale_jitter: give scale_jitter too")
+        if copy_paste is not None and scale_jitter is None:
+            raise ValueError("copy_paste pastes at the same position of a fixed canvas: give scale_jitter too")
+        self.copy_paste = check_copy_paste(copy_paste) if copy_paste is not None else None
         self.scale_jitter, self.crop_size = check_scale_jitter(scale_jitter, crop_size) if scale_jitter is not None else (None, None)
         self.color_jitter = check_color_jitter(color_jitter) if color_jitter is not None else (0.0,) * 4
         if not any(self.color_jitter):
@@ -171,7 +236,10 @@ class InputTransform:
         jitter's when it is on -- ``jitter_draws``, then ``raw`` also holds ``jitter_ops`` / ``jitter_params`` [B, 4] -- the
         size, then one draw per flip), from ``rng`` or the transform's own seeded generator.  With ``scale_jitter`` the
         size draw is the scale's, the window's draws follow the flips (``scale_crop_draws``), the descriptors have 11
-        columns, ``image_sizes`` holds the windows' (win_h, win_w), ``pad_hw`` is the canvas and the targets are cropped."""
+        columns, ``image_sizes`` holds the windows' (win_h, win_w), ``pad_hw`` is the canvas and the targets are cropped.
+        With ``copy_paste``, a batch of at least two images and targets, the copy-paste draws follow ALL of those
+        (``copy_paste_draws``); ``raw["paste_src"]`` int32 [B] then holds every image's source or -1, and a pasted-into image
+        has its new frame in ``image_sizes`` and the target of ``paste_target``."""
         rng = rng or self.rng
         if len(images) == 0:
             raise ValueError("InputTransform.host: an empty batch has no padded size")
@@ -209,12 +277,22 @@ class InputTransform:
                 sizes.append((oh, ow))
             if targets is not None:
                 out_targets.append(t)
+        paste_src = None
+        if self.copy_paste is not None and targets is not None and len(images) >= 2:
+            plan = copy_paste_draws(rng, self.copy_paste, [len(t) for t in out_targets])
+            before = out_targets  # sources are the pre-paste targets: nothing is pasted onward
+            out_targets = [t if p is None else paste_target(t, before[p[0]], p[1], i, p[0])
+                           for i, (t, p) in enumerate(zip(before, plan))]
+            sizes = [s if p is None else (t.size[1], t.size[0]) for s, t, p in zip(sizes, out_targets, plan)]
+            paste_src = torch.tensor([-1 if p is None else p[0] for p in plan], dtype=torch.int32)
         pad_h, pad_w = self.crop_size or (max(s[0] for s in sizes), max(s[1] for s in sizes))
         if self.size_divisible > 0:  # image_list.py:54-61
             d = self.size_divisible
             pad_h, pad_w = -(-pad_h // d) * d, -(-pad_w // d) * d
         raw = {"data": torch.cat(chunks), "desc": torch.tensor(desc, dtype=torch.int32), "image_sizes": sizes,
                "pad_hw": (pad_h, pad_w), "max_in_hw": (max(d[1] for d in desc), max(d[2] for d in desc))}
+        if paste_src is not None:
+            raw["paste_src"] = paste_src
         if jitter:
             raw["jitter_ops"] = torch.tensor([ops for ops, _ in jitter], dtype=torch.int32)
             raw["jitter_params"] = torch.tensor([params for _, params in jitter], dtype=torch.float32)
@@ -259,10 +337,84 @@ class InputTransform:
             done.synchronize()
             raise_on_bad_rle(host, names)
 
+    def paste(self, images, targets):
+        """The device half of copy-paste for a staged batch: ``images`` the ImageList ``device`` made, ``targets`` the staged
+        BoxLists; every target whose ``masks`` is a ``CopyPasteMasks`` receives its source's objects.  -> the new targets.
+        The mask work -- rasterise own + pasted polygons at the new frame, alpha = OR of the pasted, own &= ~alpha, the
+        per-mask counts and tight boxes, the table's copy to pinned memory, and the few row gathers the host's decision
+        asks for -- runs on the copy stream (``prefetch.copy_stream``), which already orders the staged polygons' copies:
+        the host waits for an EVENT of that stream, never for the training stream and the step queued on it.  The training
+        stream waits for the same stream's last event before the pixels are composited in place on it."""
+        holders = [t.get_field("masks") if (t is not None and t.has_field("masks")) else None for t in targets]
+        todo = [i for i, m in enumerate(holders) if isinstance(m, CopyPasteMasks)]
+        if not todo:
+            return targets
+        batch = images.tensors
+        if not batch.is_cuda:
+            raise NotImplementedError("copy-paste is device code: MODEL.DEVICE cpu is not supported")
+        cur, side = torch.cuda.current_stream(batch.device), copy_stream(batch.device)
+        out, made = list(targets), []
+        with torch.cuda.stream(side):
+            masks, alphas, stats = {}, [None] * len(targets), []
+            for i in todo:
+                masks[i] = holders[i].polygons.convert_to_binarymask()  # uint8 [G_own + G_paste, h, w] at the new frame
+                alphas[i], table = _C.copy_paste_masks(masks[i], holders[i].num_own)
+                stats.append(table)
+            table = torch.cat(stats)
+            host = torch.empty(table.shape, dtype=torch.int32, pin_memory=True)
+            host.copy_(table, non_blocking=True)
+            read = torch.cuda.Event()
+            read.record(side)
+            read.synchronize()  # the only read-back
+            at = 0
+            for i in todo:
+                t, n_own, g = targets[i], holders[i].num_own, len(holders[i])
+                keep, tight = copy_paste_keep(host[at:at + n_own].tolist())
+                at += n_own
+                rows = keep + list(range(n_own, g))  # pasted instances always stay
+                bbox, labels, dense = t.bbox, t.get_field("labels"), masks[i]
+                if len(rows) != g:
+                    index = torch.tensor(rows, dtype=torch.int64).to(batch.device)
+                    bbox, labels, dense = bbox[index], labels[index], dense[index]
+                if tight:
+                    bbox = bbox.clone() if bbox is t.bbox else bbox
+                    where = torch.tensor([rows.index(k) for k in tight], dtype=torch.int64).to(batch.device)
+                    bbox[where] = torch.tensor([tight[k] for k in tight], dtype=torch.float32).to(batch.device)
+                new = BoxList(bbox, t.size)
+                for k, v in t.extra_fields.items():
+                    new.add_field(k, labels if k == "labels" else dense if k == "masks" else v)
+                out[i] = new
+                made += [bbox, labels, dense, alphas[i]]
+            done = torch.cuda.Event()
+            done.record(side)
+        for t in made:  # allocated on the copy stream, read by the step
+            t.record_stream(cur)
+        cur.wait_event(done)
+        _C.copy_paste_images(batch, alphas, [holders[i].source if i in masks else -1 for i in range(len(targets))])
+        return out
+
     def __call__(self, batch):
         if len(batch) > 1:
             self.decode_masks(batch[1])
-        return (self.device(batch[0]),) + tuple(batch[1:])
+        images = self.device(batch[0])
+        if "paste_src" in batch[0]:
+            return (images, self.paste(images, batch[1])) + tuple(batch[2:])
+        return (images,) + tuple(batch[1:])
+
+
+def copy_paste_keep(stats):
+    """The host's decision over the table of ``_C.copy_paste_masks``: rows (pixels before, pixels after, x1, y1, x2, y2) of
+    an image's own instances.  An instance whose count did not change is untouched: it stays with its annotation box, even
+    at a count of 0.  A touched one takes the tight box and stays iff x2 > x1 and y2 > y1 -- the test of
+    ``clip_to_image(remove_empty=True)``, no new threshold.  -> (the rows kept, ascending; {kept touched row: its box})."""
+    keep, tight = [], {}
+    for g, (before, after, x1, y1, x2, y2) in enumerate(stats):
+        if after == before:
+            keep.append(g)
+        elif x2 > x1 and y2 > y1:
+            keep.append(g)
+            tight[g] = [float(x1), float(y1), float(x2), float(y2)]
+    return keep, tight
 
 
 class ViewBatch(TensorHolder):
@@ -354,15 +506,18 @@ def view_plan(cfg):
     return plan
 
 
-def build_transforms(cfg, is_train=True, seed=0, color_jitter=False, scale_jitter=None, crop_size=None):
+def build_transforms(cfg, is_train=True, seed=0, color_jitter=False, scale_jitter=None, crop_size=None, copy_paste=None):
     """build.py:5-46 for this package's split transform; the evaluation transform of TEST.BBOX_AUG.ENABLED makes every
     view (``ViewTransform``).  ``color_jitter=True`` honours INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE in the training
     transform; without the switch a non-zero key raises, and evaluation transforms never jitter.  ``scale_jitter`` =
     (lo, hi) with ``crop_size`` = (height, width): large-scale jitter in the training transform (INPUT.MIN_SIZE_TRAIN /
-    MAX_SIZE_TRAIN are then not read); evaluation transforms and ``ViewTransform`` never scale-jitter."""
+    MAX_SIZE_TRAIN are then not read); evaluation transforms and ``ViewTransform`` never scale-jitter.  ``copy_paste`` = P
+    in (0, 1], with ``scale_jitter``: copy-paste between the images of a training batch; evaluation transforms never paste."""
     jitter = None
     if scale_jitter is None and crop_size is not None:
         raise ValueError("crop_size is the canvas of scale_jitter: give scale_jitter too")
+    if copy_paste is not None and scale_jitter is None:
+        raise ValueError("copy_paste pastes at the same position of a fixed canvas: give scale_jitter too")
     if is_train:
         min_size, max_size = cfg.INPUT.MIN_SIZE_TRAIN, cfg.INPUT.MAX_SIZE_TRAIN
         flip_h, flip_v = cfg.INPUT.HORIZONTAL_FLIP_PROB_TRAIN, cfg.INPUT.VERTICAL_FLIP_PROB_TRAIN
@@ -378,7 +533,7 @@ def build_transforms(cfg, is_train=True, seed=0, color_jitter=False, scale_jitte
                                  cfg.DATALOADER.SIZE_DIVISIBILITY)
         min_size, max_size = cfg.INPUT.MIN_SIZE_TEST, cfg.INPUT.MAX_SIZE_TEST
         flip_h = flip_v = 0.0
-        scale_jitter = crop_size = None
+        scale_jitter = crop_size = copy_paste = None
     return InputTransform(min_size, max_size, flip_h, flip_v, cfg.INPUT.PIXEL_MEAN, cfg.INPUT.PIXEL_STD, cfg.INPUT.TO_BGR255,
                           cfg.DATALOADER.SIZE_DIVISIBILITY, seed=seed, color_jitter=jitter, scale_jitter=scale_jitter,
-                          crop_size=crop_size)
+                          crop_size=crop_size, copy_paste=copy_paste)

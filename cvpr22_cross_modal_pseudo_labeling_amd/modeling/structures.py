@@ -5,7 +5,8 @@ structures/boxlist_ops.py:9-129 (``boxlist_nms / remove_small_boxes / boxlist_io
 and structures/image_list.py:7-72, reduced to what the training hot path touches: boxes are always
 ``xyxy`` float32 tensors on the device, fields are plain tensors (or python objects), and instance
 masks are a field in one of four forms: a dense ``[G, H, W]`` tensor, or ``PolygonMasks`` / ``RleMasks`` /
-``PastedMasks``, which stay lazy and answer ``project`` for the mask head's targets.
+``PastedMasks``, which stay lazy and answer ``project`` for the mask head's targets (``CopyPasteMasks`` lives only between
+the two halves of the input transform, which turns it into the dense form).
 
 Every structure that carries tensors is a ``TensorHolder``: it declares the attributes that hold them, and
 ``map_tensors`` / ``to`` / ``device_tensors`` follow from that declaration (input staging: data/prefetch.py, stream
@@ -334,6 +335,40 @@ class PolygonMasks(TensorHolder):
             from .. import _cpu
             return _cpu.polygons_to_masks(self.coords, self.polygon_start, self.instance_start, self.size)
         return _C.polygons_to_masks(self.coords, self.polygon_start, self.instance_start, self.size)
+
+
+class CopyPasteMasks(TensorHolder):
+    """The ground-truth masks of an image that RECEIVES a copy-paste (data/transforms.py; include/ovis_hip.h states the
+    rule), between the two halves of the input transform: ``polygons`` -- a ``PolygonMasks`` in the image's new frame
+    holding its own instances first and the pasted ones behind them -- and ``num_own``, how many are its own; ``source``:
+    the batch index the pasted ones come from.  The host half builds it, staging moves it like every holder, and the device
+    half replaces it with the dense uint8 [G', h, w] masks that are left once the pasted objects cover the own ones.  It is
+    never a mask target's source and has no geometry of its own: nothing resizes, flips or crops behind the host half."""
+
+    _TENSORS = ("polygons",)
+
+    def __init__(self, own, pasted, size, source):
+        self.size, self.num_own, self.source = tuple(size), len(own), int(source)
+        self.polygons = PolygonMasks(own.instances() + pasted.instances(), self.size)
+
+    def __len__(self):
+        return len(self.polygons)
+
+    def _no(self, what):
+        raise NotImplementedError(f"CopyPasteMasks.{what}: the holder lives between the host and the device half of the input "
+                                  "transform; the device half turns it into dense masks (InputTransform.__call__)")
+
+    def resize(self, size):
+        self._no("resize")
+
+    def transpose(self, method):
+        self._no("transpose")
+
+    def crop(self, box):
+        self._no("crop")
+
+    def project(self, gt_index, boxes, resolution):
+        self._no("project")
 
 
 class RleMasks(TensorHolder):

@@ -950,6 +950,52 @@ int ovis_color_jitter_u8(const uint8_t* data, long data_bytes, const int32_t* de
                          int batch, int max_in_h, int max_in_w, void* workspace, size_t workspace_bytes, uint8_t* out,
                          void* stream);
 
+/* Copy-paste augmentation behind scale jitter (the other half of "Simple Copy-Paste", Ghiasi et al., CVPR 2021): objects of
+ * one image of a batch are pasted, at the same canvas position, over another.  THE RULE below is this project's own
+ * statement; it was NOT compared with any other implementation's output.
+ * Parameter: P in (0, 1] (tools/train_net.py --copy-paste P; needs --scale-jitter, whose fixed canvas gives "the same
+ * position in the other image" a meaning and bounds the memory; polygon ground truth only).
+ * Host half, on Python's random.Random in the loader worker (data/transforms.py::InputTransform.host), AFTER every image of
+ * the batch has made its own draws and has its cropped target -- those draws are exactly a run's without the flag:
+ *   - a batch of B < 2 images, or one without targets, makes no copy-paste draw and is handed on unchanged.
+ *   - for i = 0 .. B-1 in order the source is j = (i + 1) % B: u = rng.random(); image i receives a paste iff u < P.  Then
+ *     one rng.random() per instance of source j's cropped target, in order; an instance is selected iff its draw is < 0.5.
+ *     A source without instances, or no selected instance: no paste for i.  Sources are the PRE-paste images and targets.
+ *   - a pasted-into image i: its frame is (max(win_h_i, win_h_j), max(win_w_i, win_w_j)) -- both windows start at the canvas
+ *     origin --, its boxes and labels are cat(own rows, selected source rows), the source's boxes as they are; every other
+ *     field stays i's.  paste_src [B] int32 holds j, or -1.
+ * Device half, per image with paste_src >= 0:
+ *   1. own and pasted polygons rasterised at the new frame (ovis_polygons_to_masks_u8): uint8 [G_own + G_paste, h, w].
+ *   2. alpha = OR of the pasted masks, 0 / 1; every own mask becomes mask & ~alpha, in place.
+ *   3. per own mask the int32 row (pixels before, pixels after, x1, y1, x2, y2): the tight box of what is left in pixel
+ *      indices (x2 = max x: the TO_REMOVE = 1 convention); an empty remainder is the box (0, 0, -1, -1).
+ *   4. the table is read back (the only read-back).  An own instance whose count did not change is untouched: it keeps its
+ *      annotation box and stays, even at a count of 0.  A touched one takes the tight box as float32 and stays iff x2 > x1
+ *      and y2 > y1 (clip_to_image(remove_empty=True)'s test; no new threshold).  Pasted instances always stay, with their
+ *      annotation boxes.  The target's masks are the dense uint8 [G', h, w] rows kept, own first.
+ *   5. pixels, on the float batch of ovis_transform_images_window_u8: out[i, c, y, x] = alpha_i[y, x] ? in[paste_src[i], c,
+ *      y, x] : in[i, c, y, x], bit-wise, the right-hand side pre-paste for every i.
+ *
+ * ovis_copy_paste_masks_u8: steps 2 and 3.  masks [num_own + num_paste, height, width] uint8, own first; a byte that is not
+ * zero is a set pixel.  alpha_out [height, width] uint8: every byte written, 0 / 1 (all 0 when num_paste == 0; written when
+ * num_own == 0 too).  Own masks in place: a covered byte becomes 0, every other byte stays.  stats_out [num_own, 6] int32 as
+ * in 3, may be NULL when num_own == 0.  Two launches (one when num_own == 0), one workgroup per own mask, no atomics: the
+ * same words on every call.  Enqueue only.  height or width < 1, a negative count, a NULL pointer that is needed:
+ * OVIS_EINVAL; height * width > 2^30: OVIS_ERANGE.
+ *
+ * ovis_copy_paste_images_f32: step 5, IN PLACE on batch [num_images, channels, pad_h, pad_w] f32.  HOST arrays of
+ * num_images entries: paste_src (-1: the image receives nothing and its two other entries are not read), alpha_ptrs (DEVICE
+ * pointers: the image's alpha) and alpha_hw [num_images, 2] = its alpha's (height, width), at most the canvas'; outside its
+ * frame an alpha is 0.  One thread owns a pixel position across the whole batch and loads every pre-paste value before it
+ * stores, so swaps and cycles are exact.  One launch, none when no image has a source.  At most
+ * OVIS_BOX_DECODE_MAX_IMAGES images (they travel as kernel arguments): above, OVIS_ERANGE and nothing is written.  A
+ * source outside [-1, num_images), a frame outside the canvas, a NULL pointer: OVIS_EINVAL. */
+int ovis_copy_paste_masks_u8(uint8_t* masks, int num_own, int num_paste, int height, int width, uint8_t* alpha_out,
+                             int32_t* stats_out, void* stream);
+int ovis_copy_paste_images_f32(float* batch, int num_images, int channels, int pad_h, int pad_w,
+                               const uint8_t* const* alpha_ptrs, const int32_t* alpha_hw, const int32_t* paste_src,
+                               void* stream);
+
 /* Deformable convolution BACKWARD on NHWC rows (csrc/deform_conv_rows.hip; mb/csrc/cuda/deform_conv_cuda.cu:271-497,
  * 580-694): rows m = (image, h_out, w_out), k = (tap, channel), the layout of ovis_deform_conv_implicit_f32.
  * ovis_deform_im2col_pair_rows_f32: the sampled (x mask) rows col[m, (t, c)] written ONCE, in pair layout (row stride

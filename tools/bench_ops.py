@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, transform_window, color_jitter, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
+Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, transform_window, color_jitter, copy_paste, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -403,6 +403,48 @@ def main():
             res.append({"op": f"color_jitter ({'memset + 2 launches' if contrast else '1 launch'}): {name}",
                         "shape": "2 x 480x640 uint8", "ms": ms, "bytes_MB": nbytes / 1e6, "GBps": nbytes / ms / 1e6,
                         "frac_hbm_bound": nbytes / ms / 1e6 / HBM_PEAK_GBS, "outputs_equal": equal})
+    if "copy_paste" in ops:  # opt-in: copy-paste on 2 x 1024 x 1024, 8 own + 4 pasted instances per image, the rasterise included
+        import math
+
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.structures import PolygonMasks
+
+        b_, canvas, n_own, n_paste = 2, 1024, 8, 4
+        rs = torch.rand(b_, n_own + n_paste, 4, generator=g)
+        polygons = []
+        for i in range(b_):  # hexagons of 100..400 pixels across, spread over the canvas
+            inst = []
+            for cx, cy, r, _ in rs[i].tolist():
+                cx, cy, r = 100 + cx * 824, 100 + cy * 824, 50 + r * 150
+                inst.append([[v for k in range(6) for v in (cx + r * math.cos(k * math.pi / 3), cy + r * math.sin(k * math.pi / 3))]])
+            polygons.append(PolygonMasks(inst, (canvas, canvas)).to(dev))
+        batch = torch.randn(b_, 3, canvas, canvas, generator=g).to(dev)
+        paste_src = [1, 0]
+
+        def masks_only():
+            out = []
+            for p in polygons:
+                m = p.convert_to_binarymask()
+                out.append((m,) + _C.copy_paste_masks(m, n_own))
+            return out
+
+        def whole():
+            made = masks_only()
+            _C.copy_paste_images(batch, [a for _, a, _ in made], paste_src)
+            return made
+
+        ms_masks, ms = timeit(masks_only, args.iters), timeit(whole, args.iters)
+        ms_raster = timeit(lambda: [p.convert_to_binarymask() for p in polygons], args.iters)
+        made = whole()
+        covered = sum(int(a.sum()) for _, a, _ in made)
+        plane = canvas * canvas
+        # the copy-paste kernels' own traffic: alpha (pasted read, alpha written), own masks (read, alpha read; stores only where
+        # covered, not counted), pixels (alpha read; pasted values read and written)
+        nbytes = b_ * (n_paste * plane + plane + n_own * 2 * plane + plane) + covered * 3 * 4 * 2
+        res.append({"op": "copy_paste (per image: rasterise + 2 launches; + 1 launch for the batch)",
+                    "shape": f"{b_} x {canvas}x{canvas}, {n_own} own + {n_paste} pasted, {covered} pasted pixels", "ms": ms,
+                    "rasterise_ms": ms_raster, "masks_ms": ms_masks - ms_raster, "images_ms": ms - ms_masks,
+                    "bytes_MB": nbytes / 1e6, "GBps_without_rasterise": nbytes / (ms - ms_raster) / 1e6,
+                    "frac_hbm_without_rasterise": nbytes / (ms - ms_raster) / 1e6 / HBM_PEAK_GBS})
     if "render" in ops:  # opt-in: the prediction compositor, 100 fill layers on one 480 x 640 image, M = 14
         k_, m_, h_, w_ = 100, 14, 480, 640
         probs = torch.rand(k_, m_, m_, generator=g).to(dev)

@@ -1,7 +1,7 @@
 """Training entry point with the reference's command line (tools/train_net.py:162-234):
 
     python -m torch.distributed.run --nproc-per-node N tools/train_net.py --config-file CFG [--dataset-catalog FILE]
-        [--color-jitter] [--evaluate] [--boundary-ap] [--lvis] [--skip-test] KEY VALUE ...
+        [--color-jitter] [--scale-jitter LO HI [--crop-size H W] [--copy-paste P]] [--evaluate] [--boundary-ap] [--lvis] [--skip-test] KEY VALUE ...
 
 One process per GPU (RCCL via torch.distributed, env:// rendezvous), config = defaults <- yaml <- trailing overrides,
 frozen before use.  Without ``--dataset-catalog`` the data stream is the synthetic COCO-shaped generator
@@ -11,6 +11,9 @@ OUTPUT_DIR resume and SOLVER.CHECKPOINT_PERIOD behave as in the reference (utils
 resumed from whenever OUTPUT_DIR is set; ``--no-checkpoints`` opts out).  ``--color-jitter`` (with ``--raw-input`` or
 ``--dataset-catalog``) makes the training transform honour INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE: the reference's
 ColorJitter in front of the resize, drawn in the loader and run on the device (data/transforms.py); off by default.
+``--copy-paste P`` (with ``--scale-jitter``, MODEL.MASK_ON and MODEL.DEVICE cuda; polygon ground truth) pastes, with
+probability P per image, a random half of the neighbouring image's instances over it at the same canvas position: decided in
+the loader, masks and pixels composited on the device (include/ovis_hip.h states the rule; off by default).
 
 ``--evaluate`` (with ``--dataset-catalog``, OUTPUT_DIR and MODEL.DEVICE cuda) is the reference's evaluation while training:
 behind every SOLVER.TEST_PERIOD-th iteration -- counted over the whole run, after that iteration's checkpoint -- every
@@ -58,26 +61,30 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (LVIS_VOCAB, R
                                                                        SyntheticBatches, calibrate_stem_bn, make_batch,
                                                                        make_embeddings)
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import (JITTER_KEYS, build_transforms, check_color_jitter,  # noqa: E402
-                                                                        check_scale_jitter)
+                                                                        check_copy_paste, check_scale_jitter)
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, evaluation, solver, trainer  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
 
 def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter=0, max_iter=None, seed=0, color_jitter=False,
-                     scale_jitter=None, crop_size=None):
+                     scale_jitter=None, crop_size=None, copy_paste=None):
     """-> (loader of host batches, the input transform or None).  ``dataset`` (``--dataset-catalog``): the reference's
     batching over the user's files (data/build.py), counted from ``start_iter``, its size and flip draws seeded by ``seed``;
     otherwise the endless synthetic streams.  ``color_jitter``: the transform honours INPUT.BRIGHTNESS / CONTRAST /
     SATURATION / HUE (data/transforms.py).  ``scale_jitter`` = (lo, hi), ``crop_size`` = (height, width): large-scale jitter
-    on a fixed canvas, behind the colour jitter when both are on."""
+    on a fixed canvas, behind the colour jitter when both are on.  ``copy_paste`` = P: copy-paste between the images of a
+    batch on that canvas (it needs ``scale_jitter``)."""
     if color_jitter and not (raw_input or dataset is not None):
         raise ValueError("color_jitter acts on raw uint8 images: it needs raw_input or a dataset")
     if scale_jitter is not None and not (raw_input or dataset is not None):
         raise ValueError("scale_jitter acts in the device input transform: it needs raw_input or a dataset")
     if crop_size is not None and scale_jitter is None:
         raise ValueError("crop_size is the canvas of scale_jitter: give scale_jitter too")
-    transform = (build_transforms(cfg, is_train=True, color_jitter=color_jitter, scale_jitter=scale_jitter, crop_size=crop_size)
+    if copy_paste is not None and scale_jitter is None:
+        raise ValueError("copy_paste pastes at the same position of a fixed canvas: give scale_jitter too")
+    transform = (build_transforms(cfg, is_train=True, color_jitter=color_jitter, scale_jitter=scale_jitter, crop_size=crop_size,
+                                  copy_paste=copy_paste)
                  if (raw_input or dataset is not None) else None)
     if dataset is not None:
         return make_data_loader(cfg, dataset, transform, True, comm.get_rank(), comm.get_world_size(), start_iter=start_iter,
@@ -93,14 +100,18 @@ def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter
 
 def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False, dataset_catalog=None,
           data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False, lvis=False, color_jitter=False,
-          scale_jitter=None, crop_size=None):
+          scale_jitter=None, crop_size=None, copy_paste=None):
     """``evaluate``: score every DATASETS.TEST set behind every SOLVER.TEST_PERIOD-th iteration
     (engine/evaluation.py::evaluate_in_training) and, unless ``skip_test``, run the final test behind the last one
     (``evaluation.run_datasets``: predictions.pth and coco_results.json under OUTPUT_DIR/inference/<name>/).
     ``boundary_ap``: both also score the ``boundary`` task (engine/coco_eval.py: Boundary AP), behind ``segm``.  ``lvis``:
     both score under LVIS-style federated rules and write ``lvis_results*.json`` instead.  ``color_jitter``: the raw input
     path jitters the training images as INPUT.BRIGHTNESS / CONTRAST / SATURATION / HUE say.  ``scale_jitter`` / ``crop_size``:
-    it trains on large-scale-jittered crops of a fixed canvas; the periodic and the final test use the plain test transform."""
+    it trains on large-scale-jittered crops of a fixed canvas; the periodic and the final test use the plain test transform.
+    ``copy_paste`` = P in (0, 1]: copy-paste between the images of a training batch (with ``scale_jitter``, MODEL.MASK_ON and
+    MODEL.DEVICE cuda)."""
+    if copy_paste is not None and (cfg.MODEL.DEVICE != "cuda" or not cfg.MODEL.MASK_ON):
+        raise ValueError("train(copy_paste=P) composites masks on the HIP device: it needs MODEL.DEVICE cuda and MODEL.MASK_ON True")
     if lvis and not evaluate:
         raise ValueError("train(lvis=True) changes the rules of what evaluate=True scores")
     if boundary_ap and not evaluate:
@@ -147,7 +158,7 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
     # --raw-input: the workers hand over raw uint8 images at their own sizes with polygon ground truth and only decide the
     # size and the flips (data/transforms.py); resize, flip, normalisation and padding run on the device behind the copy
     loader, transform = make_data_source(cfg, ims_per_gpu, raw_input, dataset, start_iter, max_iter, seed, color_jitter,
-                                         scale_jitter, crop_size)
+                                         scale_jitter, crop_size, copy_paste)
     data = DevicePrefetcher(loader, device, depth=2, transform=transform)
     if not cfg.MODEL.WEIGHT and not checkpointer.has_checkpoint():  # random init only: give the frozen BN usable statistics
         images, _ = make_batch(1, device=device, seed=7)
@@ -217,6 +228,13 @@ def main(argv=None):
                              "crops an image of the canvas' aspect ratio)")
     parser.add_argument("--crop-size", type=int, nargs=2, default=None, metavar=("H", "W"),
                         help="with --scale-jitter: the canvas every training image is cropped or padded to (default 1024 1024)")
+    parser.add_argument("--copy-paste", type=float, default=None, metavar="P",
+                        help="with --scale-jitter, MODEL.MASK_ON True and MODEL.DEVICE cuda: copy-paste augmentation between the "
+                             "images of a batch -- image i receives, with probability P in (0, 1], each instance of image "
+                             "(i + 1) %% B with probability 0.5, pasted at the same canvas position; covered masks lose the "
+                             "occluded part, their boxes are recomputed, and instances left without extent are dropped.  Polygon "
+                             "ground truth only.  Captions are carried unchanged: a pasted object is not named by the "
+                             "destination's caption, and a covered one may still be named")
     parser.add_argument("--data-dir", default="", help="where the catalog's relative paths are taken from")
     parser.add_argument("--seed", type=int, default=0,
                         help="with --dataset-catalog: the run's seed of the input transform's random draws (sizes, flips)")
@@ -264,6 +282,18 @@ def main(argv=None):
             check_scale_jitter(args.scale_jitter, args.crop_size)
         except ValueError as e:
             parser.error(f"{'--crop-size' if str(e).startswith('crop_size') else '--scale-jitter'}: {e}")
+    if args.copy_paste is not None:
+        if args.scale_jitter is None:
+            parser.error("--copy-paste pastes at the same position of the fixed canvas of --scale-jitter: give --scale-jitter "
+                         "LO HI too")
+        try:
+            check_copy_paste(args.copy_paste)
+        except ValueError as e:
+            parser.error(f"--copy-paste: {e}")
+        if cfg.MODEL.DEVICE != "cuda":
+            parser.error("--copy-paste composites masks and pixels on the HIP device: set MODEL.DEVICE cuda")
+        if not cfg.MODEL.MASK_ON:
+            parser.error("--copy-paste edits the ground-truth masks: set MODEL.MASK_ON True")
     if cfg.MODEL.DEVICE == "cuda":
         torch.cuda.set_device(args.local_rank)
         # The training process does almost no CPU math, but every multi-threaded host op (a staging memcpy, a reduction over a
@@ -287,7 +317,7 @@ def main(argv=None):
           save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input,
           dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed, evaluate=args.evaluate,
           skip_test=args.skip_test, boundary_ap=args.boundary_ap, lvis=args.lvis, color_jitter=args.color_jitter,
-          scale_jitter=args.scale_jitter, crop_size=args.crop_size)
+          scale_jitter=args.scale_jitter, crop_size=args.crop_size, copy_paste=args.copy_paste)
     if distributed:
         dist.destroy_process_group()
 
