@@ -2066,6 +2066,28 @@ def sgd_momentum_multi(items, blocks, lr, weight_decay, momentum, apply_weight_d
     _lib.check(rc, "sgd_momentum_multi")
 
 
+def sgd_momentum_ema_multi(items, blocks, lr, weight_decay, momentum, apply_weight_decay, ema_weight):
+    """``sgd_momentum_multi`` with the weight average moved in the same pass: ``items`` = uint8 device table of 40-byte
+    records {p, g, buf, ema, n}; behind the SGD update of an element, ema += (p_new - ema) * ``ema_weight`` (three fp32
+    roundings; the rule is in include/ovis_hip.h)."""
+    if not (items.is_cuda and blocks.is_cuda):
+        raise RuntimeError("sgd_momentum_ema_multi: HIP device tensors only")
+    with _on(items.device):
+        rc = _L.ovis_sgd_momentum_ema_multi_f32(items.data_ptr(), blocks.data_ptr(), blocks.size(0), lr, weight_decay,
+                                                momentum, int(bool(apply_weight_decay)), ema_weight, _stream())
+    _lib.check(rc, "sgd_momentum_ema_multi")
+
+
+def swap_multi(items, blocks):
+    """One launch that exchanges a[i] and b[i] bit-wise, in place, over the tensor pairs of ``items`` (uint8 device table of
+    24-byte records {a, b, n}, n in 4-byte elements); ``blocks`` as for ``sgd_momentum_multi``."""
+    if not (items.is_cuda and blocks.is_cuda):
+        raise RuntimeError("swap_multi: HIP device tensors only")
+    with _on(items.device):
+        rc = _L.ovis_swap_multi_f32(items.data_ptr(), blocks.data_ptr(), blocks.size(0), _stream())
+    _lib.check(rc, "swap_multi")
+
+
 # ---- COCO scoring (evaluation/coco/coco_eval.py:315-333 -> pycocotools' COCOeval; csrc/coco_eval.hip) -------------------
 class CocoProblems:
     """The (image, category) problems of a chunk of images, the table of include/ovis_hip.h: ``table`` HOST int64 [P, 8] =

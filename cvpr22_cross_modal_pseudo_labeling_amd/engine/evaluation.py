@@ -82,8 +82,8 @@ def save_evaluation(dataset, predictions, folder, iou_types, device, logger, rec
     return results
 
 
-def run_rpn_recall(cfg, model, catalog, device, logger=None):
-    """Backbone + RPN alone over every DATASETS.TEST name (``model.propose``): the MODEL.RPN.POST_NMS_TOP_N_TEST proposals
+def run_rpn_recall(cfg, model, catalog, device, logger=None, folder="inference"):
+    """(``folder``: ``inference_ema`` when the model holds the averaged weights, see ``run_datasets``.)Backbone + RPN alone over every DATASETS.TEST name (``model.propose``): the MODEL.RPN.POST_NMS_TOP_N_TEST proposals
     of every image, gathered like detections and saved as ``<OUTPUT_DIR>/inference/<name>/proposals.pth``, and on rank 0
     their box-proposal recall by ``objectness`` (engine/proposal_recall.py) as a ``rpn_proposal`` task in the log and in
     ``rpn_recall.json`` -> {name: the numbers (rank 0) or None}."""
@@ -96,7 +96,7 @@ def run_rpn_recall(cfg, model, catalog, device, logger=None):
         dataset = build_dataset(cfg, name, catalog)
         loader = make_data_loader(cfg, dataset, transform, False, comm.get_rank(), comm.get_world_size())
         batches = DevicePrefetcher(loader, device, depth=2, transform=transform)
-        out = os.path.join(cfg.OUTPUT_DIR, "inference", name)
+        out = os.path.join(cfg.OUTPUT_DIR, folder, name)
         try:
             proposals = inference.inference(model, batches, name, device, out, logger=logger, forward=model.propose,
                                             file_name="proposals.pth")
@@ -122,8 +122,10 @@ def scored_iou_types(cfg, boundary_ap=False):
 
 def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vis_threshold=0.5, evaluate=False,
                  export_results=False, recall=False, vote_thresh=None, average_masks=False, boundary_ap=False, lvis=False,
-                 error_analysis=False):
-    """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}.  ``vote_thresh`` /
+                 error_analysis=False, folder="inference"):
+    """The detections of every DATASETS.TEST name -> {name: list of BoxLists (rank 0) or None}.  ``folder``: everything is
+    written under OUTPUT_DIR/<folder>/<name>/ -- ``inference`` always means the raw weights, ``inference_ema`` the averaged
+    ones (engine/ema.py; the caller has put them into the model).  ``vote_thresh`` /
     ``average_masks``: box voting and view-averaged masks of multi-scale / flip testing (engine/bbox_aug.py);
     ``boundary_ap``: with ``evaluate``, a ``boundary`` task behind ``segm`` (engine/coco_eval.py: Boundary AP); ``lvis``: with
     ``evaluate``, LVIS-style federated rules and ``lvis_results.json`` (``save_evaluation``); ``error_analysis``: with
@@ -139,7 +141,7 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
         dataset = build_dataset(cfg, name, catalog)
         loader = make_data_loader(cfg, dataset, transform, False, comm.get_rank(), comm.get_world_size())
         batches = DevicePrefetcher(loader, device, depth=2, transform=transform)
-        out = os.path.join(cfg.OUTPUT_DIR, "inference", name) if cfg.OUTPUT_DIR else None
+        out = os.path.join(cfg.OUTPUT_DIR, folder, name) if cfg.OUTPUT_DIR else None
         try:  # the zero-shot heads classify against THIS dataset's class embeddings
             results[name] = inference.inference(model, batches, name, device, out,
                                                 class_embeddings=getattr(dataset, "class_emb_mtx", None), logger=logger,
@@ -163,8 +165,9 @@ def run_datasets(cfg, model, catalog, device, logger=None, visualize_count=0, vi
 
 
 def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_embeddings, logger=None, boundary_ap=False,
-                         lvis=False):
-    """The SOLVER.TEST_PERIOD evaluation of a live training process, behind iteration ``iteration`` (trainer.py:174-203):
+                         lvis=False, folder="inference"):
+    """(``folder``: the results go under OUTPUT_DIR/<folder>/<name>/ -- ``inference_ema`` when the caller has put the averaged
+    weights into the model, engine/ema.py::ModelEma.applied.)  The SOLVER.TEST_PERIOD evaluation of a live training process, behind iteration ``iteration`` (trainer.py:174-203):
     every DATASETS.TEST name through the model's evaluation pass on this rank's shard, scored where it was predicted
     (``coco_eval.evaluate_coco_sharded``: AP keys of ``bbox``, of ``segm`` when MODEL.MASK_ON, and of ``boundary`` behind it
     when ``boundary_ap``) -> {name: the numbers (rank 0) or None}.  Rank 0 logs the table under the iteration and writes
@@ -209,7 +212,7 @@ def evaluate_in_training(cfg, model, catalog, device, iteration, train_class_emb
                         len(predictions), predicted - start, scored - predicted)
             if results[name] is not None:
                 logger.info("iteration %d, %s:%s", iteration, name, coco_eval.format_results(results[name]))
-                out = os.path.join(cfg.OUTPUT_DIR, "inference", name)
+                out = os.path.join(cfg.OUTPUT_DIR, folder, name)
                 os.makedirs(out, exist_ok=True)
                 with open(os.path.join(out, results_file_name(lvis, iteration)), "w") as f:
                     json.dump(results[name], f, indent=1)

@@ -34,26 +34,52 @@ class GroupFusedSGD(torch.optim.SGD):
     once and rebuilt only when a pointer changes; gradients are stable views of the reducer's flat buckets).  Otherwise
     (host tensors, other dtypes) six multi-tensor ops with per-tensor scalars -- the same operation sequence, so the two
     paths give the same bits.  Falls back to the stock step for closures, dampening, nesterov, maximize or sparse
-    gradients."""
+    gradients.
+    ``ema`` (an ``engine/ema.py::ModelEma``, default None: nothing below exists): every route through ``step`` that updates
+    parameters also moves their averages, ema += (p_new - ema) * w with w = ``ema.weight()`` (the rule: include/ovis_hip.h),
+    and counts one update per step.  The native route does both in the one launch (``_C.sgd_momentum_ema_multi``: the tables
+    gain the EMA pointers), the others in three more multi-tensor ops -- the same bits."""
 
     native = True  # False: always the multi-tensor form (tests compare the two)
+    ema = None
 
     @torch.no_grad()
     def step(self, closure=None):
         from ..layers.pair_bottleneck import note_weights_written
         note_weights_written()  # the native launch writes parameters through raw pointers: no version counter moves
+        if self.ema is None:
+            return self._step(closure, None)
+        loss = self._step(closure, self.ema.weight())
+        self.ema.num_updates += 1
+        return loss
+
+    def _ema_foreach(self, params, w):
+        """The multi-tensor twin of the EMA lines of the fused launch, over the parameters a step has just updated."""
+        if params:
+            emas = [self.ema.tensor_of(p) for p in params]
+            diff = torch._foreach_sub(params, emas)
+            torch._foreach_mul_(diff, w)
+            torch._foreach_add_(emas, diff)
+
+    def _step_stock(self, closure, w):
+        loss = super().step(closure)
+        if w is not None:
+            self._ema_foreach([p for g in self.param_groups for p in g["params"] if p.grad is not None], w)
+        return loss
+
+    def _step(self, closure, w):
         groups = self.param_groups
-        if closure is None and self.native and self._step_cached(groups):
+        if closure is None and self.native and (self._step_cached(groups) if w is None else self._step_cached(groups, w)):
             return None
         if closure is not None or any(g["dampening"] != 0 or g["nesterov"] or g.get("maximize", False) for g in groups):
-            return super().step(closure)
+            return self._step_stock(closure, w)
         params, grads, wds, lrs, moms = [], [], [], [], []
         for g in groups:
             for p in g["params"]:
                 if p.grad is None:  # (torch.optim.SGD's rule; a parameter frozen during the run keeps a zero gradient -- comm.py)
                     continue
                 if p.grad.is_sparse:
-                    return super().step(closure)
+                    return self._step_stock(closure, w)
                 params.append(p)
                 grads.append(p.grad)
                 wds.append(float(g["weight_decay"]))
@@ -63,7 +89,7 @@ class GroupFusedSGD(torch.optim.SGD):
             return None
         if self.native and all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and q.is_contiguous() and q.dtype == torch.float32
                for p, q in zip(params, grads)):
-            return self._step_native(params, grads, wds, lrs, moms)
+            return self._step_native(params, grads, wds, lrs, moms, w)
         d = torch._foreach_add(grads, torch._foreach_mul(params, wds)) if any(wds) else grads
         if any(moms):
             fresh = {i for i, p in enumerate(params) if self.state[p].get("momentum_buffer") is None}
@@ -78,9 +104,11 @@ class GroupFusedSGD(torch.optim.SGD):
         else:
             upd = d
         torch._foreach_add_(params, torch._foreach_mul(upd, [-lr for lr in lrs]))
+        if w is not None:
+            self._ema_foreach(params, w)
         return None
 
-    def _step_native(self, params, grads, wds, lrs, moms):
+    def _step_native(self, params, grads, wds, lrs, moms, w=None):
         import numpy as np
 
         from .. import _C
@@ -98,6 +126,13 @@ class GroupFusedSGD(torch.optim.SGD):
                     for p, q, b, lr, wd, m in zip(params, grads, bufs, lrs, wds, moms))
         cache = self.__dict__.setdefault("_native_tables", {})
         sig = tuple(k[:3] for k in key)
+        emas = None
+        if w is not None:  # the tables gain the EMA pointers: 40-byte records {p, g, buf, ema, n}
+            emas = [self.ema.tensor_of(p) for p in params]
+            if not all(e.is_cuda and e.dtype == torch.float32 and e.is_contiguous() and e.shape == p.shape and e.device == p.device
+                       for e, p in zip(emas, params)):
+                raise RuntimeError("GroupFusedSGD: the EMA tensors must be contiguous float32 on the parameters' device")
+            sig = tuple(k + (e.data_ptr(),) for k, e in zip(sig, emas))
         part = tuple((lr, wd, m) for _, _, _, lr, wd, m in key)
         hit = cache.get("tables")
         if hit is None or hit[0] != sig or hit[1] != self._partition_of(part):
@@ -108,10 +143,10 @@ class GroupFusedSGD(torch.optim.SGD):
             tables = []
             dev = params[0].device
             for t, idx in by.items():
-                items = np.zeros((len(idx), 4), dtype=np.int64)
+                items = np.zeros((len(idx), 4 if emas is None else 5), dtype=np.int64)
                 blocks = []
                 for j, i in enumerate(idx):
-                    items[j] = (key[i][0], key[i][1], key[i][2], params[i].numel())
+                    items[j] = sig[i] + (params[i].numel(),)
                     blocks.extend((j, c) for c in range((params[i].numel() + chunk - 1) // chunk))
                 tables.append((idx[0], torch.from_numpy(items.view(np.uint8).reshape(-1)).to(dev),
                                torch.tensor(blocks, dtype=torch.int32, device=dev).reshape(-1, 2)))
@@ -119,7 +154,10 @@ class GroupFusedSGD(torch.optim.SGD):
             cache["tables"] = hit
         use_wd = any(wds)
         for first, items, blocks in hit[2]:
-            _C.sgd_momentum_multi(items, blocks, lrs[first], wds[first], moms[first], use_wd)
+            if emas is None:
+                _C.sgd_momentum_multi(items, blocks, lrs[first], wds[first], moms[first], use_wd)
+            else:
+                _C.sgd_momentum_ema_multi(items, blocks, lrs[first], wds[first], moms[first], use_wd, w)
         # what the next steps check instead of rebuilding all of the above: every parameter's gradient pointer (None = no
         # gradient) and, per launch, the group whose scalars it reads and the groups that must agree with it
         index = {id(p): gi for gi, g in enumerate(self.param_groups) for p in g["params"]}
@@ -137,9 +175,13 @@ class GroupFusedSGD(torch.optim.SGD):
                 b = used.get(id(p)) if live else None
                 every.append((p, p.data_ptr() if live else 0, p.grad.data_ptr() if live else 0, b, 0 if b is None else b.data_ptr()))
         cache["fast"] = (len(self.param_groups), every, launches)
+        # ... and, with an EMA attached, the average of every updated parameter (``ModelEma.load_state_dict`` replaces them)
+        cache.pop("fast_ema", None)
+        if emas is not None:
+            cache["fast_ema"] = (self.ema, [(p, e, e.data_ptr()) for p, e in zip(params, emas)])
         return None
 
-    def _step_cached(self, groups):
+    def _step_cached(self, groups, w=None):
         """The step of a run in steady state -- same parameters, same gradient buffers, same partition into (lr, wd, momentum)
         classes as the last full step -- without the per-parameter list building of the general path (~0.5 ms of host time
         per step for the teacher's 110 parameters, spent at the step boundary where the GPU has nothing queued).  Returns
@@ -148,6 +190,16 @@ class GroupFusedSGD(torch.optim.SGD):
         fast = cache.get("fast") if cache else None
         if fast is None or fast[0] != len(groups):
             return False
+        averaged = cache.get("fast_ema")
+        if (averaged is None) != (w is None):
+            return False  # an EMA attached or detached since: the tables are of the other record size
+        if averaged is not None:
+            if averaged[0] is not self.ema:
+                return False
+            tensor_of = self.ema.tensor_of
+            for p, e, eptr in averaged[1]:
+                if tensor_of(p) is not e or e.data_ptr() != eptr:
+                    return False
         _, every, launches = fast
         state = self.state
         for p, pptr, gptr, buf, bptr in every:
@@ -177,7 +229,10 @@ class GroupFusedSGD(torch.optim.SGD):
         from .. import _C
         use_wd = any(wd != 0 for _, wd, _ in scalars)  # from the CURRENT scalars: a decay switched on later must apply
         for (lr, wd, mom), (_, items, blocks, _) in zip(scalars, launches):
-            _C.sgd_momentum_multi(items, blocks, lr, wd, mom, use_wd)
+            if w is None:
+                _C.sgd_momentum_multi(items, blocks, lr, wd, mom, use_wd)
+            else:
+                _C.sgd_momentum_ema_multi(items, blocks, lr, wd, mom, use_wd, w)
         return True
 
     def _drop_native_tables(self):

@@ -245,14 +245,20 @@ class PipelinedTrainer:
 
 
 def do_train(cfg, model, data_iter, optimizer, scheduler, max_iter, start_iter=0, log_period=None, logger=None,
-             checkpointer=None, checkpoint_period=None, evaluator=None, test_period=0):
-    """``evaluator`` / ``test_period`` (SOLVER.TEST_PERIOD, trainer.py:174-203): ``evaluator(iteration)`` is called behind every
+             checkpointer=None, checkpoint_period=None, evaluator=None, test_period=0, ema=None):
+    """``ema`` (engine/ema.py::ModelEma, default None: nothing changes): the optimizer moves the weight averages with every
+    step it takes (``optimizer.ema``) and every checkpoint carries them as its ``"ema"`` entry.  What an ``evaluator`` scores
+    is its own business (tools/train_net.py enters ``ema.applied(model)`` around it).
+    ``evaluator`` / ``test_period`` (SOLVER.TEST_PERIOD, trainer.py:174-203): ``evaluator(iteration)`` is called behind every
     iteration whose number -- counted over the whole run, so a resumed run evaluates where the first would have -- is a multiple
     of ``test_period``, after that iteration's checkpoint.  Any callable: the loop knows nothing about datasets.  It may put the
     model into evaluation mode and give it other class embeddings as long as it puts both back
     (engine/evaluation.py::evaluate_in_training)."""
     logger = logger or logging.getLogger("ovis.trainer")
     log_period = log_period or cfg.SOLVER.LOG_PERIOD
+    if ema is not None:
+        optimizer.ema = ema
+    extras = (lambda: {"ema": ema.state_dict()}) if ema is not None else dict
     model.train()
     reducer = comm.BucketedGradReducer(model)
     # (plain train_step for models without a frozen half; gradient accumulation / clipping as the config says)
@@ -296,7 +302,7 @@ def do_train(cfg, model, data_iter, optimizer, scheduler, max_iter, start_iter=0
                 last = now
         if checkpointer is not None and checkpoint_period and (iteration + 1) % checkpoint_period == 0:
             pipe.drain()  # the look-ahead half holds no state, but the weights must be quiescent while they are read
-            checkpointer.save("model_{:07d}".format(iteration + 1), iteration=iteration + 1)
+            checkpointer.save("model_{:07d}".format(iteration + 1), iteration=iteration + 1, **extras())
         if evaluator is not None and test_period > 0 and (iteration + 1) % test_period == 0:
             # the look-ahead thread runs ``forward_frozen`` on this very model object: it has joined before the evaluator
             # changes module modes and class embeddings.  Its outputs depend on frozen weights only and are kept.
@@ -309,7 +315,7 @@ def do_train(cfg, model, data_iter, optimizer, scheduler, max_iter, start_iter=0
     if checkpointer is not None and completed > start_iter:
         if completed < max_iter:
             logger.warning("the data stream ended after %d of %d iterations", completed, max_iter)
-        checkpointer.save("model_final", iteration=completed)
+        checkpointer.save("model_final", iteration=completed, **extras())
     total = time.time() - start
     logger.info("Total training time: %.1f s (%.4f s / it)", total, total / max(max_iter - start_iter, 1))
     return history

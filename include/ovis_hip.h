@@ -1037,6 +1037,34 @@ int ovis_sgd_momentum_multi_f32(const void* items, const void* blocks, int num_b
                                 float momentum, int apply_weight_decay, void* stream);
 int ovis_sgd_chunk_elements(void);
 
+/* The same SGD update with an exponential moving average (EMA) of the weights moved in the same pass
+ * (engine/ema.py::ModelEma, engine/solver.py::GroupFusedSGD.ema; tools/train_net.py --ema DECAY).  The rule:
+ *   - the average covers exactly the parameters with requires_grad (model.named_parameters()), keyed by name, fp32, on the
+ *     parameters' device; frozen weights are shared with the live model and FrozenBN has no moving buffers;
+ *   - the average e starts as a copy of the parameters when the EMA object is made (behind the load of MODEL.WEIGHT), the
+ *     update count at t = 0;
+ *   - at every optimizer step, behind the SGD update of an element:  d_t = min(DECAY, (1 + t) / (10 + t)) in Python doubles,
+ *     w = float32(1 - d_t), and in fp32 without contraction, three separate roundings:
+ *         diff = p_new - e;   e = e + diff * w
+ *     then t += 1, once per optimizer step (with SOLVER.GRADIENT_ACCUMULATION_STEPS > 1 only when the optimizer steps);
+ *   - a parameter the step skips (p.grad is None) gets no EMA update in that step: the EMA update covers exactly the
+ *     elements the SGD update covers (t still advances: it counts optimizer steps);
+ *   - every rank keeps its own average; they are equal by construction, so there is no collective.
+ * items = device array of {float* p; const float* g; float* buf; float* ema; long n} (40 bytes each); blocks, chunking and
+ * the SGD operation sequence are those of ovis_sgd_momentum_multi_f32, so p and buf are bit-identical to it; the EMA lines
+ * are applied to the p just computed, from registers (p, g, buf, ema read, buf, p, ema written once: 28 bytes per element
+ * against 20).  ema_weight = w.  No atomics: every element is written once.  p, buf, ema must not overlap. */
+int ovis_sgd_momentum_ema_multi_f32(const void* items, const void* blocks, int num_blocks, float lr, float weight_decay,
+                                    float momentum, int apply_weight_decay, float ema_weight, void* stream);
+
+/* a[i] <-> b[i] over many tensors in one launch, bit-wise (32-bit words: NaN payloads, signed zeros and subnormals are
+ * exchanged untouched) and in place: items = device array of {void* a; void* b; long n} (24 bytes each, n in 4-byte
+ * elements, a and b disjoint), blocks as above.  How the averaged weights are put into a model and taken out again
+ * (ModelEma.applied): values move, pointers stay -- the optimizer's tables, the reducer's gradient views, the momentum
+ * buffers and every Parameter object stay valid, and two swaps restore every bit.  Evaluations of the averaged weights write
+ * under OUTPUT_DIR/inference_ema/, those of the raw weights under OUTPUT_DIR/inference/. */
+int ovis_swap_multi_f32(const void* items, const void* blocks, int num_blocks, void* stream);
+
 /* The backward of an identity bottleneck (mb/modeling/backbone/resnet.py:290-342: out = relu(conv3(relu(conv2(relu(conv1(x)))))
  * + x); autograd derives the backward) inside a pair-only chain, behind ONE call: g3 [m, channels] = the gradient w.r.t. the
  * block's output, already gated and in pair layout (what ovis_split_gemm_pair_rp_gated of the block above wrote); x / o1 / o2 =

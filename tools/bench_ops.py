@@ -2,7 +2,7 @@
 TFLOP/s) of each hand-written kernel against its algorithmic byte / flop count.
 
     python tools/bench_ops.py [--ops roi_fwd,roi_bwd,nms,focal] [--iters 20]
-Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, transform_window, color_jitter, copy_paste, render, view_merge, rle_targets (``--ops paste,...,rle_targets``).
+Opt-in ops outside the default list: topk, paste, mask_rle, polygons, transform, transform_window, color_jitter, copy_paste, render, view_merge, rle_targets, sgd, sgd_ema (``--ops paste,...,sgd_ema``).
 Prints one JSON object per op.  Timing: HIP events on torch's current stream (the stream the
 kernels are launched on), `iters` launches after 3 warm-ups.
 """
@@ -647,6 +647,82 @@ def main():
                     "dense_route_rounds_ms": [round(v, 4) for v in d_ms], "dense_over_kernel": sorted(d_ms)[1] / sorted(k_ms)[1],
                     "dense_canvas_MB": n_img * n_gt * h1 * w1 * 5 / 1e6, "target_pixels": n_img * n_pos * m_res * m_res,
                     "target_pixels_that_differ_from_the_dense_route": differ})
+    if "sgd" in ops or "sgd_ema" in ops:  # opt-in: the optimizer launches on the teacher configuration's parameter set
+        from cvpr22_cross_modal_pseudo_labeling_amd.config import get_defaults
+        from cvpr22_cross_modal_pseudo_labeling_amd.engine import solver
+        from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model
+
+        cfg = get_defaults()
+        cfg.merge_from_file(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                         "configs/coco_cap_det/zeroshot_mask.yaml"))
+        cfg.freeze()
+        model = build_detection_model(cfg).to(dev)
+        trainable = [p for p in model.parameters() if p.requires_grad]
+        elements = sum(p.numel() for p in trainable)
+        flat = torch.randn(elements + 3, generator=g).to(dev) * 1e-3   # gradient views at odd element offsets, as the reducer's
+        off = 3
+        for p in trainable:
+            p.grad = flat[off:off + p.numel()].view_as(p)
+            off += p.numel()
+        shape = f"{len(trainable)} tensors, {elements} elements"
+
+        def launches_of(opt):
+            """The cached launches of a steady-state step as one callable (the host's list walk left out)."""
+            opt.step()
+            opt.step()
+            fast = opt._native_tables["fast"]
+            groups = opt.param_groups
+            calls = [(items, blocks, float(groups[members[0]]["lr"]), float(groups[members[0]]["weight_decay"]),
+                      float(groups[members[0]]["momentum"])) for members, items, blocks, _ in fast[2]]
+            return calls
+
+        def row(op, fn, bytes_per_element, extra=None):
+            rounds = [timeit(fn, args.iters) for _ in range(3)]
+            ms = sorted(rounds)[1]
+            alg = bytes_per_element * elements
+            res.append(dict({"op": op, "shape": shape, "ms": ms, "rounds_ms": [round(v, 4) for v in rounds],
+                             "bytes_per_element": bytes_per_element, "alg_MB": alg / 1e6, "GBps": alg / ms / 1e6,
+                             "frac_hbm": alg / ms / 1e6 / HBM_PEAK_GBS}, **(extra or {})))
+
+        opt = solver.make_optimizer(cfg, model)
+        plain = launches_of(opt)
+
+        def sgd():
+            for items, blocks, lr, wd, mom in plain:
+                _C.sgd_momentum_multi(items, blocks, lr, wd, mom, True)
+
+        if "sgd" in ops:
+            row("sgd_momentum_multi", sgd, 20, {"launches": len(plain)})
+            row("GroupFusedSGD.step (cached route, host walk included)", opt.step, 20, {"launches": len(plain)})
+        if "sgd_ema" in ops:
+            from cvpr22_cross_modal_pseudo_labeling_amd.engine.ema import ModelEma
+
+            ema = ModelEma(model, 0.999)
+            emas = [ema.tensor_of(p) for p in trainable]
+            w = ema.weight()
+
+            def sgd_then_foreach():  # the existing launch, then the average as three multi-tensor passes
+                sgd()
+                diff = torch._foreach_sub(trainable, emas)
+                torch._foreach_mul_(diff, w)
+                torch._foreach_add_(emas, diff)
+
+            with torch.no_grad():
+                row("sgd_momentum_multi + 3 foreach passes (EMA)", sgd_then_foreach, 20 + 32, {"launches": len(plain)})
+            opt_ema = solver.make_optimizer(cfg, model)
+            opt_ema.ema = ema
+            fused = launches_of(opt_ema)
+
+            def sgd_ema():
+                for items, blocks, lr, wd, mom in fused:
+                    _C.sgd_momentum_ema_multi(items, blocks, lr, wd, mom, True, w)
+
+            row("sgd_momentum_ema_multi", sgd_ema, 28, {"launches": len(fused)})
+            row("GroupFusedSGD.step with ema (cached route, host walk included)", opt_ema.step, 28, {"launches": len(fused)})
+            swap_ms = timeit(lambda: ema.swap(model), args.iters)   # (an even count of exchanges: the model is as it was)
+            res.append({"op": "swap_multi (ModelEma.swap)", "shape": shape, "ms": swap_ms, "bytes_per_element": 16,
+                        "alg_MB": 16 * elements / 1e6, "GBps": 16 * elements / swap_ms / 1e6,
+                        "frac_hbm": 16 * elements / swap_ms / 1e6 / HBM_PEAK_GBS})
     for r_ in res:
         print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r_.items()}))
 

@@ -1,7 +1,7 @@
 """Inference over the user's COCO-format files, with the command line of ``tools/test_net.py`` plus the catalog:
 
     python -m torch.distributed.run --nproc-per-node N tools/infer_net.py --config-file CFG --dataset-catalog FILE
-        [--data-dir DIR] [--ckpt FILE] KEY VALUE ...
+        [--data-dir DIR] [--ckpt FILE] [--ema] KEY VALUE ...
 
 One process per GPU; the weights come from ``--ckpt`` / ``MODEL.WEIGHT`` / the last checkpoint of OUTPUT_DIR
 (utils/checkpoint.py).  Every name of DATASETS.TEST is resolved through the catalog (data/catalog.py), read through the raw
@@ -47,7 +47,11 @@ deleted, those that fall below ``--soft-nms-min-score`` (default MODEL.ROI_HEADS
 ``scores`` are the decayed ones and DETECTIONS_PER_IMG ranks by them; ``--soft-nms-sigma`` (default 0.5) is the Gaussian's
 width, the IoU threshold is MODEL.ROI_HEADS.NMS.  It composes with ``--bbox-vote`` (the vote weighs with the candidates'
 original scores) and ``--mask-aug``.  ``tools/test_net.py`` stays the
-synthetic-stream tool; LVIS scoring is outside this build.
+synthetic-stream tool; LVIS scoring is outside this build.  ``--ema`` loads the checkpoint's ``"ema"`` entry (the weight
+average of ``tools/train_net.py --ema``, engine/ema.py) over the model's trainable parameters before inference and writes
+everything under ``<OUTPUT_DIR>/inference_ema/<name>/`` instead: ``inference_ema`` always means averaged weights, ``inference``
+raw ones.  It only changes which weights are loaded, so it composes with every other flag; a checkpoint without the entry is
+an error naming the file.
 """
 import argparse
 import json  # noqa: F401  (the module's names stay what they were before engine/evaluation.py took the functions)
@@ -70,6 +74,7 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import calibrate_stem
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import build_transforms  # noqa: E402,F401
 from cvpr22_cross_modal_pseudo_labeling_amd.engine.bbox_aug import evaluating_post_processor  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import coco_eval, coco_results, comm, inference, proposal_recall, visualize  # noqa: E402,F401
+from cvpr22_cross_modal_pseudo_labeling_amd.engine.ema import load_ema_weights  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.engine.evaluation import (run_datasets, run_rpn_recall, save_evaluation,  # noqa: E402,F401
                                                                        save_visualizations)
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
@@ -135,6 +140,14 @@ def main(argv=None):
     parser.epilog = "Soft-NMS flags (in front of the KEY VALUE overrides, like every flag) -- " + "; ".join(
         f"{a.option_strings[0]} {a.metavar or '{' + ','.join(a.choices) + '}'}: {a.help}" for a in soft_parser._actions)
     soft, argv = soft_parser.parse_known_args(sys.argv[1:] if argv is None else argv)
+    # ... and so has --ema (it only changes which weights are loaded and the folder everything is written under)
+    ema_parser = argparse.ArgumentParser(add_help=False, allow_abbrev=False)
+    ema_parser.add_argument("--ema", action="store_true",
+                            help="test the checkpoint's \"ema\" entry (the weight average of tools/train_net.py --ema) instead "
+                                 "of its raw weights, and write under OUTPUT_DIR/inference_ema/<name>/; a checkpoint without "
+                                 "the entry is an error")
+    parser.epilog += ".  --ema (in front of the overrides too): " + ema_parser._actions[0].help
+    averaged, argv = ema_parser.parse_known_args(argv)
     args = parser.parse_args(argv)
 
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -208,13 +221,21 @@ def main(argv=None):
     logging.basicConfig(level=logging.INFO if comm.get_rank() == 0 else logging.WARNING,
                         format="%(asctime)s %(name)s %(levelname)s: %(message)s")
     logger = logging.getLogger("ovis.inference")
-    logger.info("Using %d GPUs\n%s %s", world, args, soft)
+    logger.info("Using %d GPUs\n%s %s%s", world, args, soft, " --ema" if averaged.ema else "")
 
     catalog = DatasetCatalog(args.dataset_catalog, args.data_dir)
     model = build_detection_model(cfg).to(device)
     checkpointer = DetectronCheckpointer(cfg, model, save_dir=cfg.OUTPUT_DIR)
     weight = args.ckpt or cfg.MODEL.WEIGHT
     extra = checkpointer.load(weight, use_latest=args.ckpt is None)
+    if averaged.ema:
+        source = checkpointer.get_checkpoint_file() if args.ckpt is None and checkpointer.has_checkpoint() else weight
+        if "ema" not in extra:
+            parser.error(f"--ema: the checkpoint {source or '(none given)'} has no \"ema\" entry (train with "
+                         "tools/train_net.py --ema DECAY)")
+        load_ema_weights(model, extra["ema"])
+        logger.info("--ema: the averaged weights of %s (update count %d) over %d trainable tensors", source,
+                    int(extra["ema"]["num_updates"]), len(extra["ema"]["params"]))
     if not weight and not extra and not checkpointer.has_checkpoint():
         images, _ = make_batch(1, device=device, seed=7)
         calibrate_stem_bn(model, images)  # random init only: give the frozen BN usable statistics
@@ -226,12 +247,13 @@ def main(argv=None):
                                 post.score_thresh if soft.soft_nms_min_score is None else soft.soft_nms_min_score)
         logger.info("Soft-NMS in place of the per-class NMS: %s, Nt %s", post.soft_nms, post.nms)
     if args.rpn_recall:
-        run_rpn_recall(cfg, model, catalog, device, logger)
+        run_rpn_recall(cfg, model, catalog, device, logger, **({"folder": "inference_ema"} if averaged.ema else {}))
     else:
         for name, preds in run_datasets(cfg, model, catalog, device, logger, args.visualize, args.vis_threshold,
                                         args.evaluate, args.export_results, args.recall, args.bbox_vote,
                                         args.mask_aug, args.boundary_ap, args.lvis,
-                                        **({"error_analysis": True} if args.error_analysis else {})).items():
+                                        **({"error_analysis": True} if args.error_analysis else {}),
+                                        **({"folder": "inference_ema"} if averaged.ema else {})).items():
             if preds is not None:
                 logger.info("%s: %d images, %d detections", name, len(preds), sum(len(p) for p in preds))
     if world > 1:

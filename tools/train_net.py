@@ -1,7 +1,7 @@
 """Training entry point with the reference's command line (tools/train_net.py:162-234):
 
     python -m torch.distributed.run --nproc-per-node N tools/train_net.py --config-file CFG [--dataset-catalog FILE]
-        [--color-jitter] [--scale-jitter LO HI [--crop-size H W] [--copy-paste P]] [--evaluate] [--boundary-ap] [--lvis] [--skip-test] KEY VALUE ...
+        [--color-jitter] [--scale-jitter LO HI [--crop-size H W] [--copy-paste P]] [--evaluate] [--boundary-ap] [--lvis] [--skip-test] [--ema DECAY] KEY VALUE ...
 
 One process per GPU (RCCL via torch.distributed, env:// rendezvous), config = defaults <- yaml <- trailing overrides,
 frozen before use.  Without ``--dataset-catalog`` the data stream is the synthetic COCO-shaped generator
@@ -33,6 +33,15 @@ nothing to skip.  The validation loss of the reference's loop is not computed (e
 SOLVER.SKIP_VAL_LOSS True; the reference's version runs the training forward, which moves the student-teacher model's
 iteration count), TEST.BBOX_AUG belongs to ``tools/infer_net.py``, and TensorBoard and best-checkpoint tracking are outside
 this build.
+
+``--ema DECAY`` (a float in (0, 1)) keeps an exponential moving average of every trainable parameter, moved inside the fused
+SGD launch at every optimizer step (engine/ema.py, csrc/optim.hip; include/ovis_hip.h states the rule:
+d_t = min(DECAY, (1 + t) / (10 + t)), fp32 averages, made behind the checkpoint load, one per rank and no collective).  Every
+checkpoint carries it as its ``"ema"`` entry, and a resumed run restores it (MODEL.LOAD_TRAINER_STATE).  With ``--evaluate`` the
+periodic scoring runs on the AVERAGED weights and writes ``OUTPUT_DIR/inference_ema/<name>/coco_results_<iteration:07d>.json``,
+and the final test runs twice: on the raw weights into ``inference/`` as without the flag, then on the averaged ones into
+``inference_ema/``.  ``inference_ema`` always means averaged weights, ``inference`` always raw.  Without the flag nothing
+changes: no tensor, no launch, no checkpoint key, no file.
 """
 import argparse
 import functools
@@ -63,6 +72,7 @@ from cvpr22_cross_modal_pseudo_labeling_amd.data.synthetic import (LVIS_VOCAB, R
 from cvpr22_cross_modal_pseudo_labeling_amd.data.transforms import (JITTER_KEYS, build_transforms, check_color_jitter,  # noqa: E402
                                                                         check_copy_paste, check_scale_jitter)
 from cvpr22_cross_modal_pseudo_labeling_amd.engine import comm, evaluation, solver, trainer  # noqa: E402
+from cvpr22_cross_modal_pseudo_labeling_amd.engine.ema import ModelEma  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.modeling.detector import build_detection_model  # noqa: E402
 from cvpr22_cross_modal_pseudo_labeling_amd.utils.checkpoint import DetectronCheckpointer  # noqa: E402
 
@@ -100,8 +110,10 @@ def make_data_source(cfg, ims_per_gpu, raw_input=False, dataset=None, start_iter
 
 def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=False, raw_input=False, dataset_catalog=None,
           data_dir="", seed=0, evaluate=False, skip_test=False, boundary_ap=False, lvis=False, color_jitter=False,
-          scale_jitter=None, crop_size=None, copy_paste=None):
-    """``evaluate``: score every DATASETS.TEST set behind every SOLVER.TEST_PERIOD-th iteration
+          scale_jitter=None, crop_size=None, copy_paste=None, ema_decay=None):
+    """``ema_decay`` = DECAY in (0, 1): a weight average moved by every optimizer step (engine/ema.py), saved with every
+    checkpoint, scored by the periodic evaluation and by a second final test, both into OUTPUT_DIR/inference_ema/.
+    ``evaluate``: score every DATASETS.TEST set behind every SOLVER.TEST_PERIOD-th iteration
     (engine/evaluation.py::evaluate_in_training) and, unless ``skip_test``, run the final test behind the last one
     (``evaluation.run_datasets``: predictions.pth and coco_results.json under OUTPUT_DIR/inference/<name>/).
     ``boundary_ap``: both also score the ``boundary`` task (engine/coco_eval.py: Boundary AP), behind ``segm``.  ``lvis``:
@@ -152,6 +164,14 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
             "teacher's at the first iteration (set MODEL.RESUME True to keep them)", cfg.OUTPUT_DIR)
     if distributed:
         comm.broadcast_parameters(model)
+    ema = None
+    if ema_decay is not None:  # behind the checkpoint load (and the broadcast: every rank's average starts equal)
+        ema = ModelEma(model, ema_decay)
+        if cfg.MODEL.LOAD_TRAINER_STATE and "ema" in extra:
+            ema.load_state_dict(extra["ema"])
+        else:
+            logging.getLogger("ovis.trainer").info("--ema %s: no average restored, it starts from the loaded weights "
+                                                   "(%d tensors, update count 0)", ema_decay, len(ema.tensors))
 
     # host batches come from DATALOADER.NUM_WORKERS worker processes (the training process' interpreter lock is busy feeding
     # two HIP streams) and are staged through pinned memory on a copy stream, two batches ahead
@@ -171,11 +191,18 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
         evaluator = functools.partial(evaluation.evaluate_in_training, cfg, model, catalog, device,
                                       train_class_embeddings=e_seen, logger=logger, boundary_ap=boundary_ap,
                                       lvis=lvis)
+        if ema is not None:  # the periodic scoring sees the averaged weights and says so in where it writes
+            scoring = functools.partial(evaluator, folder="inference_ema")
+
+            def evaluator(iteration):
+                with ema.applied(model):
+                    return scoring(iteration)
     try:
         history = trainer.do_train(cfg, model, data, optimizer, scheduler, max_iter, start_iter=start_iter,
                                    checkpointer=checkpointer if save_checkpoints else None,
                                    checkpoint_period=cfg.SOLVER.CHECKPOINT_PERIOD, evaluator=evaluator,
-                                   test_period=cfg.SOLVER.TEST_PERIOD if evaluate else 0)
+                                   test_period=cfg.SOLVER.TEST_PERIOD if evaluate else 0,
+                                   **({"ema": ema} if ema is not None else {}))
     finally:
         data.close()
     if evaluate and not skip_test:  # tools/train_net.py:129-159: the final test, the route of tools/infer_net.py --evaluate
@@ -183,6 +210,11 @@ def train(cfg, local_rank, distributed, max_iter, ims_per_gpu, save_checkpoints=
         evaluation.run_datasets(cfg, model, catalog, device, logging.getLogger("ovis.inference"), evaluate=True,
                                 boundary_ap=boundary_ap, lvis=lvis)
         comm.synchronize()
+        if ema is not None:  # ... and once more on the averaged weights
+            with ema.applied(model):
+                evaluation.run_datasets(cfg, model, catalog, device, logging.getLogger("ovis.inference"), evaluate=True,
+                                        boundary_ap=boundary_ap, lvis=lvis, folder="inference_ema")
+            comm.synchronize()
     return history
 
 
@@ -235,6 +267,12 @@ def main(argv=None):
                              "occluded part, their boxes are recomputed, and instances left without extent are dropped.  Polygon "
                              "ground truth only.  Captions are carried unchanged: a pasted object is not named by the "
                              "destination's caption, and a covered one may still be named")
+    parser.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                        help="keep an exponential moving average of the trainable weights, DECAY a float in (0, 1): moved "
+                             "inside the fused SGD launch at every optimizer step with d_t = min(DECAY, (1 + t) / (10 + t)), "
+                             "saved as the checkpoints' \"ema\" entry and restored on resume; with --evaluate the periodic "
+                             "scoring and a second final test run on the averaged weights and write under "
+                             "OUTPUT_DIR/inference_ema/ (inference/ always holds the raw weights' results)")
     parser.add_argument("--data-dir", default="", help="where the catalog's relative paths are taken from")
     parser.add_argument("--seed", type=int, default=0,
                         help="with --dataset-catalog: the run's seed of the input transform's random draws (sizes, flips)")
@@ -248,6 +286,8 @@ def main(argv=None):
         cfg.merge_from_file(args.config_file)
     cfg.merge_from_list(args.opts or [])
     cfg.freeze()
+    if args.ema is not None and not 0.0 < args.ema < 1.0:
+        parser.error(f"--ema takes a decay in (0, 1), got {args.ema}")
     if args.evaluate and not args.dataset_catalog:
         parser.error("--evaluate runs the DATASETS.TEST sets of the catalog through the model: give --dataset-catalog")
     if args.evaluate and not cfg.OUTPUT_DIR:
@@ -317,7 +357,8 @@ def main(argv=None):
           save_checkpoints=bool(cfg.OUTPUT_DIR) and not args.no_checkpoints, raw_input=args.raw_input,
           dataset_catalog=args.dataset_catalog, data_dir=args.data_dir, seed=args.seed, evaluate=args.evaluate,
           skip_test=args.skip_test, boundary_ap=args.boundary_ap, lvis=args.lvis, color_jitter=args.color_jitter,
-          scale_jitter=args.scale_jitter, crop_size=args.crop_size, copy_paste=args.copy_paste)
+          scale_jitter=args.scale_jitter, crop_size=args.crop_size, copy_paste=args.copy_paste,
+          **({"ema_decay": args.ema} if args.ema is not None else {}))
     if distributed:
         dist.destroy_process_group()
 
