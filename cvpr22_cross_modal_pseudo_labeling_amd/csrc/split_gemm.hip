@@ -1471,6 +1471,9 @@ extern "C" int ovis_split_gemm_pair_tn(const void* g_pair, long g_row_bytes, con
   if (!g_pair || !x_pair || !c_slabs || m > 0x7fffff00L) return OVIS_EINVAL;
   const int T = taps_h * taps_w;
   if (T > 1 && (height <= 0 || width <= 0)) return OVIS_EINVAL;
+  // whole maps only: a tap reads row m + dy * W + dx of every row whose shifted pixel lies inside the map, which for the
+  // rows of a partial last map would be up to (KH / 2) * W + KW / 2 rows behind the operand
+  if (T > 1 && m % ((long)height * width) != 0) return OVIS_EINVAL;
   if (n % 128 != 0 || channels % 128 != 0 ||
       g_row_bytes % 16 != 0 || x_row_bytes % 16 != 0 || ((uintptr_t)g_pair & 15) || ((uintptr_t)x_pair & 15) ||
       ((uintptr_t)c_slabs & 15))
@@ -1659,6 +1662,8 @@ static int split_gemm_pair_impl(const void* a_pair, long a_row_bytes, const void
   if (pool && (pool_rows < 32 || pool_rows > 64 || ((uintptr_t)pool & 15))) return OVIS_ERANGE;
   const int T = taps_h * taps_w;
   if (T > 1 && (height <= 0 || width <= 0 || height > 32767 || width > 32767 || channels2 != 0)) return OVIS_EINVAL;
+  // whole maps only: the rows of a partial last map would read their taps behind the operand (as ovis_split_gemm_pair_tn)
+  if (T > 1 && m % ((long)height * width) != 0) return OVIS_EINVAL;
   if (channels2 != 0 && !a2_pair) return OVIS_EINVAL;
   // one epilogue operand -- or the pair shortcut together with a gate (the DUAL kernels, plain products only)
   const bool dual = residual_pair && gate_pair && !residual;

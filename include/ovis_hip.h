@@ -529,7 +529,9 @@ int ovis_im2col_nchw_pair_f32(const float* src, void* dst_pair, int num, int cha
  *            applies the epilogue (deterministic).  Without a workspace the un-split grid runs.
  *   config : 0 = choose.  Otherwise a bit set for tests and A/B measurements: 1 = one LDS stage, 2 = two
  *            stages, 4 = never use the halo form, 8 = no K slices.
- * channels % 32 == 0, channels2 % 32 == 0, n % 4 == 0, 16-byte aligned pointers and strides (else OVIS_ERANGE). */
+ * channels % 32 == 0, channels2 % 32 == 0, n % 4 == 0, 16-byte aligned pointers and strides (else OVIS_ERANGE).
+ * More than one tap: m is a multiple of height * width (whole maps; the rows of a partial last map would read their taps
+ * behind a_pair), else OVIS_EINVAL before any launch -- also through ovis_split_gemm_pair_gated_ws. */
 size_t ovis_split_gemm_pair_workspace_bytes(long m, int n, int channels, int channels2, int taps_h, int taps_w,
                                             int width);
 /* The same query for a launch with a non-zero `config` (bit 16 = co-scheduled launch: slices chosen for least total work;
@@ -554,7 +556,9 @@ int ovis_split_gemm_pair_rp(const void* a_pair, long a_row_bytes, const void* b_
  * G[m, n] * X[row(m, tap), c]  (G = gated output gradient [m, n], X = the layer input [m, channels], both pair
  * rows; taps as in ovis_split_gemm_pair, X read shifted with zeros outside the map).  The rows are cut into
  * `slices` (ovis_split_gemm_tn_slices gives a count that fills the chip); the caller sums the slabs.
- * n % 128 == 0, channels % 128 == 0 (else OVIS_ERANGE); any map size.
+ * n % 128 == 0, channels % 128 == 0 (else OVIS_ERANGE); any map size, but whole maps: with more than one tap m is a
+ * multiple of height * width (the rows of a partial last map would read X behind the operand), else OVIS_EINVAL before
+ * any launch.  A slice count above the number of 32-row steps is served: the slabs of the empty slices are zero-filled.
  * On maps of at most 64 pixels (m a multiple of height * width, at most 5 x 5 taps) a tap contracts over its in-map rows
  * only, every tap is cut into `slices` slices of its own rows and the taps with the most rows are dispatched first;
  * the slab layout is the same.  ovis_split_gemm_tn_map_slices scores that work (and equals ovis_split_gemm_tn_slices
